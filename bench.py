@@ -15,7 +15,10 @@ For N>1 every rank gets its own shard of the same size (weak scaling), as the re
 `python bench.py --gpus N` with N>1 and no WORLD_SIZE in the environment re-launches itself under
 torch.distributed.run with N ranks (backend nccl = RCCL); launched under torchrun it uses the environment as is.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run sets up, warms up, times the --steps steps, writes the last step's outputs if --dump-outputs DIR is given (the logits
+of each mate and the labels a caller of the timed path receives, as DIR/<name>.npy in float32; a fixed seeded sample of the rows
+when they would exceed 64 MB, with the rows' indices in sample_rows.npy) and prints ONE JSON line (rank 0) with the driver's
+contract fields and the configuration. Everything else runs only under --full, which adds to the line and to bench_full.json
   config.kernel_only_reads_per_s - timed region (i): the same steps with the read bytes already resident in HBM
   roofline     - the recurrence kernel against the dense MFMA peak: the algorithmic FLOPs of the steps the kernel EXECUTES
                  (steps x 131072 + 1024 per read; the steps a prefix-state table row stands for are not counted -
@@ -224,7 +227,7 @@ def compact(full):
     tests/test_gpu_bench.py): contract keys, a dozen config scalars, the roofline's numbers, cpu_baseline, parity_sample and one
     scalar per alt / e2e leg. Everything else is in bench_full.json (--full-out)."""
     r3 = lambda x: (float("%.5g" % x) if isinstance(x, float) else x)      # noqa: E731
-    c, rf = full["config"], full["roofline"]
+    c, rf = full["config"], full.get("roofline")          # (no roofline in a plain run: --full measures it)
     out = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                     "vs_baseline", "dtype", "data")}
     out["config"] = {k: r3(c[k]) for k in ("workload", "timed_region", "per_step_per_gpu", "read_len", "ensure", "kernel_variant", "parallelism",
@@ -233,12 +236,13 @@ def compact(full):
     out["config"]["prefix_k"] = c["prefix_table"]["k"]
     out["config"]["refine_band"] = c["refine"]["band"]
     out["config"]["label_counts"] = [c["label_counts"][k] for k in ("non_rrna", "rrna", "unclassified")]
-    out["roofline"] = {k: r3(rf[k]) for k in ("bound", "achieved", "peak", "unit", "frac", "kernel", "launches", "avg_launch_ms", "traffic",
-                                              "traffic_over_algorithmic", "steps_executed_over_steps", "frac_counting_table_steps",
-                                              "mfma_pipe_frac", "algorithmic_flops_per_launch", "algorithmic_bytes_per_launch", "effective_clock_ghz",
-                                              "package_power_w") if k in rf}
-    if isinstance(rf.get("traffic_source"), str):
-        out["roofline"]["traffic_source"] = rf["traffic_source"][:120]
+    if rf is not None:
+        out["roofline"] = {k: r3(rf[k]) for k in ("bound", "achieved", "peak", "unit", "frac", "kernel", "launches", "avg_launch_ms", "traffic",
+                                                  "traffic_over_algorithmic", "steps_executed_over_steps", "frac_counting_table_steps",
+                                                  "mfma_pipe_frac", "algorithmic_flops_per_launch", "algorithmic_bytes_per_launch",
+                                                  "effective_clock_ghz", "package_power_w") if k in rf}
+        if isinstance(rf.get("traffic_source"), str):
+            out["roofline"]["traffic_source"] = rf["traffic_source"][:120]
     for name, key in (("alt_fp32", "alt_fp32_kernel"), ("alt_no_prefix_table", "alt_no_prefix_table")):
         if key in full:
             out[name + "_reads_per_s"] = r3(full[key]["value"])
@@ -269,19 +273,43 @@ def compact(full):
             out["cpu_baseline"]["sample"] = cb["sample_short"]
     if "parity_sample" in full:
         out["parity_sample"] = {k: r3(v) for k, v in full["parity_sample"].items() if k != "vs"}
-    out["full_record"] = os.path.basename(full.get("_full_out", "bench_full.json"))
+    if "_full_out" in full:
+        out["full_record"] = os.path.basename(full["_full_out"])
     return out
 
 
+DUMP_CAP_BYTES = 64 * 10 ** 6       # --dump-outputs: at most this much array data in all
+
+
+def dump_outputs(d, logits, labels):
+    """--dump-outputs DIR: what the timed path computed in its last step, as a caller receives it - the logits [P, 2] of each mate
+    (logits_r1, logits_r2) and the labels [P] (pair labels for paired-end: 0, 1, -1) - as DIR/<name>.npy in float32. Above
+    DUMP_CAP_BYTES the same fixed, seeded sample of rows is taken from every array, their indices in sample_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = dict(("logits_r%d" % (m + 1), lg) for m, lg in enumerate(logits))
+    arrays["labels"] = labels
+    n = int(labels.shape[0])
+    row_bytes = sum(4 * (t.numel() // n) for t in arrays.values())
+    rows = None
+    if n * row_bytes > DUMP_CAP_BYTES:
+        rows = np.sort(np.random.default_rng(20240601).choice(n, size=DUMP_CAP_BYTES // (row_bytes + 8), replace=False))
+        np.save(os.path.join(d, "sample_rows.npy"), rows.astype(np.float64))
+    for name, t in arrays.items():
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a if rows is None else a[rows], dtype=np.float32))
+
+
 def emit(full, args):
-    """bench_full.json (everything) + the compact line as the LAST line of stdout"""
-    path = args.full_out or os.path.join(ROOT, "bench_full.json")
-    full["_full_out"] = path
-    try:
-        with open(path, "w") as fh:
-            json.dump(full, fh, indent=1)
-    except OSError as e:
-        sys.stderr.write("bench.py: cannot write %s: %s\n" % (path, e))
+    """bench_full.json (everything; with --full or --full-out) + the compact line as the LAST line of stdout"""
+    if args.full_out or args.full:
+        path = args.full_out or os.path.join(ROOT, "bench_full.json")
+        full["_full_out"] = path
+        try:
+            with open(path, "w") as fh:
+                json.dump(full, fh, indent=1)
+        except OSError as e:
+            sys.stderr.write("bench.py: cannot write %s: %s\n" % (path, e))
     line = json.dumps(compact(full), separators=(",", ":"))
     if args.verbose:
         sys.stderr.write(json.dumps(full) + "\n")
@@ -317,9 +345,17 @@ def main():
     ap.add_argument("--traffic", default="live", choices=["live", "off"],
                     help="live: collect FETCH_SIZE/WRITE_SIZE with rocprofv3 --pmc over a child run of this command (adds ~40 s)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--full-out", default=None, help="where the full record goes (default: bench_full.json next to this script)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: region (i), the roofline (per-launch hipEvents, "
+                         "rocprofv3 --pmc child runs, clock and power samples), the alt kernels, the encoders, device gzip, the CLI legs, "
+                         "the CPU baseline and its parity sample; the full record goes to bench_full.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step (rank 0) as DIR/<name>.npy in float32")
+    ap.add_argument("--full-out", default=None, help="where the full record goes (default with --full: bench_full.json next to this script)")
     ap.add_argument("--verbose", action="store_true", help="also print the full record on stderr")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
@@ -383,13 +419,14 @@ def main():
             rr += float(first.sum().item())
             nl += 1
         return se / nl, rr / nl
-    steps_exec_sum, rows_read = executed(PK)
-    flops_all_steps = float(steps_full.sum().item()) * 131072 + 1024.0 * P
-    flops_per_launch = steps_exec_sum * 131072 + 1024.0 * P
-    bytes_survey = float(steps_full.sum().item()) + P * (4 + 8 + 1)       # 113 B per 100 bp read
-    bytes_offsets = P * 8.0                                               # this ABI's int64 start offset per read (not in §8d's count)
-    bytes_table = rows_read * 1024.0                                      # ONE 1 KiB table row per read that starts from the table
-    exec_steps_frac = steps_exec_sum / float(steps_full.sum().item())
+    if args.full:                                         # (the roofline's work per launch: --full only)
+        steps_exec_sum, rows_read = executed(PK)
+        flops_all_steps = float(steps_full.sum().item()) * 131072 + 1024.0 * P
+        flops_per_launch = steps_exec_sum * 131072 + 1024.0 * P
+        bytes_survey = float(steps_full.sum().item()) + P * (4 + 8 + 1)       # 113 B per 100 bp read
+        bytes_offsets = P * 8.0                                               # this ABI's int64 start offset per read (not in §8d's count)
+        bytes_table = rows_read * 1024.0                                      # ONE 1 KiB table row per read that starts from the table
+        exec_steps_frac = steps_exec_sum / float(steps_full.sum().item())
     nm = 2 if paired else 1
     # two sets of result buffers: the post-pass of step i (side stream) runs while the recurrences of step i+1 (main stream) write
     # the other set
@@ -408,6 +445,7 @@ def main():
         # stream beside the next step's recurrences. No scan launch over the logits (rounds 2-3 issued rd_refine here: 1.4 ms each).
         model.set_refine_async(16)
     ev_post = [None, None]                                 # post-pass that last read result set k
+    last_lab = [None]                                      # the labels of the last step (--dump-outputs)
 
     def compute(i, a1, a2, after=None):
         """one step: the recurrences of both mates on the main stream; on the side stream (overlapping the next step's recurrences)
@@ -439,6 +477,7 @@ def main():
             else:
                 module_arch.count_labels(lab8, counts)
                 lab = lab8.view(torch.int8)
+            last_lab[0] = lab
             fin = after(lab) if after else None
             ev_post[k] = torch.cuda.Event(blocking=True)   # the host SLEEPS in .synchronize() (8 ranks share 16 host cores)
             ev_post[k].record(post)
@@ -559,20 +598,25 @@ def main():
     timed_path(args.warmup)
     sync()
     counts.zero_()
-    model.profile_enable(True)
-    sync()
-    th0 = thread_cpu()
-    sampler = GpuSampler(torch, dev).start()
+    if args.full:
+        model.profile_enable(True)
+        sync()
+        th0 = thread_cpu()
+        sampler = GpuSampler(torch, dev).start()
     t0, c0 = time.perf_counter(), time.process_time()
     timed_path(args.steps)
     sync()
     dt, cpu_s = time.perf_counter() - t0, time.process_time() - c0      # cpu_s: user + system time of ALL threads of this rank
-    gpu_state = sampler.stop()
-    th1 = thread_cpu()
-    by_thread = sorted(((th1[t][1] - th0.get(t, (None, 0.0))[1], th1[t][0]) for t in th1), reverse=True)
-    by_thread = [{"thread": nm, "cpu_s": round(c, 3)} for c, nm in by_thread if c >= 0.01][:6]
-    launches, kms = model.profile_read()
-    model.profile_enable(False)
+    gpu_state, by_thread, launches, kms = None, None, 0, 0.0
+    if args.full:
+        gpu_state = sampler.stop()
+        th1 = thread_cpu()
+        by_thread = sorted(((th1[t][1] - th0.get(t, (None, 0.0))[1], th1[t][0]) for t in th1), reverse=True)
+        by_thread = [{"thread": nm, "cpu_s": round(c, 3)} for c, nm in by_thread if c >= 0.01][:6]
+        launches, kms = model.profile_read()
+        model.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, lgs[(args.steps - 1) & 1], last_lab[0])
     rdist.reduce_counts(counts)
     on_dev = not multi or backend == "nccl"
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev if on_dev else "cpu")
@@ -594,7 +638,7 @@ def main():
 
     # ---- region (i): the same steps with the bytes resident in HBM -------------------------------------------------------------
     dt_res = None
-    if not args.resident_only:
+    if args.full and not args.resident_only:
         sync()
         t1 = time.perf_counter()
         run_resident(args.steps)
@@ -608,12 +652,12 @@ def main():
     if rank == 0:
         mult = 2.0 if paired else 1.0
         avg_ms = kms / max(launches, 1)
-        achieved = flops_per_launch / (avg_ms * 1e-3) / 1e12 if launches else None
+        achieved = flops_per_launch / (avg_ms * 1e-3) / 1e12 if launches else None      # (launches: --full only)
         base = ("mfma_f16x3_t32" if variant.startswith(("mfma_f16x3_t32", "t32_")) else "mfma_f32" if variant.startswith("mfma_f32") else variant)
         peak = PEAKS[base]
         kname = "rd_lstm_%s_kernel" % base
         traffic, traffic_src = None, "not collected (--traffic off or N>1)"
-        if args.traffic == "live" and world == 1:
+        if args.full and args.traffic == "live" and world == 1:
             tj, err = pmc_traffic(args, "rd_lstm_")
             if tj:
                 traffic = tj["hbm_bytes_per_launch"]
@@ -642,10 +686,6 @@ def main():
             "config": {"workload": wl_text + ", %d %s/step/GPU x %d steps (%.1f M total); %s"
                                    % (P, "pairs" if paired else "reads", args.steps, total_pairs / 1e6, region),
                        "timed_region": "i" if args.resident_only else "ii",
-                       "timed_regions": "value = (ii) pinned host bytes -> host labels; kernel_only_reads_per_s = (i) bytes resident in HBM; "
-                                        "e2e_cli_reads_per_s = (iii) the whole CLI on a FASTQ file in tmpfs (SURVEY 8d)",
-                       "kernel_only_reads_per_s": (mult * total_pairs / dt_res) if dt_res else None,
-                       "device_path_over_kernel_only": (dt_res / dt) if dt_res else None,
                        "pairs_per_s": (total_pairs / dt) if paired else None, "per_step_per_gpu": P,
                        "read_len": RL if args.workload != "var300" else "40-300",
                        "ensure": args.ensure if paired else None,
@@ -656,7 +696,6 @@ def main():
                        "parallelism": "reads sharded x%d, label gather to rank 0" % world,
                        "host_cpu_seconds_per_rank_in_timed_region": [round(c, 4) for c in cpu_ranks],
                        "host_cores_busy": sum(cpu_ranks) / dt, "host_cores_usable": usable_cores(),
-                       "host_cpu_seconds_by_thread_rank0": by_thread,
                        "rccl_ranks": world, "dist_backend": backend, "forced_dist": bool(multi and world == 1),
                        "ranks": rank_info, "gather_self_check": "passed" if rank_info else None,
                        "prefix_table": {"k": PK, "bytes": (4 ** PK + 1) * 1024 if PK else 0,
@@ -671,33 +710,40 @@ def main():
                                   if pipelined else "inline in rd_classify"},
                        "label_counts": {"non_rrna": c[0], "rrna": c[1], "unclassified": c[2]},
                        "host_labels_nonzero_last_step": host_check},
-            "roofline": {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                         "frac": (achieved / peak) if achieved else None, "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": kname, "launches": launches, "avg_launch_ms": avg_ms,
-                         "effective_clock_ghz": round(gpu_state["sclk_mhz"]["avg"] / 1e3, 3) if gpu_state.get("sclk_mhz") else None,
-                         "package_power_w": gpu_state["power_w"]["avg"] if gpu_state.get("power_w") else None,
-                         "gpu_state_in_timed_region": gpu_states if world > 1 else gpu_state,
-                         "what": "achieved = algorithmic FLOPs of the steps the kernel EXECUTES (steps x 131072 + 1024 per read, SURVEY 8d) / "
-                                 "avg_launch_ms; the steps a prefix-state table row stands for are looked up, not computed, and are not "
-                                 "counted here (frac_counting_table_steps counts them: reads/s x SURVEY 8d FLOPs per read / peak)",
-                         "algorithmic_flops_per_launch": flops_per_launch,
-                         "algorithmic_flops_per_launch_counting_table_steps": flops_all_steps,
-                         "achieved_counting_table_steps": (flops_all_steps / (avg_ms * 1e-3) / 1e12) if launches else None,
-                         "frac_counting_table_steps": (flops_all_steps / (avg_ms * 1e-3) / 1e12 / peak) if launches else None,
-                         "steps_executed_over_steps": exec_steps_frac,
-                         "mfma_flops_executed_per_algorithmic_flop": MFMA_FLOPS_PER_ALGO_FLOP[base],
-                         "mfma_pipe_frac": (achieved * MFMA_FLOPS_PER_ALGO_FLOP[base] / peak) if achieved else None,
-                         "algorithmic_bytes_per_launch": bytes_survey,
-                         "table_bytes_per_launch": bytes_table,
-                         "offset_bytes_per_launch": bytes_offsets,
-                         "traffic_over_algorithmic": (traffic / bytes_survey) if traffic else None,
-                         "traffic_over_algorithmic_plus_table_and_offsets": (traffic / (bytes_survey + bytes_table + bytes_offsets)) if traffic else None,
-                         "traffic_note": "algorithmic_bytes_per_launch = SURVEY 8d (T + 4 + 8 + 1 B per read). The kernel also reads an 8-byte "
-                                         "start offset per read (this ABI's index) and, with the prefix-state table, ONE 1 KiB row per read "
-                                         "that starts from it (table_bytes_per_launch: ~9x the 8d bytes, read once, 40 GB/s of the 8 TB/s; "
-                                         "they buy k of the T steps - alt_no_prefix_table runs without them)" if PK else
-                                         "algorithmic_bytes_per_launch = SURVEY 8d (T + 4 + 8 + 1 B per read); + an 8-byte start offset per read"},
         }
+        if args.full:
+            out["config"].update({
+                "timed_regions": "value = (ii) pinned host bytes -> host labels; kernel_only_reads_per_s = (i) bytes resident in HBM; "
+                                 "e2e_cli_reads_per_s = (iii) the whole CLI on a FASTQ file in tmpfs (SURVEY 8d)",
+                "kernel_only_reads_per_s": (mult * total_pairs / dt_res) if dt_res else None,
+                "device_path_over_kernel_only": (dt_res / dt) if dt_res else None,
+                "host_cpu_seconds_by_thread_rank0": by_thread})
+            out["roofline"] = {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+                               "frac": (achieved / peak) if achieved else None, "traffic": traffic, "traffic_source": traffic_src,
+                               "kernel": kname, "launches": launches, "avg_launch_ms": avg_ms,
+                               "effective_clock_ghz": round(gpu_state["sclk_mhz"]["avg"] / 1e3, 3) if gpu_state.get("sclk_mhz") else None,
+                               "package_power_w": gpu_state["power_w"]["avg"] if gpu_state.get("power_w") else None,
+                               "gpu_state_in_timed_region": gpu_states if world > 1 else gpu_state,
+                               "what": "achieved = algorithmic FLOPs of the steps the kernel EXECUTES (steps x 131072 + 1024 per read, SURVEY 8d) / "
+                                       "avg_launch_ms; the steps a prefix-state table row stands for are looked up, not computed, and are not "
+                                       "counted here (frac_counting_table_steps counts them: reads/s x SURVEY 8d FLOPs per read / peak)",
+                               "algorithmic_flops_per_launch": flops_per_launch,
+                               "algorithmic_flops_per_launch_counting_table_steps": flops_all_steps,
+                               "achieved_counting_table_steps": (flops_all_steps / (avg_ms * 1e-3) / 1e12) if launches else None,
+                               "frac_counting_table_steps": (flops_all_steps / (avg_ms * 1e-3) / 1e12 / peak) if launches else None,
+                               "steps_executed_over_steps": exec_steps_frac,
+                               "mfma_flops_executed_per_algorithmic_flop": MFMA_FLOPS_PER_ALGO_FLOP[base],
+                               "mfma_pipe_frac": (achieved * MFMA_FLOPS_PER_ALGO_FLOP[base] / peak) if achieved else None,
+                               "algorithmic_bytes_per_launch": bytes_survey,
+                               "table_bytes_per_launch": bytes_table,
+                               "offset_bytes_per_launch": bytes_offsets,
+                               "traffic_over_algorithmic": (traffic / bytes_survey) if traffic else None,
+                               "traffic_over_algorithmic_plus_table_and_offsets": (traffic / (bytes_survey + bytes_table + bytes_offsets)) if traffic else None,
+                               "traffic_note": "algorithmic_bytes_per_launch = SURVEY 8d (T + 4 + 8 + 1 B per read). The kernel also reads an 8-byte "
+                                               "start offset per read (this ABI's index) and, with the prefix-state table, ONE 1 KiB row per read "
+                                               "that starts from it (table_bytes_per_launch: ~9x the 8d bytes, read once, 40 GB/s of the 8 TB/s; "
+                                               "they buy k of the T steps - alt_no_prefix_table runs without them)" if PK else
+                                               "algorithmic_bytes_per_launch = SURVEY 8d (T + 4 + 8 + 1 B per read); + an 8-byte start offset per read"}
         def alt_run(label):
             """the same timed region and step count as `value` with the model as it is configured now"""
             timed_path(1)
@@ -711,7 +757,7 @@ def main():
             model.profile_enable(False)
             return d1, k2 / max(l2, 1), l2
 
-        if world == 1 and not args.no_alt and base != "mfma_f32":
+        if args.full and world == 1 and not args.no_alt and base != "mfma_f32":
             # the same steps on the exact-fp32 MFMA kernel (v_mfma_f32_16x16x4_f32) - the strict-precision line, against the fp32-MFMA
             # roofline of SURVEY §8d. Same timed region and step count as `value`; the kernel has its own prefix-state table (round 4:
             # set_variant rebuilds the table with the kernel that will use it), so the same steps are executed / looked up.
@@ -730,7 +776,7 @@ def main():
                                                    "frac": f_exec / (ms32 * 1e-3) / 1e12 / pk_f, "avg_launch_ms": ms32, "launches": l2,
                                                    "frac_counting_table_steps": flops_all_steps / (ms32 * 1e-3) / 1e12 / pk_f,
                                                    "steps_executed_over_steps": se32 / float(steps_full.sum().item())}}
-        if world == 1 and not args.no_alt and PK:
+        if args.full and world == 1 and not args.no_alt and PK:
             # the same steps without the prefix-state table (every read steps over all its bases)
             model.set_prefix_table(0)
             d1, ms0, l2 = alt_run("k0")
@@ -742,19 +788,19 @@ def main():
                                                   "(k = 0): the rate to quote if the prefix-state table is not credited",
                                           "roofline": {"bound": "mfma", "achieved": a2, "peak": peak, "unit": "TFLOP/s", "frac": a2 / peak,
                                                        "avg_launch_ms": ms0, "launches": l2}}
-        if world == 1 and not args.no_encoder:
+        if args.full and world == 1 and not args.no_encoder:
             try:
                 out["encoder"] = encoder_record(torch, N, dev, r1[0][0], offs, lens, P, MAXLEN)
             except Exception as e:
                 out["encoder"] = {"error": repr(e)}
-        if world == 1 and not args.no_encoder and args.workload != "var300":
+        if args.full and world == 1 and not args.no_encoder and args.workload != "var300":
             try:
                 lab_now = (host_lab[(args.steps - 1) & 1].to(dev) if not args.resident_only and args.steps > 0 else
                            torch.zeros(P, dtype=torch.int8, device=dev))
                 out["device_gzip"] = gzip_record(torch, synth, dev, r1[(args.steps - 1) % nslices][0], r1[0][1], lens, lab_now)
             except Exception as e:
                 out["device_gzip"] = {"error": repr(e)}
-        if world == 1 and not args.no_e2e and not multi:
+        if args.full and world == 1 and not args.no_e2e and not multi:
             try:
                 torch.cuda.empty_cache()
                 out["e2e_cli"] = e2e_legs(args, P, RL, MAXLEN, paired)
@@ -763,7 +809,7 @@ def main():
                         out["config"]["e2e_cli_%s_reads_per_s" % k] = v["reads_per_s"]
             except Exception as e:
                 out["e2e_cli"] = {"error": repr(e)}
-        if not args.no_cpu_baseline and world == 1 and args.workload in ("pe100", "se100"):
+        if args.full and not args.no_cpu_baseline and world == 1 and args.workload in ("pe100", "se100"):
             try:
                 nb = min(P, 400000)
                 cb = cpu_baseline(r1[0][0][: nb * READ_LEN].cpu().numpy(), nb)

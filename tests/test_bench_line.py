@@ -62,3 +62,44 @@ def test_emit_writes_the_full_record_and_prints_one_line(tmp_path, capsys):
     out = capsys.readouterr().out
     assert out.endswith("\n") and out.count("\n") == 1 and len(out) < 4000
     assert json.load(open(A.full_out))["e2e_cli"]["gz_to_gz"]["calls"]          # the nested per-call records live in the file
+
+
+def test_compact_line_of_a_plain_run():
+    """a plain run (no --full) measures no roofline, no alt kernels, no CLI legs and no CPU baseline: its line keeps the contract keys"""
+    b = _bench()
+    full = _full()
+    for k in ("roofline", "alt_fp32_kernel", "alt_no_prefix_table", "encoder", "device_gzip", "e2e_cli", "cpu_baseline", "parity_sample"):
+        full.pop(k, None)
+    for k in ("kernel_only_reads_per_s", "gpu_over_cpu", "timed_regions", "device_path_over_kernel_only"):
+        full["config"].pop(k, None)
+    j = json.loads(json.dumps(b.compact(full), separators=(",", ":")))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+              "data", "config"):
+        assert k in j, k
+    assert j["value"] == full["value"] and j["ms_per_step"] == full["ms_per_step"] and j["dtype"] == full["dtype"]
+    assert "roofline" not in j and "cpu_baseline" not in j and "full_record" not in j and "kernel_only_reads_per_s" not in j["config"]
+
+
+def test_dump_outputs_float32_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per array; above the cap the same seeded sample of rows from every array, indices alongside"""
+    import numpy as np
+    import torch
+    b = _bench()
+    g = torch.Generator().manual_seed(3)
+    lg = [torch.randn(1000, 2, generator=g), torch.randn(1000, 2, generator=g)]
+    lab = torch.randint(-1, 2, (1000,), generator=g, dtype=torch.int8)
+    b.dump_outputs(str(tmp_path / "all"), lg, lab)
+    got = {n: np.load(str(tmp_path / "all" / (n + ".npy"))) for n in ("logits_r1", "logits_r2", "labels")}
+    assert all(a.dtype == np.float32 for a in got.values()) and not (tmp_path / "all" / "sample_rows.npy").exists()
+    assert (got["logits_r1"] == lg[0].numpy()).all() and (got["logits_r2"] == lg[1].numpy()).all() and (got["labels"] == lab.numpy()).all()
+    monkeypatch.setattr(b, "DUMP_CAP_BYTES", 4000)
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), lg, lab)
+    rows = np.load(str(tmp_path / "s1" / "sample_rows.npy"))
+    assert rows.dtype == np.float64 and (rows == np.load(str(tmp_path / "s2" / "sample_rows.npy"))).all()
+    r = rows.astype(np.int64)
+    assert len(r) == len(set(r.tolist())) and 0 < len(r) < 1000
+    sizes = sum(os.path.getsize(str(p)) for p in (tmp_path / "s1").iterdir())
+    assert sizes < 4000 + 4 * 128                                    # (+ the .npy headers)
+    assert (np.load(str(tmp_path / "s1" / "logits_r2.npy")) == lg[1].numpy()[r]).all()
+    assert (np.load(str(tmp_path / "s1" / "labels.npy")) == lab.numpy()[r]).all()

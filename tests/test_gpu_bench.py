@@ -30,7 +30,7 @@ def _line(out, full_path=None):
 
 def test_bench_single_gpu_contract(tmp_path):
     fp = str(tmp_path / "full.json")
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--pairs-per-step", "65536", "--no-alt",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--pairs-per-step", "65536", "--no-alt",
                         "--no-cpu-baseline", "--traffic", "off", "--e2e-records", "0", "--full-out", fp], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(r.stderr) < 6000, r.stderr[-3000:]                     # the e2e legs log at WARNING: no per-chunk lines
@@ -79,7 +79,7 @@ def test_bench_single_gpu_contract(tmp_path):
 def test_bench_reports_the_rate_without_the_prefix_table(tmp_path):
     """alt_no_prefix_table: same timed region, same steps, k = 0 - lower rate, same roofline definition; alt_fp32_kernel rides along"""
     fp = str(tmp_path / "full.json")
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "4", "--warmup", "2", "--pairs-per-step", "524288", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "4", "--warmup", "2", "--pairs-per-step", "524288", "--no-cpu-baseline",
                         "--no-encoder", "--no-e2e", "--traffic", "off", "--full-out", fp], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line, j = _line(r.stdout, fp)
@@ -95,6 +95,33 @@ def test_bench_reports_the_rate_without_the_prefix_table(tmp_path):
     assert f["roofline"]["frac"] > 0.5 and f["roofline"]["launches"] == 2 * 4
     assert abs(f["roofline"]["steps_executed_over_steps"] - j["roofline"]["steps_executed_over_steps"]) < 1e-9
     assert abs(f["value"] - 2 * 524288 * 4 / (f["ms_per_step"] * 4e-3)) < 1e-6 * f["value"]
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """a plain run (no --full): the contract line and nothing measured beside it; --dump-outputs writes the last timed step's logits of
+    both mates and its pair labels in float32, the same from run to run (seeded inputs)"""
+    import numpy as np
+    P = 65536
+    got = []
+    for run in range(2):
+        d = tmp_path / ("out%d" % run)
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs-per-step", str(P),
+                            "--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = _line(r.stdout)
+        for k in KEYS[:-1]:
+            assert k in j, k
+        assert "roofline" not in j and "cpu_baseline" not in j and "alt_fp32_frac" not in j and not any(k.startswith("e2e_") for k in j)
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["metric"] == "reads/sec classified, 100 bp paired-end" and j["unit"] == "reads/s"
+        assert abs(j["value"] - 2 * P * 3 / (j["ms_per_step"] * 3e-3)) < 1e-6 * j["value"]
+        assert sum(j["config"]["label_counts"]) == P * 3 and j["config"]["timed_region"] == "ii"
+        got.append({n: np.load(str(d / (n + ".npy"))) for n in ("logits_r1", "logits_r2", "labels")})
+    a, b = got
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["logits_r1"].shape == a["logits_r2"].shape == (P, 2) and a["labels"].shape == (P,)
+    assert np.isfinite(a["logits_r1"]).all() and set(np.unique(a["labels"]).tolist()) <= {-1.0, 0.0, 1.0}
+    assert all((a[n] == b[n]).all() for n in a)
+    assert int((a["labels"] != 0).sum()) > 0 and int((a["labels"] == 0).sum()) > 0
 
 
 def test_bench_self_launches_two_ranks_one_gpu(tmp_path):

@@ -17,7 +17,7 @@ PY
 : > $O/ab.txt
 for rep in 1 2; do
 for v in $VARS; do
-  timeout 300 python bench.py --steps 8 --variant $v --resident-only --inline-refine --no-cpu-baseline --no-alt --no-encoder --traffic off 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --steps 8 --variant $v --resident-only --inline-refine --no-cpu-baseline --no-alt --no-encoder --traffic off 2>/dev/null | python -c "
 import sys,json
 j=json.loads([l for l in sys.stdin if l.startswith('{')][0]); print('%-28s %.2f M reads/s  launch %.3f ms  step %.3f ms' % ('$v', j['value']/1e6, j['roofline']['avg_launch_ms'], j['ms_per_step']))" | tee -a $O/ab.txt
 done

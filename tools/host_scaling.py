@@ -40,7 +40,7 @@ def run_bench(world, pairs):
         env.pop(k, None)
     full = os.path.join(tempfile.gettempdir(), "rd_hs_full_%d_%d.json" % (os.getpid(), world))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "2", "--pairs-per-step", str(pairs),
-           "--no-alt", "--no-cpu-baseline", "--no-encoder", "--no-e2e", "--traffic", "off", "--full-out", full]
+           "--full", "--no-alt", "--no-cpu-baseline", "--no-encoder", "--no-e2e", "--traffic", "off", "--full-out", full]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1800)
     if r.returncode != 0 or not os.path.exists(full):
         return {"error": (r.stdout + r.stderr)[-1500:]}

@@ -12,7 +12,7 @@ VARS=${@:-auto mfma_f32 mfma_f32_diag_mfmaonly}
 for v in $VARS; do
   steps=300; [ "$v" = "mfma_f32" ] && steps=80
   echo "## variant $v: python bench.py --variant $v --steps $steps --warmup 2 --no-cpu-baseline --no-alt" >> $O
-  python $R/bench.py --variant $v --steps $steps --warmup 2 --no-cpu-baseline --no-alt --no-encoder --traffic off --resident-only > /tmp/pt_$v.json 2>/dev/null &
+  python $R/bench.py --full --variant $v --steps $steps --warmup 2 --no-cpu-baseline --no-alt --no-encoder --traffic off --resident-only > /tmp/pt_$v.json 2>/dev/null &
   pid=$!
   t=0
   while kill -0 $pid 2>/dev/null; do

@@ -3,7 +3,7 @@
 # recorded by the recurrence epilogue, rd_sync_results on the post stream) against the round-3 form (rd_refine, a scan of all logits,
 # on the side stream). Three interleaved pairs, 20 steps each.   tools/refine_ab.sh > profiles/r04_refine_ab.txt
 R=$(cd "$(dirname "$0")/.." && pwd); cd "$R"
-F="--steps 20 --warmup 3 --no-cpu-baseline --no-alt --no-encoder --no-e2e --traffic off"
+F="--full --steps 20 --warmup 3 --no-cpu-baseline --no-alt --no-encoder --no-e2e --traffic off"
 for i in 1 2 3; do
   for mode in deferred deferred_normal_prio scan; do
     X=""; [ $mode = scan ] && X="--refine-scan"

@@ -11,7 +11,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${1:-$R/gpurun_out/scale_sweep.json}
 shift || true
 NS=${RD_SWEEP_NS:-"1 2 4 8"}
-FLAGS="--no-cpu-baseline --no-alt --no-encoder --no-e2e --traffic off $*"
+FLAGS="--full --no-cpu-baseline --no-alt --no-encoder --no-e2e --traffic off $*"
 TMP=$(mktemp -d)
 cd "$R"
 # a throw-away run first: the first process on a box pays cold caches and clocks, and the plain line is compared with the N = 1 group
