@@ -323,6 +323,22 @@ RD_API size_t rd_select_workspace_bytes(int64_t n);
 RD_API int rd_select_pack(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int8_t *labels, int64_t n, int32_t label, uint8_t *out,
                    size_t out_cap, int64_t *info, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The per-read report of a chunk (the CLI's --read_report) as ONE contiguous text in `out` [dev, 16-byte aligned]: line i, in input order,
+ * is `<id>\t<label>\t<p>\n` (logits_b NULL: single-end) or `<id>\t<label>\t<p_a>\t<p_b>\t<p_pair>\n` (pairs). id = the bytes of record i's
+ * header after its leading '@' / '>' up to the first of {space, \t, \r, \n, \v, \f} (may be empty); label = "rRNA" / "nonrRNA" /
+ * "unclassified" for labels[i] = 1 / 0 / -1 (the labels that select the output files: rd_pair_fuse's, or rd_classify's uint8 labels);
+ * p = softmax(logits)[1] of logits_a / logits_b [dev] fp32[n, 2], p_pair of their sum, in fp32 from d = l1 - l0, printed as
+ * q = rint(p * 1e4): "0.dddd", "1.0000" when q = 10000. text / text_bytes / rec_start as rd_select_pack. line_start [dev] int64[n + 1]:
+ * where line i starts (entry n = the report's bytes) - a record table of the report text, so that rd_gz_compress_selected deflates it
+ * with an all-zero label vector and label 0. info [dev] int64[4]: info[0] = lines, info[1] = bytes written, info[3] != 0: nothing
+ * written - 1: the report holds more than out_cap bytes, 2: a record does not start with '@' / '>', its header runs past rec_start[i + 1]
+ * or its label is not -1 / 0 / 1. out_cap >= rd_report_out_bound(n, text_bytes) is always enough. Asynchronous on `stream`. */
+RD_API size_t rd_report_workspace_bytes(int64_t n);
+RD_API size_t rd_report_out_bound(int64_t n, int64_t text_bytes);
+RD_API int rd_report_format(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, int64_t n, const float *logits_a, const float *logits_b,
+                   const int8_t *labels, uint8_t *out, size_t out_cap, int64_t *line_start, int64_t *info, void *workspace, size_t workspace_bytes,
+                   void *stream);
+
 /* ONE DEFLATE stream - a plain .gz, the format sequencers write - inflated on the device (round 5; the CLI's default for such FASTQ, RD_DEVICE_INFLATE=members keeps the host's decoders).
  * Replaces, for such files: gzip.open(path, 'rt') of reference data_loader/seq_encoder.py:21-39. The two-pass scheme of pugz (this
  * build's host reader: csrc/rd_pgzip.h) with one wave per SECTION of `section_bytes` compressed bytes: block starts are searched on the

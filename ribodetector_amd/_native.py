@@ -27,6 +27,7 @@ SYMBOLS = [
     "rd_gz_workspace_bytes", "rd_gz_out_bound", "rd_gz_compress_selected", "rd_gz_eof_block", "rd_gz_inflate_members",
     "rd_fastq_index_workspace_bytes", "rd_fastq_index", "rd_fastq_gather", "rd_fastq_sample", "rd_fastq_strip_mark", "rd_fasta_index_workspace_bytes", "rd_fasta_index", "rd_fasta_gather", "rd_fasta_sample", "rd_select_workspace_bytes", "rd_select_pack", "rd_stream_create", "rd_stream_destroy", "rd_copy_bytes", "rd_gz_stream_workspace_bytes", "rd_gz_stream_inflate",
     "rd_gz_range_workspace_bytes", "rd_gz_range_decode", "rd_gz_range_resolve_workspace_bytes", "rd_gz_range_resolve",
+    "rd_report_workspace_bytes", "rd_report_out_bound", "rd_report_format",
 ]
 
 
@@ -100,6 +101,11 @@ def lib():
     L.rd_select_workspace_bytes.argtypes = [i64]
     L.rd_select_workspace_bytes.restype = sz
     L.rd_select_pack.argtypes = [vp, i64, vp, vp, i64, i32, vp, sz, vp, vp, sz, vp]
+    L.rd_report_workspace_bytes.argtypes = [i64]
+    L.rd_report_workspace_bytes.restype = sz
+    L.rd_report_out_bound.argtypes = [i64, i64]
+    L.rd_report_out_bound.restype = sz
+    L.rd_report_format.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp]
     L.rd_stream_create.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(vp)]
     L.rd_stream_destroy.argtypes = [vp]
     L.rd_copy_bytes.argtypes = [vp, vp, i64, i32, vp]

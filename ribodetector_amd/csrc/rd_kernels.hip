@@ -26,6 +26,7 @@
 //   rd_pair_fuse_kernel, rd_count_kernel
 //   rd_gz_*                            records of one label -> gzip (BGZF) members on the device (rd_deflate.hpp)
 //   rd_fq_* / rd_fa_*                  FASTQ records framed, FASTA batches re-written and indexed in HBM (rd_fastq_index.hpp, rd_fasta_index.hpp)
+//   rd_report_*                        per-read report lines (id, label, probabilities) of a chunk (rd_report.hpp)
 #include <stdlib.h>
 #include "rd_common.hpp"
 #include "rd_prep.hpp"
@@ -40,6 +41,7 @@
 #include "rd_inflate_stream.hpp"
 #include "rd_fastq_index.hpp"
 #include "rd_fasta_index.hpp"
+#include "rd_report.hpp"
 
 // ================================================================================================
 // C ABI
@@ -952,6 +954,64 @@ int rd_select_pack(const uint8_t *text, int64_t text_bytes, const int64_t *rec_s
     hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, bsum, p.nb, info, limit);
     hipLaunchKernelGGL(rd_gz_sel_off_kernel, dim3(p.nb), dim3(256), 0, st, rec_start, labels, n, label, bsum, out_off);
     hipLaunchKernelGGL(rd_gz_pack_kernel, dim3((unsigned)((n + GZ_PACK_RECS - 1) / GZ_PACK_RECS)), dim3(256), 0, st, text, rec_start, out_off, n, out, info);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+// the per-read report of a chunk (rd_report.hpp): one line per record, and the lines' starts as a record table of the report text
+namespace {
+struct ReportPlan {
+    int nb;
+    size_t idlen_bytes, q_bytes, bsum_bytes, fault_bytes, total;
+};
+ReportPlan report_plan(int64_t n) {
+    ReportPlan p;
+    p.nb = (int)((n + 1 + GZ_SCAN_ITEMS - 1) / GZ_SCAN_ITEMS);
+    p.idlen_bytes = align_up((size_t)n * 4, 256);
+    p.q_bytes = align_up((size_t)n * 8, 256);
+    p.bsum_bytes = align_up((size_t)p.nb * 8, 256);
+    p.fault_bytes = 256;
+    p.total = p.idlen_bytes + p.q_bytes + p.bsum_bytes + p.fault_bytes;
+    return p;
+}
+}  // namespace
+
+size_t rd_report_workspace_bytes(int64_t n) {
+    if (n < 0) return 0;
+    return report_plan(n).total;
+}
+
+size_t rd_report_out_bound(int64_t n, int64_t text_bytes) {
+    if (n < 0 || text_bytes < 0) return 0;
+    return (size_t)text_bytes + (size_t)n * RP_MAX_SUFFIX;      // an id is shorter than its record
+}
+
+int rd_report_format(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, int64_t n, const float *logits_a, const float *logits_b,
+                     const int8_t *labels, uint8_t *out, size_t out_cap, int64_t *line_start, int64_t *info, void *workspace, size_t workspace_bytes,
+                     void *stream) {
+    if (n < 0 || n > 0x7fffffffLL || text_bytes < 0) RD_FAIL(RD_E_INVALID, "rd_report_format: bad n or text_bytes");
+    if (!info || !line_start) RD_FAIL(RD_E_INVALID, "rd_report_format: null info or line_start");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        RD_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int64_t), st));
+        RD_HIP(hipMemsetAsync(line_start, 0, sizeof(int64_t), st));
+        return RD_OK;
+    }
+    if ((!text && text_bytes > 0) || !rec_start || !logits_a || !labels || !out || !workspace) RD_FAIL(RD_E_INVALID, "rd_report_format: null pointer");
+    if (((uintptr_t)workspace & 255) || ((uintptr_t)out & 15)) RD_FAIL(RD_E_INVALID, "rd_report_format: workspace must be 256-byte aligned, out 16-byte aligned");
+    const ReportPlan p = report_plan(n);
+    if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "rd_report_format: workspace too small: %zu < %zu", workspace_bytes, p.total);
+    char *w = (char *)workspace;
+    int32_t *idlen = (int32_t *)w; w += p.idlen_bytes;
+    uint64_t *qs = (uint64_t *)w; w += p.q_bytes;
+    int64_t *bsum = (int64_t *)w; w += p.bsum_bytes;
+    int32_t *fault = (int32_t *)w;
+    RD_HIP(hipMemsetAsync(fault, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(rd_report_len_kernel, dim3(p.nb), dim3(256), 0, st, text, text_bytes, rec_start, n, logits_a, logits_b, labels, line_start, idlen, qs, bsum, fault);
+    hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, bsum, p.nb, info, (int64_t)(out_cap < (size_t)INT64_MAX ? out_cap : (size_t)INT64_MAX));
+    hipLaunchKernelGGL(rd_report_off_kernel, dim3(p.nb), dim3(256), 0, st, line_start, n, bsum, fault, info);
+    hipLaunchKernelGGL(rd_report_write_kernel, dim3((unsigned)((n + RP_LINES - 1) / RP_LINES)), dim3(256), 0, st, text, rec_start, line_start, n, idlen, qs, labels,
+                       logits_b ? 3 : 1, out, info);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }

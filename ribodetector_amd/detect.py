@@ -81,6 +81,7 @@ class Predictor:
         self._shared = None                      # gzip input, several ranks of one node: one decode per node (decided once per run)
         self._chunk_reads = None
         self._use_device = None                  # does the text of the inputs stay on the device? decided once per run
+        self._report = self._rep_fh = None       # --read_report: gz.DeviceReport and the report's writer (run_with_chunks)
         self._install_cleanup()
 
     # ---- cleanup ------------------------------------------------------------------------------------
@@ -305,12 +306,42 @@ class Predictor:
                     ih = torch.empty(4, dtype=torch.int64, pin_memory=True)
                     ih.copy_(info, non_blocking=True)
                     gzparts[(e, lab)] = [(out, ih)]
+            if self._report is not None:
+                self._report_chunk(chunks, dev_in, outs, labels, lo, hi, on_dev, gzparts)
             if self.multi and not self.sharded_parse:   # label gather (1 B per read) queued behind the kernels, collected later
                 _, finish = rdist.gather_labels(labels, n, dst=0, bounds=bounds, async_op=True)
             done = _native_mod.new_event()
             done.record(post)
         return {"n": n, "bounds": bounds, "labels": labels, "host": host, "finish": finish, "done": done, "keep": (dev_in, outs),
                 "gz": gzparts, "totals": [c.total for c in chunks] if on_dev else ()}
+
+    def _report_chunk(self, chunks, dev_in, outs, labels, lo, hi, on_dev, gzparts):
+        """--read_report: the lines of records [lo, hi) of the chunk, formatted where mate 1's text, its record starts and the final
+        logits already are (rd_report_format, on the post stream after the float64 pass and the pair fusion), then deflated there too
+        for a .gz report (its line starts are a record table of the report text: rd_gz_compress_selected of all of it). Own ring of
+        buffers: the label files' slots are not shared."""
+        ring = self._rep_seq % self.GZ_RING
+        self._rep_seq += 1
+        if on_dev:
+            text, rs = chunks[0].dev[0], chunks[0].dev[3]
+        else:
+            c = chunks[0]
+            text = dev_in[0][0]
+            rs = c.tensors[3][lo:hi + 1].to(self.device, non_blocking=True) - int(c.rec_start[lo])
+        rep, line_start, info = self._report.format(text, rs, outs[0][0], outs[1][0] if self.is_paired else None, labels.view(torch.int8), slot=ring)
+        fih = torch.empty(4, dtype=torch.int64, pin_memory=True)
+        fih.copy_(info, non_blocking=True)
+        gzparts["report_fault"] = fih
+        gzparts["report_text"] = (rep, fih)
+        if self._rep_gz:
+            gather = self.multi and not self.sharded_parse
+            out, ginfo = self._gz.compress_selected(rep, line_start, self._report.zeros(hi - lo), 0, slot=("report", ring),
+                                                    out_frac=1.0 if gather else 0.5)
+            ih = torch.empty(4, dtype=torch.int64, pin_memory=True)
+            ih.copy_(ginfo, non_blocking=True)
+            gzparts["report"] = [(out, ih)]
+        else:
+            gzparts["report"] = [(rep, fih)]
 
     def collect_chunk(self, tk):
         """Labels of a submitted chunk: int8 numpy on rank 0 (whole chunk, input order), None elsewhere."""
@@ -320,10 +351,14 @@ class Predictor:
                 # the members every rank made of its shard travel to rank 0, which appends them in rank order = input order (sizes
                 # first: one small all-gather per chunk; then one padded gather per output file)
                 _native_mod.wait_event(tk["done"])
-                mine = [int(tk["gz"][key][0][1][0]) for key in self._gz_files]
+                keys = [key for key in self._gz_files if key in tk["gz"]] + (["report"] if "report" in tk["gz"] else [])
+                fault = tk["gz"].get("report_fault")
+                if fault is not None and int(fault[3]):
+                    raise RuntimeError("device report: the chunk's record table does not describe its text")
+                mine = [int(tk["gz"][key][0][1][1 if key == "report" and not self._rep_gz else 0]) for key in keys]
                 sizes = rdist.all_gather_sizes(mine)
                 gathered = {}
-                for f, key in enumerate(self._gz_files):
+                for f, key in enumerate(keys):
                     out, _ = tk["gz"][key][0]
                     if mine[f] > out.numel():
                         raise RuntimeError("device gzip: output buffer too small (%d > %d)" % (mine[f], out.numel()))
@@ -580,6 +615,25 @@ class Predictor:
         if any(self._device_parse(p) for p in self.input):
             from .gz import DeviceSelect
             self._sel = DeviceSelect(self.device)
+        # --read_report: one line per read (pair), formatted on the device for every chunk; mate 1's writer appends the pieces
+        self._report = self._rep_fh = None
+        self._rep_gz, self._rep_seq = False, 0
+        rep_path = getattr(self.args, 'read_report', None)
+        if rep_path:
+            from .gz import DeviceReport, DeviceGzip, REPORT_HEADER_PE, REPORT_HEADER_SE
+            self._report = DeviceReport(self.device)
+            self._rep_gz = self.gzip_on_device and rep_path.endswith('gz')       # (else a .gz report is deflated by the host's writer)
+            if self._rep_gz and not self._gz_files:
+                self._gz = DeviceGzip(self.device)
+            if writer:
+                log('Writing per-read report into file: {}{}{}'.format(colors.OKBLUE, rep_path, colors.ENDC))
+                self._rep_fh = fx.open_for_write(part(rep_path))
+                finals.append(rep_path)
+                if self.sharded_parse:
+                    self._rep_fh.set_eof_marker(False)
+                if self.rank == 0:                 # (the sharded parse: rank 0's part comes first in the joined file)
+                    hdr = np.frombuffer(REPORT_HEADER_PE if self.is_paired else REPORT_HEADER_SE, dtype=np.uint8)
+                    self._rep_fh.write_text(hdr.ctypes.data, hdr.size)
 
         # writer threads (rank 0): one per mate, records of every label file in input order
         wq, werr, wth = [], [], []
@@ -625,7 +679,38 @@ class Predictor:
                                 done.record(gz_copy)
                                 jobs.append(("dev", put, st[slot], nb, done))
                                 slot += 1
+                    if e == 0 and self._rep_fh is not None:
+                        slot = report_jobs(gzparts, jobs, k, slot)
                     return item, jobs
+
+                def report_jobs(gzparts, jobs, k, slot):
+                    """the chunk's report pieces (one per rank under the label gather): gzip members made on the device, or its text"""
+                    fault = gzparts.get("report_fault")
+                    if fault is not None and int(fault[3]):
+                        raise RuntimeError("device report: the chunk's record table does not describe its text")
+                    fh = self._rep_fh
+                    for out, info in gzparts["report"]:
+                        as_text = not self._rep_gz
+                        nb = int(info[1 if as_text else 0]) if info is not None else int(out.numel())
+                        if nb > out.numel():        # members that do not fit the reserved half: the text goes, the host deflates it
+                            out, info = gzparts["report_text"]
+                            as_text, nb = True, int(info[1])
+                        put = fh.write_text if as_text else fh.write_members
+                        if nb and not out.is_cuda:
+                            jobs.append(("host", put, out, nb, None))
+                        elif nb:
+                            st = stages[k]
+                            if slot == len(st):
+                                st.append(None)
+                            if st[slot] is None or st[slot].numel() < nb:
+                                st[slot] = None
+                                st[slot] = torch.empty(max(nb, 1 << 22) * 5 // 4, dtype=torch.uint8, pin_memory=True)
+                            _native.copy_bytes(st[slot], out, nb, gz_copy)
+                            done = _native.new_event()
+                            done.record(gz_copy)
+                            jobs.append(("dev", put, st[slot], nb, done))
+                            slot += 1
+                    return slot
 
                 def complete(pending):
                     (chunk, labels, _), jobs = pending
@@ -724,6 +809,8 @@ class Predictor:
             for handles in fhs.values():
                 for fh in handles:
                     fh.close()
+            if self._rep_fh is not None:
+                self._rep_fh.close()
         if self.sharded_parse:                     # totals over the ranks; the parts are joined in rank order = input order
             import torch.distributed as dist
             tot = torch.tensor([num_read, num_nonrrna, num_rrna, num_unknown], dtype=torch.int64,
@@ -806,6 +893,8 @@ class Predictor:
             raise RuntimeError(
                 "Ouput rRNA should have no more than two files and they should the same number with input files.")
         self.is_paired = (num_inputs == 2)
+        check_read_report(self.args.read_report if hasattr(self.args, 'read_report') else None, self.output, self.rrna, self.is_paired,
+                          self.args.ensure)
         # reference batch-size heuristic (detect.py:558-568); kept because --chunk_size is expressed in these batches
         denom = (2 * self.len * 6.4) if self.is_paired else (self.len * 6.4)
         self.batch_size = 2 ** math.floor(math.log2(((self.args.memory - 2) * 1024 * 1024) / denom))
@@ -829,6 +918,20 @@ class Predictor:
         """Pair fusion on the device (rd_pair_fuse) then the reference's dict-of-lists result (detect.py:616-663)."""
         lab = module_arch.pair_fuse(r1_outs.contiguous(), r2_outs.contiguous(), self.args.ensure).cpu().tolist()
         return Predictor.separate_reads(r1_reads, lab), Predictor.separate_reads(r2_reads, lab)
+
+
+def check_read_report(path, output, rrna, is_paired, ensure):
+    """--read_report must not name a file the run writes anyway: an -o / -r file or an '<out>.unclassified.gz' file (-e both, pairs)"""
+    if not path:
+        return
+    same = lambda a, b: os.path.abspath(a) == os.path.abspath(b)      # noqa: E731
+    for o in list(output or []) + list(rrna or []):
+        if same(path, o):
+            raise RuntimeError("--read_report {} is also an output sequence file (-o / -r)".format(path))
+    if is_paired and ensure == 'both':
+        for o in output or []:
+            if same(path, o + '.unclassified.gz'):
+                raise RuntimeError("--read_report {} is the unclassified pairs' output file".format(path))
 
 
 def build_parser():
@@ -861,6 +964,14 @@ none: give label based on the mean probability of read pair.
     args.add_argument('--semantics', default=None, choices=['gpu', 'cpu'],
                       help='(extension) which reference product to reproduce for reads shorter than --len or ending in N:\n'
                            'gpu = ribodetector (packed sequences, default); cpu = ribodetector_cpu (zero-padded input).')
+    args.add_argument('--read_report', default=None, type=str,
+                      help='(extension) write one line per read (per pair for paired-end input) to this file, in input order:\n'
+                           '  single-end: #read_id<TAB>label<TAB>p_rrna\n'
+                           '  paired-end: #read_id<TAB>label<TAB>p_rrna_1<TAB>p_rrna_2<TAB>p_rrna_pair\n'
+                           'read_id = the header up to its first whitespace (mate 1\'s for pairs); label = rRNA, nonrRNA or\n'
+                           'unclassified (-e both), the output file the read went to; p_rrna = softmax of the final logits\n'
+                           '(p_rrna_pair: of the summed logits of the mates, what decides -e none) as 0.dddd / 1.0000.\n'
+                           'gzip-compressed when the name ends with gz.')
     args.add_argument('-v', '--version', action='version', version='%(prog)s {version}'.format(version=__version__))
     return args
 

@@ -117,6 +117,58 @@ class DeviceSelect:
         return out, info
 
 
+REPORT_HEADER_SE = b"#read_id\tlabel\tp_rrna\n"
+REPORT_HEADER_PE = b"#read_id\tlabel\tp_rrna_1\tp_rrna_2\tp_rrna_pair\n"
+
+
+class DeviceReport:
+    """format(text, rec_start, logits_a, logits_b, labels): the per-read report lines of a chunk as ONE contiguous text on the device
+    (C ABI rd_report_format; the line format is in include/ribodetector_amd.h and the README). logits_b None = single-end. Returns
+    (out, line_start, info): out uint8 and line_start int64[n + 1] (where every line starts: a record table of the report text) are
+    owned by this object until the next call with the same `slot`; info int64[4] on the device, info[1] = bytes, info[3] != 0 = bad
+    record table. Asynchronous on the current stream. zeros(n): an all-zero int8 label vector, with which DeviceGzip.compress_selected
+    deflates the whole report (text = out, rec_start = line_start, label 0)."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._ws = None
+        self._out = {}
+        self._zeros = None
+
+    def zeros(self, n):
+        if self._zeros is None or self._zeros.numel() < n:
+            self._zeros = None
+            self._zeros = torch.zeros(max(n, 1 << 16), dtype=torch.int8, device=self.device)
+        return self._zeros[:n]
+
+    def format(self, text, rec_start, logits_a, logits_b, labels, slot=0):
+        lib = N.lib()
+        n, tb = int(labels.numel()), int(text.numel())
+        if rec_start.dtype != torch.int64 or rec_start.numel() < n + 1 or not rec_start.is_contiguous():
+            raise TypeError("DeviceReport.format: rec_start must be a contiguous int64 tensor of n + 1 entries")
+        if labels.dtype not in (torch.int8, torch.uint8) or text.dtype != torch.uint8:
+            raise TypeError("DeviceReport.format: labels must be int8 / uint8 and text uint8")
+        for lg in (logits_a, logits_b):
+            if lg is not None and (lg.dtype != torch.float32 or not lg.is_contiguous() or lg.numel() < 2 * n):
+                raise TypeError("DeviceReport.format: logits must be contiguous fp32 [n, 2] tensors")
+        need = int(lib.rd_report_workspace_bytes(n))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=self.device)
+        cap = int(lib.rd_report_out_bound(n, tb))
+        out, ls = self._out.get(slot, (None, None))
+        if out is None or out.numel() < cap or ls.numel() < n + 1:
+            self._out[slot] = None
+            out = torch.empty(((cap + 255) // 256) * 256 + 256, dtype=torch.uint8, device=self.device)
+            ls = torch.empty(max(n + 1, 1024), dtype=torch.int64, device=self.device)
+            self._out[slot] = (out, ls)
+        info = torch.empty(4, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(lib.rd_report_format(N.ptr(text), tb, N.ptr(rec_start), n, N.ptr(logits_a), N.ptr(logits_b), N.ptr(labels), N.ptr(out), out.numel(),
+                                         N.ptr(ls), N.ptr(info), N.ptr(self._ws), self._ws.numel(), N.stream_ptr(self.device)), "rd_report_format")
+        return out, ls[:n + 1], info
+
+
 # ---- the input side: gzip members inflated on the device (csrc/rd_inflate_dev.hpp) ---------------------------------------------------------
 
 GZI_ERRORS = {1: "invalid block type", 2: "invalid Huffman code", 3: "invalid code lengths set", 4: "more data than the member's ISIZE says",
