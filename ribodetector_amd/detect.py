@@ -8,27 +8,35 @@ Flow per chunk (reference run_with_chunks, detect.py:326-523):
     -> pinned host buffer -> H2D on a copy stream (double buffered: chunk k+1 is parsed/copied while chunk k computes)
     -> rd_classify (R1 [, R2]) -> rd_pair_fuse / argmax -> labels D2H (1 B/read)
     -> records written by label in input order.
-Under torchrun (WORLD_SIZE > 1), one process per GPU:
-  * plain input files: every rank parses only its own byte range (record-aligned, mates cut at the same record index:
-    data_loader/fastx_parser.plan_ranges), classifies it, writes its own part of every output file; the counters are
-    all-reduced (RCCL) and every rank copies its part to its offset in the final file (rank order = input order);
-  * gzip input (one DEFLATE stream, not splittable): every rank parses the stream, classifies a contiguous shard of each
-    chunk, and rank 0 gathers the 1-byte labels over RCCL and writes (ribodetector_amd/dist.py).
+A run takes one of three layouts (Predictor._plan_ranks decides; under torchrun, WORLD_SIZE > 1, one process per GPU):
+  * one rank: it reads, classifies and writes everything;
+  * sharded parse - plain inputs, BGZF inputs (rank 0 indexes the members) and single-stream .gz inputs that the device decoder
+    takes (every rank decodes its own compressed range, data_loader/gz_shard.py): every rank parses only its own share
+    (record-aligned, mates cut at the same record index: data_loader/fastx_parser.plan_ranges), classifies it and writes its own
+    part of every output file; the counters are all-reduced (RCCL) and every rank copies its part to its offset in the final file
+    (rank order = input order);
+  * label gather - the other gzip inputs (one DEFLATE stream decoded once per node into shared memory, or by every rank): every
+    rank classifies a contiguous shard of each chunk, and rank 0 gathers the 1-byte labels - and the gzip members and report
+    lines made of every shard - over RCCL and writes (ribodetector_amd/dist.py).
 """
 import argparse
+import functools
 import math
 import os
 import threading
 import time
 import queue
 from argparse import RawTextHelpFormatter
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
 from . import __version__
 from . import _native as _native_mod
 from . import dist as rdist
+from . import gz as _gzmod
 from .data_loader import device_reader as dr
 from .data_loader import fastx_parser as fx
 from .model import model as module_arch
@@ -58,6 +66,120 @@ def part_path(path, rank):
     return '%s.part%d' % (path, rank)
 
 
+REPORT = (0, None)      # the --read_report among the (mate, label) output files: mate 1's writer appends it, it holds no label's records
+
+
+def _pinned(t):
+    """a pinned host copy of a device tensor, queued on the current stream (read it once an event recorded behind it has passed)"""
+    return torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
+
+
+class Piece(NamedTuple):
+    """Bytes that one output file gets from the GPU for one chunk (one piece per rank under the label gather). info: pinned copy of
+    the int64[4] that the kernel which made buf wrote ([0] = gzip bytes, [1] = text bytes: gz.DeviceGzip / DeviceSelect /
+    DeviceReport), or None when all of buf counts (bytes gathered from the ranks); text: text or gzip members; fault: pinned info
+    whose [3] != 0 says that the chunk's record table did not describe its text to `what`; fallback: what the file gets when the bytes
+    exceed buf (text that did not compress into the reserved half): None = the host writes the chunk's selected records."""
+    buf: torch.Tensor
+    info: Optional[torch.Tensor]
+    text: bool
+    fault: Optional[torch.Tensor] = None
+    what: str = "gzip"
+    fallback: Optional["Piece"] = None
+
+    def size(self):
+        """the bytes made, whether or not they fit buf; raises when the kernel found the record table wrong"""
+        if self.fault is not None and int(self.fault[3]):
+            raise RuntimeError("device %s: the chunk's record table does not describe its text" % self.what)
+        return int(self.buf.numel()) if self.info is None else int(self.info[1 if self.text else 0])
+
+    def take(self):
+        """(piece, bytes) that the file gets: this piece, or its fallback when the bytes do not fit buf; (None, 0) = the host writes
+        the chunk's selected records"""
+        nb = self.size()
+        if nb <= self.buf.numel():
+            return self, nb
+        return (None, 0) if self.fallback is None else self.fallback.take()
+
+
+class _MateWriter:
+    """The writer thread of one mate: the records of that mate's output files in input order (mate 1's: and the per-read report).
+    Two sets of pinned staging buffers: the bytes an item's files get from the GPU (gzip members / packed records / report text) are
+    fetched for item k+1 while item k is being written. The fetch is a kernel on this thread's stream (C ABI rd_copy_bytes), not a
+    DMA copy - an SDMA queue is shared in order with copies that wait for kernels."""
+
+    def __init__(self, pred, e, files, errors):
+        self.pred, self.e, self.files, self.errors = pred, e, files, errors     # files: [((mate, label), handle)] of mate e in file order
+        self.q = queue.Queue(maxsize=2)      # items (chunk of this mate, labels, {(mate, label): [Piece]}); None ends
+        self.stream, self.stages = _gzmod.acquire_stream(pred.device), [[], []]
+        self.thread = pred._spawn(self._run)
+
+    def _run(self):
+        item = ()
+        try:
+            torch.cuda.set_device(self.pred.device)          # (the current device is per thread)
+            pending, k = None, 0
+            while True:
+                try:
+                    item = self.q.get() if pending is None else self.q.get_nowait()
+                except queue.Empty:         # nothing to prefetch: write what is in hand, then wait
+                    self._complete(*pending)
+                    pending = None
+                    continue
+                if item is not None:
+                    nxt, k = (item, self._issue(item, k)), k ^ 1
+                if pending is not None:
+                    self._complete(*pending)
+                if item is None:
+                    return
+                pending = nxt
+        except BaseException as ex:
+            self.errors.append(ex)
+            while item is not None:          # keep draining so that the producer never blocks
+                item = self.q.get()
+        finally:
+            self.pred.thread_cpu_s["writer:%d" % self.e] = round(time.thread_time(), 4)
+
+    def _issue(self, item, k):
+        """queue the D2H of everything the item's files take from the GPU into stage set k; returns the writes in file order, as
+        (event to wait for or None, write)"""
+        chunk, labels, pieces = item
+        jobs, slot = [], 0
+        for key, fh in self.files:
+            for piece in pieces.get(key) or (None,):
+                p, nb = (None, 0) if piece is None else piece.take()
+                if p is None:           # nothing from the GPU, or too much for its buffer: the host writes the records of this label
+                    jobs.append((None, functools.partial(fh.write_selected, chunk, labels, key[1])))
+                elif nb:
+                    buf, done = p.buf, None
+                    if buf.is_cuda:
+                        (buf, done), slot = self._fetch(k, slot, buf, nb), slot + 1
+                    jobs.append((done, functools.partial(fh.write_text if p.text else fh.write_members, buf.data_ptr(), nb)))
+        return jobs
+
+    def _fetch(self, k, slot, src, nb):
+        """the first nb bytes of device buffer src -> pinned staging buffer `slot` of set k; returns (staging buffer, event)"""
+        st = self.stages[k]
+        if slot == len(st):
+            st.append(None)
+        if st[slot] is None or st[slot].numel() < nb:
+            st[slot] = None
+            st[slot] = torch.empty(max(nb, 1 << 22) * 5 // 4, dtype=torch.uint8, pin_memory=True)
+        _native_mod.copy_bytes(st[slot], src, nb, self.stream)
+        done = _native_mod.new_event()
+        done.record(self.stream)
+        return st[slot], done
+
+    @staticmethod
+    def _complete(item, jobs):
+        for done, write in jobs:
+            if done is not None:
+                _native_mod.wait_event(done)    # (sleeping in the driver: stream.synchronize() would spin a core)
+            write()
+        if item[0].release is not None:   # a shared-memory slot: free for the next chunk once its text is written
+            item[0].release()
+
+
 class Predictor:
     """Main class of predictor for rRNA, non-rRNA sequences (interface of reference detect.py:34-43)."""
 
@@ -77,12 +199,17 @@ class Predictor:
         self.multi = False                       # collectives in use: several ranks (or one rank under RD_FORCE_DIST=1, dist.py)
         self._arenas = []                        # shared-memory chunk arenas of this rank (rank 0, gzip input, several ranks)
         self._part_files = []                    # this rank's part files of a sharded-parse run (removed if the run fails)
-        self.sharded_parse = False               # several ranks, plain input: every rank parses its own byte range
+        self.sharded_parse = False               # the sharded-parse layout: every rank parses its own share of the input (_plan_ranks)
         self._shared = None                      # gzip input, several ranks of one node: one decode per node (decided once per run)
         self._chunk_reads = None
         self._use_device = None                  # does the text of the inputs stay on the device? decided once per run
-        self._report = self._rep_fh = None       # --read_report: gz.DeviceReport and the report's writer (run_with_chunks)
+        self._report = None                      # --read_report: gz.DeviceReport (run_with_chunks)
         self._install_cleanup()
+
+    @property
+    def gathers_labels(self):
+        """the label-gather layout (module docstring): several ranks classify shards of one decode, and rank 0 gathers and writes"""
+        return not self.sharded_parse and self.multi
 
     # ---- cleanup ------------------------------------------------------------------------------------
     def cleanup(self):
@@ -228,13 +355,19 @@ class Predictor:
             ln = tlen[lo:hi].to(self.device, non_blocking=True)
         return arena, off, ln
 
+    def _device_text(self, chunk, arena, lo, hi):
+        """text (arena: from _to_device) and int64 record starts on the device of records [lo, hi) of one mate's chunk"""
+        if isinstance(chunk, dr.DeviceChunk):
+            return chunk.dev[0], chunk.dev[3]
+        return arena, chunk.tensors[3][lo:hi + 1].to(self.device, non_blocking=True) - int(chunk.rec_start[lo])
+
     def submit_chunk(self, chunks):
         """Enqueue one chunk: H2D on the copy stream, kernels on the compute stream, D2H of the labels into pinned memory.
         Nothing here waits for the GPU, so the next chunk's H2D overlaps this chunk's kernels. Returns a ticket for
         collect_chunk()."""
         n = len(chunks[0].seq_len)
         bounds = None
-        if self.multi and not self.sharded_parse:   # equal bases (= recurrence steps) per rank, not equal read counts
+        if self.gathers_labels:                     # equal bases (= recurrence steps) per rank, not equal read counts
             work = sum(np.minimum(np.asarray(c.seq_len, dtype=np.int64), self.len) for c in chunks)
             bounds = rdist.shard_bounds(n, self.world, work)
         lo, hi = (0, n) if bounds is None else (bounds[self.rank], bounds[self.rank + 1])
@@ -268,110 +401,91 @@ class Predictor:
                 labels = module_arch.pair_fuse(outs[0][0], outs[1][0], self.args.ensure)
             else:
                 labels = outs[0][1].view(torch.int8)
-            host = finish = None
-            gzparts = {}
-            if not self.multi or self.sharded_parse:
-                host = torch.empty(labels.shape, dtype=torch.int8, pin_memory=True)
-                host.copy_(labels, non_blocking=True)
-            if on_dev:
-                # a chunk whose text lives on the device: every output file's records are selected there - deflated (.gz outputs, as
-                # below) or packed into one contiguous text (plain outputs, rd_select_pack) - and only those bytes travel to the host
-                ring = self._gz_seq % self.GZ_RING
-                self._gz_seq += 1
-                lab8 = labels.view(torch.int8)
-                for e, lab in self._out_files:
-                    text, rs = chunks[e].dev[0], chunks[e].dev[3]
-                    if (e, lab) in self._gz_files:
-                        out, info = self._gz.compress_selected(text, rs, lab8, lab, slot=(e, lab, ring))
-                    else:
-                        out, info = self._sel.pack_selected(text, rs, lab8, lab, slot=(e, lab, ring))
-                    ih = torch.empty(4, dtype=torch.int64, pin_memory=True)
-                    ih.copy_(info, non_blocking=True)
-                    gzparts[(e, lab)] = [(out, ih)]
-            # .gz outputs: the records of every label file of this chunk - under the label gather: of this rank's shard of it - are
-            # deflated here, where the text already is (BGZF members, csrc/rd_deflate.hpp), beside the next chunk's recurrences; the
-            # writer threads fetch the compressed bytes and append them (reference: gzip.open(..., compresslevel=5) on the host,
-            # detect.py:729-741). Every rank takes the same decision (the chunks of a shared decode are the same chunks).
-            if not on_dev and self._gz_files and all(c.tensors is not None and len(c.tensors) > 3 and c.verbatim for c in chunks):
-                ring = self._gz_seq % self.GZ_RING
-                self._gz_seq += 1
-                for e, lab in self._gz_files:
-                    c = chunks[e]
-                    b0 = int(c.rec_start[lo])
-                    rs = c.tensors[3][lo:hi + 1].to(self.device, non_blocking=True) - b0
-                    # (own writer: half of the worst-case output size is reserved - an incompressible chunk falls back to the host's
-                    # deflate; under the label gather the full bound, every rank must take the same path)
-                    out, info = self._gz.compress_selected(dev_in[e][0], rs, labels.view(torch.int8), lab, slot=(e, lab, ring),
-                                                           out_frac=1.0 if (self.multi and not self.sharded_parse) else 0.5)
-                    ih = torch.empty(4, dtype=torch.int64, pin_memory=True)
-                    ih.copy_(info, non_blocking=True)
-                    gzparts[(e, lab)] = [(out, ih)]
+            host = None if self.gathers_labels else _pinned(labels)
+            pieces = self._select_chunk(chunks, dev_in, labels, lo, hi, on_dev)
             if self._report is not None:
-                self._report_chunk(chunks, dev_in, outs, labels, lo, hi, on_dev, gzparts)
-            if self.multi and not self.sharded_parse:   # label gather (1 B per read) queued behind the kernels, collected later
+                pieces[REPORT] = self._report_chunk(chunks, dev_in, outs, labels, lo, hi)
+            finish = None
+            if self.gathers_labels:                 # label gather (1 B per read) queued behind the kernels, collected later
                 _, finish = rdist.gather_labels(labels, n, dst=0, bounds=bounds, async_op=True)
             done = _native_mod.new_event()
             done.record(post)
         return {"n": n, "bounds": bounds, "labels": labels, "host": host, "finish": finish, "done": done, "keep": (dev_in, outs),
-                "gz": gzparts, "totals": [c.total for c in chunks] if on_dev else ()}
+                "pieces": pieces, "totals": [c.total for c in chunks] if on_dev else ()}
 
-    def _report_chunk(self, chunks, dev_in, outs, labels, lo, hi, on_dev, gzparts):
-        """--read_report: the lines of records [lo, hi) of the chunk, formatted where mate 1's text, its record starts and the final
-        logits already are (rd_report_format, on the post stream after the float64 pass and the pair fusion), then deflated there too
-        for a .gz report (its line starts are a record table of the report text: rd_gz_compress_selected of all of it). Own ring of
-        buffers: the label files' slots are not shared."""
+    def _select_chunk(self, chunks, dev_in, labels, lo, hi, on_dev):
+        """{(mate, label): [Piece]}: the label files whose records of this chunk are selected on the device, on the post stream beside
+        the next chunk's recurrences, so that only the selected bytes travel to the host. A chunk whose text lives on the device: every
+        file's, deflated (.gz outputs: BGZF members, csrc/rd_deflate.hpp) or packed into one text (rd_select_pack). Otherwise the .gz
+        outputs' only - under the label gather: of this rank's shard (reference: gzip.open(..., compresslevel=5) on the host,
+        detect.py:729-741). Every rank takes the same decision (the chunks of a shared decode are the same chunks)."""
+        if on_dev:
+            files = self._out_files
+        elif self._gz_files and all(c.tensors is not None and len(c.tensors) > 3 and c.verbatim for c in chunks):
+            files = self._gz_files
+        else:
+            return {}
+        ring = self._gz_seq % self.GZ_RING
+        self._gz_seq += 1
+        # (own writer: half of the worst-case output size is reserved - an incompressible chunk falls back to the host's deflate; under
+        # the label gather the full bound, every rank must take the same path; a chunk on the device has no host text to fall back to)
+        frac = 1.0 if on_dev or self.gathers_labels else 0.5
+        pieces = {}
+        for e, lab in files:
+            text, rs = self._device_text(chunks[e], dev_in[e][0], lo, hi)
+            gz = (e, lab) in self._gz_files
+            if gz:
+                out, info = self._gz.compress_selected(text, rs, labels.view(torch.int8), lab, slot=(e, lab, ring), out_frac=frac)
+            else:
+                out, info = self._sel.pack_selected(text, rs, labels.view(torch.int8), lab, slot=(e, lab, ring))
+            info = _pinned(info)
+            pieces[(e, lab)] = [Piece(out, info, not gz, info, "gzip" if gz else "select")]
+        return pieces
+
+    def _report_chunk(self, chunks, dev_in, outs, labels, lo, hi):
+        """--read_report: the pieces of the lines of records [lo, hi) of the chunk, formatted where mate 1's text, its record starts
+        and the final logits already are (rd_report_format, on the post stream after the float64 pass and the pair fusion), then
+        deflated there too for a .gz report (its line starts are a record table of the report text: rd_gz_compress_selected of all of
+        it; members that do not fit the reserved half fall back to the text, which the host deflates). Own ring of buffers: the label
+        files' slots are not shared."""
         ring = self._rep_seq % self.GZ_RING
         self._rep_seq += 1
-        if on_dev:
-            text, rs = chunks[0].dev[0], chunks[0].dev[3]
-        else:
-            c = chunks[0]
-            text = dev_in[0][0]
-            rs = c.tensors[3][lo:hi + 1].to(self.device, non_blocking=True) - int(c.rec_start[lo])
+        text, rs = self._device_text(chunks[0], dev_in[0][0], lo, hi)
         rep, line_start, info = self._report.format(text, rs, outs[0][0], outs[1][0] if self.is_paired else None, labels.view(torch.int8), slot=ring)
-        fih = torch.empty(4, dtype=torch.int64, pin_memory=True)
-        fih.copy_(info, non_blocking=True)
-        gzparts["report_fault"] = fih
-        gzparts["report_text"] = (rep, fih)
+        fault = _pinned(info)
+        piece = Piece(rep, fault, True, fault, "report")
         if self._rep_gz:
-            gather = self.multi and not self.sharded_parse
-            out, ginfo = self._gz.compress_selected(rep, line_start, self._report.zeros(hi - lo), 0, slot=("report", ring),
-                                                    out_frac=1.0 if gather else 0.5)
-            ih = torch.empty(4, dtype=torch.int64, pin_memory=True)
-            ih.copy_(ginfo, non_blocking=True)
-            gzparts["report"] = [(out, ih)]
-        else:
-            gzparts["report"] = [(rep, fih)]
+            out, ginfo = self._gz.compress_selected(rep, line_start, self._report.zeros(hi - lo), 0, slot=REPORT + (ring,),
+                                                    out_frac=1.0 if self.gathers_labels else 0.5)
+            piece = Piece(out, _pinned(ginfo), False, fault, "report", fallback=piece)
+        return [piece]
 
     def collect_chunk(self, tk):
         """Labels of a submitted chunk: int8 numpy on rank 0 (whole chunk, input order), None elsewhere."""
-        if self.multi and not self.sharded_parse:
+        if self.gathers_labels:
             labels = tk["finish"]()
-            if tk.get("gz"):
-                # the members every rank made of its shard travel to rank 0, which appends them in rank order = input order (sizes
-                # first: one small all-gather per chunk; then one padded gather per output file)
-                _native_mod.wait_event(tk["done"])
-                keys = [key for key in self._gz_files if key in tk["gz"]] + (["report"] if "report" in tk["gz"] else [])
-                fault = tk["gz"].get("report_fault")
-                if fault is not None and int(fault[3]):
-                    raise RuntimeError("device report: the chunk's record table does not describe its text")
-                mine = [int(tk["gz"][key][0][1][1 if key == "report" and not self._rep_gz else 0]) for key in keys]
-                sizes = rdist.all_gather_sizes(mine)
-                gathered = {}
-                for f, key in enumerate(keys):
-                    out, _ = tk["gz"][key][0]
-                    if mine[f] > out.numel():
-                        raise RuntimeError("device gzip: output buffer too small (%d > %d)" % (mine[f], out.numel()))
-                    parts = rdist.gather_var_bytes(out, mine[f], sizes[:, f].tolist(), dst=0)
-                    if self.rank == 0:
-                        gathered[key] = [(t, None) for t in parts]
-                tk["gz"] = gathered
+            if tk["pieces"]:
+                self._gather_pieces(tk)
             return None if self.rank != 0 else labels.cpu().numpy()
         _native_mod.wait_event(tk["done"])         # (a blocking event: the thread sleeps in the driver, it does not spin a host core)
         for t in tk.get("totals", ()):
             if int(t[0]) < 0:
                 raise RuntimeError("device chunk assembly failed (rd_fastq_gather)")
         return tk["host"].numpy()
+
+    def _gather_pieces(self, tk):
+        """label gather: the pieces every rank made of its shard travel to rank 0, which appends them in rank order = input order
+        (sizes first: one small all-gather per chunk; then one padded gather per output file)"""
+        _native_mod.wait_event(tk["done"])
+        pieces = tk["pieces"]
+        own = [(key, pieces[key][0]) for key in pieces]
+        mine = [p.size() for _, p in own]
+        sizes = rdist.all_gather_sizes(mine)
+        for f, (key, p) in enumerate(own):
+            if mine[f] > p.buf.numel():
+                raise RuntimeError("device gzip: output buffer too small (%d > %d)" % (mine[f], p.buf.numel()))
+            parts = rdist.gather_var_bytes(p.buf, mine[f], sizes[:, f].tolist(), dst=0)
+            pieces[key] = [p._replace(buf=t, info=None, fault=None, fallback=None) for t in parts or ()]
 
     def classify_chunk(self, chunks):
         """chunks: (c1,) or (c1, c2). Returns the int8 labels of the whole chunk on rank 0 (numpy), None elsewhere."""
@@ -392,7 +506,7 @@ class Predictor:
 
         def work():
             try:
-                self._timeline.append(("reader_thread_%s" % os.path.basename(str(path)), round(time.perf_counter() - self._t_run, 4)))
+                self._mark("reader_thread_%s" % os.path.basename(str(path)))
                 # FASTQ whose text can stay on the device (plain files, BGZF): H2D of the file's bytes, members inflated and records
                 # framed there - no parser thread at all (data_loader/device_reader.py; RD_DEVICE_PARSE=0 keeps the host parser)
                 if arena is None and self._device_parse(path):
@@ -420,7 +534,7 @@ class Predictor:
         """does this input's text stay on the device? FASTQ, plain or BGZF, when every record a rank reads is a record it classifies
         (one rank, or the sharded parse) - under the label gather the chunk's lengths are needed on the host for the shard bounds"""
         if self._use_device is None:      # ONE decision for the run: the mates' chunks must be of one kind (submit_chunk looks at the first)
-            self._use_device = (not self.multi or self.sharded_parse) and all(dr.device_parse_wanted(p) for p in self.input)
+            self._use_device = not self.gathers_labels and all(dr.device_parse_wanted(p) for p in self.input)
         return self._use_device
 
     def _shared_decode(self):
@@ -428,10 +542,9 @@ class Predictor:
         and tells the others where each chunk lies; they map it and take their share of the records. (Ranks spread over several
         nodes cannot share memory: there every rank decodes the stream itself, as in round 2.)"""
         if self._shared is None:
-            import torch.distributed as dist
             # one node only - and only when the launcher SAYS so (torchrun sets LOCAL_WORLD_SIZE; a launcher that sets just
             # RANK / WORLD_SIZE may have spread the ranks over several hosts, whose /dev/shm are different memories)
-            ok = (self.multi and not self.sharded_parse and self.world > 1 and os.environ.get("RD_SHARED_DECODE", "1") != "0" and
+            ok = (self.gathers_labels and self.world > 1 and os.environ.get("RD_SHARED_DECODE", "1") != "0" and
                   os.environ.get("LOCAL_WORLD_SIZE") is not None and int(os.environ["LOCAL_WORLD_SIZE"]) == self.world)
             if ok:                                   # rank 0 owns the slots: its /dev/shm must hold them (all ranks take its answer)
                 msg = [None]
@@ -449,8 +562,6 @@ class Predictor:
         return self._shared
 
     def _chunk_stream(self, chunk_reads):
-        import torch.distributed as dist
-        from . import _native
         shared = self._shared_decode()
         if shared and self.rank != 0:                # chunks arrive as descriptions of rank 0's shared-memory slots
             while True:
@@ -467,7 +578,7 @@ class Predictor:
         # -t/--threads also bounds the decoder threads of .gz inputs (parallel DEFLATE decoding, csrc/rd_pgzip.h): what is left after
         # the parser threads and this one, divided among the input files - and among the ranks when every rank decodes for itself
         sharers = len(self.input) * (1 if shared else self.world)
-        _native.host_lib().rd_host_set_gz_threads(max(2, min(12, (int(self.args.threads) - 2) // max(1, sharers))))
+        _native_mod.host_lib().rd_host_set_gz_threads(max(2, min(12, (int(self.args.threads) - 2) // max(1, sharers))))
         arenas = [None] * len(self.input)
         if shared:
             tag = "rd_%s_%d" % (os.environ.get("MASTER_PORT", "0"), os.getpid())
@@ -505,6 +616,90 @@ class Predictor:
             chunk_reads = self.batch_size * self.chunk_size
         self._chunk_reads, self._shared, self._use_device = chunk_reads, None, None
         self._timeline, self._t_run = [], time.perf_counter()
+        self._plan_ranks()
+        _native_mod.host_lib().rd_host_set_threads(int(self.args.threads))   # -t/--threads: gzip workers; read when a writer is opened
+        writes = self.rank == 0 or not self.gathers_labels
+        files = self._open_outputs() if writes else []     # [((mate, label), final path, handle)]
+        counts = [0, 0, 0, 0]                      # num_read, num_nonrrna, num_rrna, num_unknown
+        self._mark("outputs_open")
+        self._stage_s = {"wait_reader": 0.0, "classify": 0.0, "wait_writer": 0.0}   # main-thread seconds per pipeline stage
+        self.thread_cpu_s = {}                                                      # CPU seconds of the pipeline's Python threads, by role
+        main_cpu0 = time.thread_time()
+        self._first_chunk = None
+        self.ingest = {}                           # per input file: which reader took it, and the device feeder's stage times
+        self._copy_stream = _gzmod.acquire_stream(self.device)      # (pooled: the allocator's cache is per stream, gz.acquire_stream)
+        self._post_stream = _gzmod.acquire_stream(self.device)
+        self._device_outputs([key for key, _, _ in files if key != REPORT])
+        # writer threads (rank 0; every rank under the sharded parse): one per mate, records of every label file in input order
+        errors = []
+        writers = [_MateWriter(self, e, [(key, fh) for key, _, fh in files if key[0] == e], errors)
+                   for e in ((0, 1) if self.is_paired else (0,))] if writes else []
+        self._mark("writers_started")
+        try:
+            for chunks, tk in self._in_flight(self._chunk_stream(chunk_reads)):
+                t0 = time.perf_counter()
+                labels = self.collect_chunk(tk)
+                self._mark("labels")
+                self._stage_s["classify"] += time.perf_counter() - t0
+                counts[0] += len(chunks[0].seq_len)
+                if self._first_chunk is None:
+                    self._first_chunk = (time.perf_counter(), counts[0])
+                if writes:
+                    if errors:
+                        raise errors[0]
+                    for i, lab in enumerate((0, 1, -1), 1):
+                        counts[i] += int((labels == lab).sum())
+                    t0 = time.perf_counter()
+                    for w in writers:
+                        w.q.put((chunks[w.e], labels, tk["pieces"]))
+                    self._stage_s["wait_writer"] += time.perf_counter() - t0
+                    if self.rank == 0:
+                        self.logger.info('{}{}{} sequences finished!'.format(colors.OKGREEN, counts[0], colors.ENDC))
+        finally:
+            for w in writers:
+                w.q.put(None)
+            for w in writers:
+                w.thread.join()
+            # (given back in the order they were taken: the pool is last-in first-out, so the streams come back in the same roles every
+            # other run - and with them the allocator's blocks cached per stream)
+            for st in [self._copy_stream, self._post_stream] + [w.stream for w in writers]:
+                try:
+                    st.synchronize()
+                except Exception:      # noqa: BLE001 - (a failed run: the stream is given back all the same)
+                    pass
+                _gzmod.release_stream(st)
+        if errors:
+            raise errors[0]
+        self.thread_cpu_s["main"] = round(time.thread_time() - main_cpu0, 4)
+        self._close_arenas()
+        if writes:
+            self.writer_threads = sorted({fh.threads for key, _, fh in files if key != REPORT})
+            for _, _, fh in files:
+                fh.close()
+        if self.sharded_parse:
+            counts = self._join_parts(counts, [path for _, path, _ in files])
+        self.num_read, self.num_nonrrna, self.num_rrna, self.num_unknown = counts
+        if self.rank == 0:
+            self.logger.info('Processed {}{}{}{} sequences in total'.format(colors.BOLD, colors.OKCYAN, self.num_read, colors.ENDC))
+            self.logger.info('Detected {}{}{}{} non-rRNA sequences'.format(colors.BOLD, colors.OKCYAN, self.num_nonrrna, colors.ENDC))
+            self.logger.info('Detected {}{}{}{} rRNA sequences'.format(colors.BOLD, colors.OKCYAN, self.num_rrna, colors.ENDC))
+            if self.is_paired and self.args.ensure == 'both':
+                self.logger.info('Discarded {}{}{}{} unclassified sequences'.format(
+                    colors.BOLD, colors.OKCYAN, self.num_unknown, colors.ENDC))
+
+    def _mark(self, event, t=None):
+        """the first events of the run on its timeline, seconds since it started (timing first_chunks_timeline: tools/first_chunk_probe.py)"""
+        if len(self._timeline) < 30:
+            self._timeline.append((event, round((time.perf_counter() if t is None else t) - self._t_run, 4)))
+
+    def _all_gather(self, obj):
+        out = [None] * self.world
+        dist.all_gather_object(out, obj)
+        return out
+
+    def _plan_ranks(self):
+        """How the ranks share the input - the run's layout (module docstring): sets sharded_parse and, under it, this rank's share of
+        every input file (_ranges, bytes_parsed). Every rank calls it (collectives)."""
         # plain inputs under several ranks: every rank parses, classifies and writes its own byte range (no label exchange)
         plain = not any(fx.file_info(p)[1] for p in self.input)
         # ... and BGZF FASTQ inputs likewise: their members are independent, so every rank inflates (on its own GPU), parses, classifies
@@ -513,7 +708,6 @@ class Predictor:
                 and all(fx.get_seq_format(p) in ("fqgz", "fagz") and fx.bgzf_all_the_way(p) and fx.device_inflate_wanted(p) for p in self.input))
         views = None
         if bgzf:                    # the member index: rank 0 walks the headers, the others receive the three arrays per file
-            import torch.distributed as dist
             idx = [None]
             if self.rank == 0:
                 try:
@@ -527,21 +721,16 @@ class Predictor:
                 bgzf = False
             else:
                 views = [fx.BgzfView(p, index=i) for p, i in zip(self.input, idx[0])]
-        def all_gather(obj):
-            import torch.distributed as dist
-            out = [None] * self.world
-            dist.all_gather_object(out, obj)
-            return out
         # ... and single-stream .gz inputs (what sequencers write; round 6): every rank decodes its own compressed range on its own GPU -
         # symbols first, bytes once the ranks have exchanged the 64 KiB maps of their ranges (data_loader/gz_shard.py). What the device
-        # decoder does not take (or RD_GZ_SHARD=0) stays with the one-decode path below.
+        # decoder does not take (or RD_GZ_SHARD=0) stays with the one-decode path (the label gather).
         gzr = None
         if (self.multi and not plain and not bgzf and os.environ.get("RD_GZ_SHARD", "1") != "0"
                 and all(dr.device_ingest_kind(p) == "stream" for p in self.input)):
             from .data_loader import gz_shard
             t0 = time.perf_counter()
             gzr, why = gz_shard.prepare(self.input, self.rank, self.world, self.device, [fx.get_seq_format(p).startswith("fa") for p in self.input],
-                                        all_gather, rdist.shift_to_prev)
+                                        self._all_gather, rdist.shift_to_prev)
             if gzr is None and self.rank == 0:
                 self.logger.info('{}: one rank decodes'.format(why))
             self.gz_shard_s = time.perf_counter() - t0
@@ -554,306 +743,113 @@ class Predictor:
             if gzr is not None:
                 self._ranges = gzr
             else:
-                self._ranges = fx.plan_ranges(self.input, self.rank, self.world, all_gather, views=views)
+                self._ranges = fx.plan_ranges(self.input, self.rank, self.world, self._all_gather, views=views)
             self.bytes_parsed = [e - b for b, e in self._ranges]
             totals = [v.size for v in views] if views else [fx.file_info(p)[0] for p in self.input]
-            for r, bp in enumerate(all_gather(self.bytes_parsed)):
+            for r, bp in enumerate(self._all_gather(self.bytes_parsed)):
                 if self.rank == 0:
                     self.logger.info('Rank {} parses {} bytes of {}{}'.format(
                         r, ", ".join(str(b) for b in bp), ", ".join(str(t) for t in totals),
                         " (decompressed; BGZF members)" if bgzf else " (compressed; ranges of one DEFLATE stream)" if gzr is not None else ""))
-        def part(path):
-            if not self.sharded_parse:
-                return path
-            self._part_files.append(part_path(path, self.rank))
-            return self._part_files[-1]
-        writer = self.rank == 0 or self.sharded_parse
-        ends = (0, 1) if self.is_paired else (0,)
-        fhs = {}
-        from . import _native
-        _native.host_lib().rd_host_set_threads(int(self.args.threads))   # -t/--threads: gzip workers; read when a writer is opened
+
+    def _open_outputs(self):
+        """Open this rank's output set - under the sharded parse its part of every file: the label files, the '.unclassified.gz'
+        files (-e both, pairs) and the --read_report with its header. Returns [((mate, label), final path, handle)] in opening order."""
+        files = []
         log = self.logger.info if self.rank == 0 else (lambda *a, **k: None)
-        finals = []                                # final output paths, in the order the handles are opened
-        if writer:
-            if self.rrna is not None:
-                log('Writing output rRNA sequences into file: {}{}{}'.format(colors.OKBLUE, ", ".join(self.rrna), colors.ENDC))
-                fhs[1] = [fx.open_for_write(part(self.rrna[e])) for e in ends]
-                finals += [self.rrna[e] for e in ends]
-            log('Writing output non-rRNA sequences into file: {}{}{}'.format(colors.OKBLUE, ", ".join(self.output), colors.ENDC))
-            fhs[0] = [fx.open_for_write(part(self.output[e])) for e in ends]
-            finals += [self.output[e] for e in ends]
-            if self.is_paired and self.args.ensure == 'both':
-                unclf = [self.output[e] + '.unclassified.gz' for e in ends]
-                fhs[-1] = [fx.open_for_write(part(u)) for u in unclf]
-                finals += unclf
-                log('Writing unclassified sequences into file: {}{}{}'.format(colors.OKYELLOW, ", ".join(unclf), colors.ENDC))
-        if writer and self.sharded_parse:          # parts are joined below: the joined file gets ONE BGZF end-of-file block, at its end
-            for handles in fhs.values():
-                for fh in handles:
-                    fh.set_eof_marker(False)
-        num_read = num_nonrrna = num_rrna = num_unknown = 0
-        self._timeline.append(("outputs_open", round(time.perf_counter() - self._t_run, 4)))
-        self._stage_s = {"wait_reader": 0.0, "classify": 0.0, "wait_writer": 0.0}   # main-thread seconds per pipeline stage
-        self.thread_cpu_s = {}                                                      # CPU seconds of the pipeline's Python threads, by role
-        main_cpu0 = time.thread_time()
-        self._first_chunk = None
-        self.ingest = {}                           # per input file: which reader took it, and the device feeder's stage times
-        from . import gz as _gzmod
-        self._copy_stream = _gzmod.acquire_stream(self.device)      # (pooled: the allocator's cache is per stream, gz.acquire_stream)
-        self._post_stream = _gzmod.acquire_stream(self.device)
-        wr_streams = []
-        # which (mate, label) files are gzip outputs deflated on the device: every rank deflates the records it classified - and writes
-        # them itself (one rank, or the sharded parse of plain inputs) or, under the label gather, sends the members to rank 0
-        self._gz_files, self._gz_seq = [], 0
-        if self.gzip_on_device:                    # (the same list on every rank: it is derived from the arguments)
-            from .gz import DeviceGzip
-            self._gz_files = self.gz_output_files(self.output, self.rrna, self.is_paired, self.args.ensure)
-            if self._gz_files:
-                self._gz = DeviceGzip(self.device)
-        # every (mate, label) file this run writes; for chunks on the device the plain ones are packed there (rd_select_pack)
-        self._out_files = [(e, lab) for lab in fhs for e in ends]
-        if any(self._device_parse(p) for p in self.input):
-            from .gz import DeviceSelect
-            self._sel = DeviceSelect(self.device)
-        # --read_report: one line per read (pair), formatted on the device for every chunk; mate 1's writer appends the pieces
-        self._report = self._rep_fh = None
-        self._rep_gz, self._rep_seq = False, 0
+
+        def open_(label, paths):               # one file per mate: keys (mate, label); the report's is REPORT
+            for e, path in enumerate(paths):
+                if self.sharded_parse:
+                    self._part_files.append(part_path(path, self.rank))
+                files.append(((e, label), path, fx.open_for_write(self._part_files[-1] if self.sharded_parse else path)))
+                if self.sharded_parse:         # parts are joined later: the joined file gets ONE BGZF end-of-file block, at its end
+                    files[-1][2].set_eof_marker(False)
+        if self.rrna is not None:
+            log('Writing output rRNA sequences into file: {}{}{}'.format(colors.OKBLUE, ", ".join(self.rrna), colors.ENDC))
+            open_(1, self.rrna)
+        log('Writing output non-rRNA sequences into file: {}{}{}'.format(colors.OKBLUE, ", ".join(self.output), colors.ENDC))
+        open_(0, self.output)
+        if self.is_paired and self.args.ensure == 'both':
+            unclf = [path + '.unclassified.gz' for path in self.output]
+            open_(-1, unclf)
+            log('Writing unclassified sequences into file: {}{}{}'.format(colors.OKYELLOW, ", ".join(unclf), colors.ENDC))
         rep_path = getattr(self.args, 'read_report', None)
         if rep_path:
-            from .gz import DeviceReport, DeviceGzip, REPORT_HEADER_PE, REPORT_HEADER_SE
-            self._report = DeviceReport(self.device)
-            self._rep_gz = self.gzip_on_device and rep_path.endswith('gz')       # (else a .gz report is deflated by the host's writer)
-            if self._rep_gz and not self._gz_files:
-                self._gz = DeviceGzip(self.device)
-            if writer:
-                log('Writing per-read report into file: {}{}{}'.format(colors.OKBLUE, rep_path, colors.ENDC))
-                self._rep_fh = fx.open_for_write(part(rep_path))
-                finals.append(rep_path)
-                if self.sharded_parse:
-                    self._rep_fh.set_eof_marker(False)
-                if self.rank == 0:                 # (the sharded parse: rank 0's part comes first in the joined file)
-                    hdr = np.frombuffer(REPORT_HEADER_PE if self.is_paired else REPORT_HEADER_SE, dtype=np.uint8)
-                    self._rep_fh.write_text(hdr.ctypes.data, hdr.size)
+            log('Writing per-read report into file: {}{}{}'.format(colors.OKBLUE, rep_path, colors.ENDC))
+            open_(REPORT[1], [rep_path])
+            if self.rank == 0:                 # (the sharded parse: rank 0's part comes first in the joined file)
+                hdr = np.frombuffer(_gzmod.REPORT_HEADER_PE if self.is_paired else _gzmod.REPORT_HEADER_SE, dtype=np.uint8)
+                files[-1][2].write_text(hdr.ctypes.data, hdr.size)
+        return files
 
-        # writer threads (rank 0): one per mate, records of every label file in input order
-        wq, werr, wth = [], [], []
-        if writer:
-            def write_end(e, q):
-                # Two sets of pinned staging buffers: the bytes an item's files get from the GPU (gzip members / packed records) are
-                # fetched for item k+1 while item k is being written. The fetch is a kernel on this thread's stream (C ABI
-                # rd_copy_bytes), not a DMA copy - an SDMA queue is shared in order with copies that wait for kernels.
-                from . import _native
-                stages = [[], []]
-                torch.cuda.set_device(self.device)          # (the current device is per thread)
-                gz_copy = _gzmod.acquire_stream(self.device)
-                wr_streams.append(gz_copy)
+    def _device_outputs(self, out_files):
+        """what the GPU makes of the outputs: which (mate, label) files it deflates or packs, and the --read_report's lines"""
+        # which (mate, label) files are gzip outputs deflated on the device: every rank deflates the records it classified - and writes
+        # them itself (one rank, or the sharded parse) or, under the label gather, sends the members to rank 0
+        self._gz_files, self._gz_seq = [], 0
+        if self.gzip_on_device:                    # (the same list on every rank: it is derived from the arguments)
+            self._gz_files = self.gz_output_files(self.output, self.rrna, self.is_paired, self.args.ensure)
+        # every (mate, label) file this run writes; for chunks on the device the plain ones are packed there (rd_select_pack)
+        self._out_files = out_files
+        if any(self._device_parse(p) for p in self.input):
+            self._sel = _gzmod.DeviceSelect(self.device)
+        # --read_report: one line per read (pair), formatted on the device for every chunk; mate 1's writer appends the pieces
+        rep_path = getattr(self.args, 'read_report', None)
+        self._report = _gzmod.DeviceReport(self.device) if rep_path else None
+        self._rep_gz = bool(rep_path) and self.gzip_on_device and rep_path.endswith('gz')      # (else the host's writer deflates a .gz report)
+        self._rep_seq = 0
+        if self._gz_files or self._rep_gz:
+            self._gz = _gzmod.DeviceGzip(self.device)
 
-                def issue(item, k):
-                    """queue the D2H of everything the item's files take from the GPU; returns the jobs to complete() in file order"""
-                    chunk, labels, gzparts = item
-                    jobs, slot = [], 0
-                    for lab, handles in fhs.items():
-                        part = gzparts.get((e, lab)) if gzparts else None
-                        if part is None:
-                            jobs.append(("selected", handles[e], lab, None, None))
-                            continue
-                        as_text = (e, lab) not in self._gz_files      # packed records (rd_select_pack) instead of gzip members
-                        put = handles[e].write_text if as_text else handles[e].write_members
-                        for out, info in part:      # made on the GPU (one piece per rank under the label gather): fetch, append
-                            nb = int(info[1 if as_text else 0]) if info is not None else int(out.numel())
-                            if info is not None and int(info[3]):
-                                raise RuntimeError("device %s: the chunk's record table does not describe its text" % ("select" if as_text else "gzip"))
-                            if nb > out.numel():        # text that does not compress into the reserved half: the host deflates this piece
-                                jobs.append(("selected", handles[e], lab, None, None))
-                            elif nb and not out.is_cuda:
-                                jobs.append(("host", put, out, nb, None))
-                            elif nb:
-                                st = stages[k]
-                                if slot == len(st):
-                                    st.append(None)
-                                if st[slot] is None or st[slot].numel() < nb:
-                                    st[slot] = None
-                                    st[slot] = torch.empty(max(nb, 1 << 22) * 5 // 4, dtype=torch.uint8, pin_memory=True)
-                                _native.copy_bytes(st[slot], out, nb, gz_copy)
-                                done = _native.new_event()
-                                done.record(gz_copy)
-                                jobs.append(("dev", put, st[slot], nb, done))
-                                slot += 1
-                    if e == 0 and self._rep_fh is not None:
-                        slot = report_jobs(gzparts, jobs, k, slot)
-                    return item, jobs
-
-                def report_jobs(gzparts, jobs, k, slot):
-                    """the chunk's report pieces (one per rank under the label gather): gzip members made on the device, or its text"""
-                    fault = gzparts.get("report_fault")
-                    if fault is not None and int(fault[3]):
-                        raise RuntimeError("device report: the chunk's record table does not describe its text")
-                    fh = self._rep_fh
-                    for out, info in gzparts["report"]:
-                        as_text = not self._rep_gz
-                        nb = int(info[1 if as_text else 0]) if info is not None else int(out.numel())
-                        if nb > out.numel():        # members that do not fit the reserved half: the text goes, the host deflates it
-                            out, info = gzparts["report_text"]
-                            as_text, nb = True, int(info[1])
-                        put = fh.write_text if as_text else fh.write_members
-                        if nb and not out.is_cuda:
-                            jobs.append(("host", put, out, nb, None))
-                        elif nb:
-                            st = stages[k]
-                            if slot == len(st):
-                                st.append(None)
-                            if st[slot] is None or st[slot].numel() < nb:
-                                st[slot] = None
-                                st[slot] = torch.empty(max(nb, 1 << 22) * 5 // 4, dtype=torch.uint8, pin_memory=True)
-                            _native.copy_bytes(st[slot], out, nb, gz_copy)
-                            done = _native.new_event()
-                            done.record(gz_copy)
-                            jobs.append(("dev", put, st[slot], nb, done))
-                            slot += 1
-                    return slot
-
-                def complete(pending):
-                    (chunk, labels, _), jobs = pending
-                    for kind, put, src, nb, done in jobs:
-                        if kind == "selected":
-                            put.write_selected(chunk, labels, src)
-                            continue
-                        if done is not None:
-                            _native.wait_event(done)    # (sleeping in the driver: stream.synchronize() would spin a core)
-                        put(src.data_ptr(), nb)
-                    if chunk.release is not None:   # a shared-memory slot: free for the next chunk once its text is written
-                        chunk.release()
-                try:
-                    pending, k = None, 0
-                    while True:
-                        try:
-                            item = q.get() if pending is None else q.get_nowait()
-                        except queue.Empty:         # nothing to prefetch: write what is in hand, then wait
-                            complete(pending)
-                            pending = None
-                            continue
-                        if item is None:
-                            if pending is not None:
-                                complete(pending)
-                            return
-                        nxt = issue(item, k)
-                        k ^= 1
-                        if pending is not None:
-                            complete(pending)
-                        pending = nxt
-                except BaseException as ex:
-                    werr.append(ex)
-                    while q.get() is not None:   # keep draining so that the producer never blocks
-                        pass
-                finally:
-                    self.thread_cpu_s["writer:%d" % e] = round(time.thread_time(), 4)
-            for e in ends:
-                q = queue.Queue(maxsize=2)
-                wq.append(q)
-                wth.append(self._spawn(write_end, e, q))
-        def in_flight(stream):
-            """chunk k+1 is submitted (its H2D starts) before the labels of chunk k are waited for"""
-            prev = None
-            for chunks in stream:
-                t0 = time.perf_counter()
-                if len(self._timeline) < 30:          # (the first chunks' way through the pipeline, seconds since the run started: tools/first_chunk_probe.py)
-                    self._timeline.append(("chunk_of_%d_read" % len(chunks[0].seq_len), round(t0 - self._t_run, 4)))
-                tk = self.submit_chunk(chunks)
-                if len(self._timeline) < 30:
-                    self._timeline.append(("submitted", round(time.perf_counter() - self._t_run, 4)))
-                self._stage_s["classify"] += time.perf_counter() - t0
-                if prev is not None:
-                    yield prev
-                prev = (chunks, tk)
+    def _in_flight(self, stream):
+        """chunk k+1 is submitted (its H2D starts) before the labels of chunk k are waited for"""
+        prev = None
+        for chunks in stream:
+            t0 = time.perf_counter()
+            self._mark("chunk_of_%d_read" % len(chunks[0].seq_len), t0)    # (the first chunks' way through the pipeline)
+            tk = self.submit_chunk(chunks)
+            self._mark("submitted")
+            self._stage_s["classify"] += time.perf_counter() - t0
             if prev is not None:
                 yield prev
-        self._timeline.append(("writers_started", round(time.perf_counter() - self._t_run, 4)))
-        try:
-            for chunks, tk in in_flight(self._chunk_stream(chunk_reads)):
-                t0 = time.perf_counter()
-                labels = self.collect_chunk(tk)
-                if len(self._timeline) < 30:
-                    self._timeline.append(("labels", round(time.perf_counter() - self._t_run, 4)))
-                self._stage_s["classify"] += time.perf_counter() - t0
-                num_read += len(chunks[0].seq_len)
-                if self._first_chunk is None:
-                    self._first_chunk = (time.perf_counter(), num_read)
-                if writer:
-                    if werr:
-                        raise werr[0]
-                    num_nonrrna += int((labels == 0).sum())
-                    num_rrna += int((labels == 1).sum())
-                    num_unknown += int((labels == -1).sum())
-                    t0 = time.perf_counter()
-                    for e in ends:
-                        wq[e].put((chunks[e], labels, tk.get("gz")))
-                    self._stage_s["wait_writer"] += time.perf_counter() - t0
-                    log('{}{}{} sequences finished!'.format(colors.OKGREEN, num_read, colors.ENDC))
-        finally:
-            for q in wq:
-                q.put(None)
-            for th in wth:
-                th.join()
-            for st in [self._copy_stream, self._post_stream] + wr_streams:
-                try:
-                    st.synchronize()
-                except Exception:      # noqa: BLE001 - (a failed run: the stream is given back all the same)
-                    pass
-                _gzmod.release_stream(st)
-        if werr:
-            raise werr[0]
-        self.thread_cpu_s["main"] = round(time.thread_time() - main_cpu0, 4)
-        self._close_arenas()
-        if writer:
-            self.writer_threads = sorted({fh.threads for handles in fhs.values() for fh in handles})
-            for handles in fhs.values():
-                for fh in handles:
-                    fh.close()
-            if self._rep_fh is not None:
-                self._rep_fh.close()
-        if self.sharded_parse:                     # totals over the ranks; the parts are joined in rank order = input order
-            import torch.distributed as dist
-            tot = torch.tensor([num_read, num_nonrrna, num_rrna, num_unknown], dtype=torch.int64,
-                               device=self.device if dist.get_backend() == 'nccl' else 'cpu')
-            dist.all_reduce(tot, op=dist.ReduceOp.SUM)          # also the barrier: every part file is closed before the merge
-            num_read, num_nonrrna, num_rrna, num_unknown = (int(x) for x in tot.cpu().tolist())
-            # join the parts (rank order = input order) concurrently: every rank copies its own part to the offset that the sizes
-            # of the lower ranks' parts give; gzip parts are complete members, whose concatenation is a valid gzip file
-            mine = [os.path.getsize(part_path(path, self.rank)) for path in finals]
-            sizes = [None] * self.world
-            dist.all_gather_object(sizes, mine)
-            # the join goes into '<final>.joining' and is renamed after the last barrier: a run that dies while the parts are
-            # being placed never leaves a full-size, partly zero-filled file under the final name
-            tmps = [path + '.joining' for path in finals]
-            self._part_files += tmps if self.rank == 0 else []
-            # .gz files whose members were made on the device are BGZF: one end-of-file block (an empty member) behind the last part
-            from .gz import eof_block
-            tails = [eof_block() if (self.gzip_on_device and path.endswith('gz')) else b'' for path in finals]
-            if self.rank == 0:
-                for f, tmp in enumerate(tmps):
-                    with open(tmp, 'wb') as fh:
-                        body = sum(sz[f] for sz in sizes)
-                        fh.truncate(body + len(tails[f]))
-                        if tails[f]:
-                            fh.seek(body)
-                            fh.write(tails[f])
-            dist.barrier()
-            for f, path in enumerate(finals):
-                fx.place_part(tmps[f], part_path(path, self.rank), sum(sizes[r][f] for r in range(self.rank)))
-            dist.barrier()
-            if self.rank == 0:
-                for tmp, path in zip(tmps, finals):
-                    os.replace(tmp, path)
-            self._part_files = []
-            dist.barrier()
+            prev = (chunks, tk)
+        if prev is not None:
+            yield prev
+
+    def _join_parts(self, counts, finals):
+        """sharded parse: the four counters summed over the ranks (returned), and every output file joined from the ranks' parts"""
+        tot = torch.tensor(counts, dtype=torch.int64, device=self.device if dist.get_backend() == 'nccl' else 'cpu')
+        dist.all_reduce(tot, op=dist.ReduceOp.SUM)          # also the barrier: every part file is closed before the merge
+        counts = [int(x) for x in tot.cpu().tolist()]
+        # join the parts (rank order = input order) concurrently: every rank copies its own part to the offset that the sizes
+        # of the lower ranks' parts give; gzip parts are complete members, whose concatenation is a valid gzip file
+        mine = [os.path.getsize(part_path(path, self.rank)) for path in finals]
+        sizes = self._all_gather(mine)
+        # the join goes into '<final>.joining' and is renamed after the last barrier: a run that dies while the parts are
+        # being placed never leaves a full-size, partly zero-filled file under the final name
+        tmps = [path + '.joining' for path in finals]
+        self._part_files += tmps if self.rank == 0 else []
+        # .gz files whose members were made on the device are BGZF: one end-of-file block (an empty member) behind the last part
+        tails = [_gzmod.eof_block() if (self.gzip_on_device and path.endswith('gz')) else b'' for path in finals]
         if self.rank == 0:
-            self.logger.info('Processed {}{}{}{} sequences in total'.format(colors.BOLD, colors.OKCYAN, num_read, colors.ENDC))
-            self.logger.info('Detected {}{}{}{} non-rRNA sequences'.format(colors.BOLD, colors.OKCYAN, num_nonrrna, colors.ENDC))
-            self.logger.info('Detected {}{}{}{} rRNA sequences'.format(colors.BOLD, colors.OKCYAN, num_rrna, colors.ENDC))
-            if self.is_paired and self.args.ensure == 'both':
-                self.logger.info('Discarded {}{}{}{} unclassified sequences'.format(
-                    colors.BOLD, colors.OKCYAN, num_unknown, colors.ENDC))
-        self.num_read, self.num_nonrrna, self.num_rrna, self.num_unknown = num_read, num_nonrrna, num_rrna, num_unknown
+            for f, tmp in enumerate(tmps):
+                with open(tmp, 'wb') as fh:
+                    body = sum(sz[f] for sz in sizes)
+                    fh.truncate(body + len(tails[f]))
+                    if tails[f]:
+                        fh.seek(body)
+                        fh.write(tails[f])
+        dist.barrier()
+        for f, path in enumerate(finals):
+            fx.place_part(tmps[f], part_path(path, self.rank), sum(sizes[r][f] for r in range(self.rank)))
+        dist.barrier()
+        if self.rank == 0:
+            for tmp, path in zip(tmps, finals):
+                os.replace(tmp, path)
+        self._part_files = []
+        dist.barrier()
+        return counts
 
     @staticmethod
     def gz_output_files(output, rrna, is_paired, ensure):

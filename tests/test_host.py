@@ -231,3 +231,42 @@ def test_which_output_files_are_gzip(tmp_path):
     assert f(["o1.fq.gz", "o2.fq"], ["r1.fq", "r2.fastq.gz"], True, "rrna") == [(1, 1), (0, 0)]
     assert f(["o1.fq", "o2.fq"], None, True, "both") == [(0, -1), (1, -1)]
     assert f(["o1.fqgz", "o2.fq"], None, True, "none") == [(0, 0)]            # ends with 'gz', as the reference tests it
+
+
+def test_output_piece_size_fallback_and_fault():
+    """what an output file gets of the bytes the GPU made for one chunk (detect.Piece), with CPU tensors for the device buffers and
+    the pinned info words: gzip members are sized by info[0] and text by info[1]; bytes that exceed the buffer fall back to the
+    host's selection of the records (label files) or to the report's text (.gz report); a set fault word is an error; info None
+    (bytes gathered from the ranks) counts all of the buffer"""
+    import torch
+    from ribodetector_amd.detect import Piece
+
+    def info(gz_bytes, text_bytes, fault=0):
+        return torch.tensor([gz_bytes, text_bytes, 1, fault], dtype=torch.int64)
+
+    def taken(piece):
+        p, nb = piece.take()
+        return ("self" if p is piece else None if p is None else p), nb
+    buf = torch.zeros(100, dtype=torch.uint8)
+    gz, text = info(60, 500), info(500, 70)
+    assert taken(Piece(buf, gz, False, gz, "gzip")) == ("self", 60)                    # fits
+    assert taken(Piece(buf, text, True, text, "select")) == ("self", 70)
+    edge = info(100, 0)
+    assert taken(Piece(buf, edge, False, edge, "gzip")) == ("self", 100)
+    big = info(101, 0)
+    assert Piece(buf, big, False, big, "gzip").size() == 101
+    assert taken(Piece(buf, big, False, big, "gzip")) == (None, 0)                     # too big: the host writes the records
+    rep_info = info(0, 90)
+    rep_text = Piece(torch.zeros(200, dtype=torch.uint8), rep_info, True, rep_info, "report")
+    rep_gz = Piece(buf, info(150, 0), False, rep_info, "report", fallback=rep_text)
+    assert taken(rep_gz) == (rep_text, 90)                                              # too big: the report's text goes
+    assert taken(Piece(buf, info(40, 0), False, rep_info, "report", fallback=rep_text)) == ("self", 40)
+    bad = info(10, 20, fault=1)
+    for what, piece in (("select", Piece(buf, bad, True, bad, "select")), ("gzip", Piece(buf, bad, False, bad, "gzip")),
+                        ("report", Piece(buf, info(10, 0), False, bad, "report", fallback=rep_text))):
+        for call in (piece.size, piece.take):
+            with pytest.raises(RuntimeError, match="device %s: the chunk's record table does not describe its text" % what):
+                call()
+    gathered = Piece(buf[:37], None, False)
+    assert gathered.size() == 37 and taken(gathered) == ("self", 37)                   # info None: all of the buffer
+    assert taken(Piece(buf[:0], None, True)) == ("self", 0)
