@@ -791,7 +791,11 @@ int rd_host_gz_index(const uint8_t *buf, int64_t len, int64_t in_base, int64_t o
         // a member of more than 64 MiB (either side) is not for the member-per-wave decoder: the caller's batch buffers are sized for
         // BGZF blocks / this writer's 4 MiB members, and a crafted size field must not drive its allocations - streaming decoder
         if (isize > (64u << 20) || msize - 12 - (int64_t)xlen - 8 > (64 << 20)) { rc = 1; break; }
-        if (isize) {
+        // an empty member is skipped only when it is the canonical one (BGZF's end-of-file block: one empty fixed block, CRC 0); any other
+        // goes to the kernel, which checks it like every member (a damaged member that claims ISIZE 0 is an error there, as in zlib)
+        const bool canonical_empty = isize == 0 && msize - 12 - (int64_t)xlen - 8 == 2 && h[12 + xlen] == 0x03 && h[13 + xlen] == 0x00 &&
+                                     (t[0] | t[1] | t[2] | t[3]) == 0;
+        if (!canonical_empty) {
             out[n].in_off = in_base + p + 12 + (int64_t)xlen;
             out[n].out_off = out_base + ob;
             out[n].in_len = (int32_t)(msize - 12 - (int64_t)xlen - 8);

@@ -114,17 +114,20 @@ inline uint32_t sym_entry(Kind kind, int sym, int len) {
 
 // Canonical Huffman decoding table from code lengths: tab[0 .. 1<<tbits) is indexed by the next tbits input bits (LSB
 // first); codes longer than tbits go through F_SUB entries (value = offset of the second-level table, extra = its index
-// bits). Entries no code reaches are F_BAD. Returns false for an over-subscribed set of lengths.
+// bits). Entries no code reaches are F_BAD. Returns false for a set of lengths zlib's inflate rejects (inftrees.c): an over-subscribed
+// one, or an incomplete one - except a literal/length or distance code of one codeword of length 1, or of none at all.
 inline bool build_table(const uint8_t *lens, int n, int tbits, Kind kind, std::vector<uint32_t> &tab) {
     int count[16] = {0};
     for (int s = 0; s < n; ++s) ++count[lens[s]];
     count[0] = 0;
-    int left = 1;
+    int left = 1, longest = 0;
     for (int l = 1; l <= 15; ++l) {
         left <<= 1;
         left -= count[l];
         if (left < 0) return false;
+        if (count[l]) longest = l;
     }
+    if (left > 0 && longest > 0 && (kind == K_PRE || longest > 1)) return false;
     uint32_t next[16];
     uint32_t code = 0;
     for (int l = 1; l <= 15; ++l) {

@@ -64,7 +64,8 @@ struct GziCode { uint32_t first, count, offs; };
 __device__ __forceinline__ uint32_t gzi_rl(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 
 // Build the two orderings and the per-lane triples from S.len[0 .. nl) (literal/length) and S.len[nl .. nl + nd) (distance).
-// Returns false when a length set is over-subscribed (or incomplete in a way zlib's inflate also rejects).
+// Returns false for a length set zlib's inflate rejects (inftrees.c): over-subscribed, or incomplete - unless it is one codeword of
+// length 1, or none at all (a block without matches needs no distance code).
 __device__ __forceinline__ bool gzi_build(GziWave &S, int nl, int nd, int lane, GziCode &lit, GziCode &dst) {
     // counts per length: lane L counts the symbols whose length is L (lit: lanes 1..15; dist: lanes 17..31)
     const bool isd = lane >= 16;
@@ -76,7 +77,7 @@ __device__ __forceinline__ bool gzi_build(GziWave &S, int nl, int nd, int lane, 
         for (int s = n0; s < n1; ++s) cnt += S.len[s] == L ? 1u : 0u;
     // first code and offset of every length: a prefix scan over the 15 lengths, done by each lane for itself (15 steps, uniform)
     uint32_t first = 0, offs = 0, code = 0, off = 0;
-    int left = 1;
+    int left = 1, longest = 0;
     bool over = false;
     for (int l = 1; l <= 15; ++l) {
         const uint32_t cl = gzi_rl(cnt, l), cd = gzi_rl(cnt, 16 + l);
@@ -86,10 +87,9 @@ __device__ __forceinline__ bool gzi_build(GziWave &S, int nl, int nd, int lane, 
         off += c;
         left = (left << 1) - (int)c;
         over = over || left < 0;
+        longest = c ? l : longest;
     }
-    // over-subscribed: invalid. Incomplete codes are let through: a bit string that is no codeword is an error where it is met
-    // (zlib accepts an incomplete distance code of one symbol; an all-zero distance code is legal for a block without matches)
-    const uint64_t bad = __ballot((lane == 1 || lane == 17) && over);
+    const uint64_t bad = __ballot((lane == 1 || lane == 17) && (over || (left > 0 && longest > 1)));
     if (bad) return false;
     lit = GziCode{first, cnt, offs};
     dst = lit;   // (same registers: a lane is either a literal-code lane or a distance-code lane)
@@ -268,9 +268,9 @@ __global__ __launch_bounds__(64 * GZI_WAVES) __attribute__((amdgpu_waves_per_eu(
             if (type == 3) { err = GZI_BAD_BLOCK; break; }
             int nl, nd;
             if (type == 1) {                                            // fixed codes
-                nl = 288; nd = 30;
+                nl = 288; nd = 32;                                      // (complete codes; symbols 286, 287, 30, 31 are errors where met)
                 for (int s = lane; s < 288; s += 64) S.len[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8;
-                if (lane < 30) S.len[288 + lane] = 5;
+                if (lane < 32) S.len[288 + lane] = 5;
             } else {                                                    // dynamic codes: the code-length code first
                 nl = (int)((uint32_t)(H >> 3) & 31u) + 257; nd = (int)((uint32_t)(H >> 8) & 31u) + 1;
                 const int nc = (int)((uint32_t)(H >> 13) & 15u) + 4;
@@ -300,7 +300,7 @@ __global__ __launch_bounds__(64 * GZI_WAVES) __attribute__((amdgpu_waves_per_eu(
                         left = (left << 1) - (int)c;
                         over = over || left < 0;
                     }
-                    if (__ballot(lane == 1 && over)) { err = GZI_BAD_LENGTHS; break; }
+                    if (__ballot(lane == 1 && (over || left != 0))) { err = GZI_BAD_LENGTHS; break; }   // (zlib: complete, always)
                     cl = GziCode{first, lane < 16 ? cnt : 0u, offs};
                     if (lane < 19) {
                         const int l = S.len[300 + lane];

@@ -136,9 +136,9 @@ __device__ __forceinline__ int gzs_blocks(GziWave &S, int lane, const uint8_t *_
         int nl, nd;
         if (type == 1) {                                                // fixed codes
             if (!WRITE) { err = GZS_DECODE; break; }
-            nl = 288; nd = 30;
+            nl = 288; nd = 32;                                          // (complete codes, as gzi_build wants them)
             for (int s = lane; s < 288; s += 64) S.len[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8;
-            if (lane < 30) S.len[288 + lane] = 5;
+            if (lane < 32) S.len[288 + lane] = 5;
         } else {
             nl = (int)((uint32_t)(H >> 3) & 31u) + 257; nd = (int)((uint32_t)(H >> 8) & 31u) + 1;
             const int nc = (int)((uint32_t)(H >> 13) & 15u) + 4;
@@ -167,7 +167,7 @@ __device__ __forceinline__ int gzs_blocks(GziWave &S, int lane, const uint8_t *_
                     left = (left << 1) - (int)c;
                     over = over || left < 0;
                 }
-                if (__ballot(lane == 1 && (over || (!WRITE && left != 0)))) { err = GZS_DECODE; break; }
+                if (__ballot(lane == 1 && (over || left != 0))) { err = GZS_DECODE; break; }      // (zlib: complete, always)
                 cl = GziCode{first, lane < 16 ? cnt : 0u, offs};
                 if (lane < 19) {
                     const int l = S.len[300 + lane];

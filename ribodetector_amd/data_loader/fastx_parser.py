@@ -736,13 +736,14 @@ class BgzfView:
         self.fasta = get_seq_format(path).startswith("fa") if fasta is None else bool(fasta)      # records start with '>' lines
         if index is None:
             index = self.build_index(self.path)
-        self.comp_off, self.comp_len, self.out_off = index      # per non-empty member: file offset / size; text offsets (n + 1 entries)
+        self.comp_off, self.comp_len, self.out_off = index      # per member (BGZF's empty EOF block left out): file offset / size; text offsets (n + 1 entries)
         self.size = int(self.out_off[-1])
 
     @staticmethod
     def build_index(path):
-        """(comp_off int64[n], comp_len int64[n], out_off int64[n + 1]) of the non-empty members; ValueError if a member without a
-        size subfield is met (the file is not BGZF all the way: not for the sharded reader)"""
+        """(comp_off int64[n], comp_len int64[n], out_off int64[n + 1]) of the members but BGZF's canonical empty EOF block (another empty
+        member is listed: it is decoded and checked like any); ValueError if a member without a size subfield is met (the file is not BGZF
+        all the way: not for the sharded reader)"""
         L = N.host_lib()
         size = os.path.getsize(path)
         mm = np.memmap(path, dtype=np.uint8, mode="r") if size else np.zeros(0, dtype=np.uint8)

@@ -2,9 +2,11 @@
 """Soak of the single-stream gzip decoder on the device (csrc/rd_inflate_stream.hpp behind data_loader/device_reader.py, the DEFAULT for
 .gz FASTQ on one rank): random FASTQ-like files - read lengths from 30 bp to 30 kb, header styles of four platforms, qualities from
 2-level bins to uniform noise, LF / CR LF, N runs, low-complexity stretches - compressed with every zlib level / strategy / memLevel /
-window size, cut by flushes, glued from several members, read through the device reader with random batch sizes. THE property: the
-text delivered equals gzip.decompress()'s (line ends as LF), whichever way it went (device, host fallback before the first batch, host resume behind a
-failed batch); the record counts how often each way was taken.        python tools/gzs_soak.py <seconds> [seed] [out.json]"""
+window size, with libdeflate (levels 0-12; zlib where it is missing) and pigz-style (tests/deflate_corpus.py), cut by flushes, glued
+from several members, read through the device reader with random batch sizes. THE property: the text delivered equals
+gzip.decompress()'s (line ends as LF), whichever way it went (device, host fallback before the first batch, host resume behind a failed
+batch); the record counts how often each way was taken, and which encoders made the members.
+        python tools/gzs_soak.py <seconds> [seed] [out.json]"""
 import gzip
 import json
 import os
@@ -14,8 +16,11 @@ import time
 import zlib
 
 sys.path.insert(0, os.getcwd())
+sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
 import numpy as np
 import torch
+
+import deflate_corpus as D
 
 from ribodetector_amd import gz
 from ribodetector_amd.data_loader import device_reader as dr
@@ -62,7 +67,23 @@ def fastq_text(rng):
     return b"".join(out)
 
 
-def deflate_member(data, rng):
+def deflate_member(data, rng, erng):
+    """one member of `data`: zlib with parameters drawn from `rng` (the same draws as before libdeflate and pigz-style joined, so a seed
+    gives the files of earlier soak records when erng picks zlib), or - picked by `erng`, a generator of its own - libdeflate
+    (tools/e2e_bench.py's inputs; bgzip built with it: long blocks) or pigz-style (pieces primed with the 32 KiB before them, joined
+    by sync flushes)"""
+    body, meta = deflate_member_zlib(data, rng)
+    pick = erng.random()
+    if pick < 0.25 and D.libdeflate() is not None:
+        level, flags = int(erng.integers(0, 13)), int(erng.choice([0, 8]))
+        return D.gzip_member(D.libdeflate_raw(data, level), data, flags), dict(encoder="libdeflate", level=level, flags=flags)
+    if 0.25 <= pick < 0.4:
+        level, piece = int(erng.integers(1, 10)), int(erng.choice([1 << 16, 1 << 17, 1 << 20]))
+        return D.gzip_member(D.pigz_raw(data, level, piece), data), dict(encoder="pigz", level=level, piece=piece)
+    return body, meta
+
+
+def deflate_member_zlib(data, rng):
     level = int(rng.integers(1, 10))
     strategy = [zlib.Z_DEFAULT_STRATEGY, zlib.Z_DEFAULT_STRATEGY, zlib.Z_DEFAULT_STRATEGY, zlib.Z_FILTERED, zlib.Z_RLE, zlib.Z_HUFFMAN_ONLY, zlib.Z_FIXED][int(rng.integers(0, 7))]
     if rng.random() < 0.03:
@@ -86,7 +107,8 @@ def deflate_member(data, rng):
         hdr += b"a comment\0"
     if flags & 2:
         hdr += struct.pack("<H", zlib.crc32(hdr) & 0xffff)
-    return hdr + body + struct.pack("<II", zlib.crc32(data) & 0xffffffff, len(data) & 0xffffffff), dict(level=level, strategy=strategy, mem=mem, wbits=wbits, flags=flags)
+    return hdr + body + struct.pack("<II", zlib.crc32(data) & 0xffffffff, len(data) & 0xffffffff), dict(encoder="zlib", level=level, strategy=strategy, mem=mem,
+                                                                                                      wbits=wbits, flags=flags)
 
 
 def main():
@@ -94,19 +116,22 @@ def main():
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     out = sys.argv[3] if len(sys.argv) > 3 else None
     rng = np.random.default_rng(seed)
+    erng = np.random.default_rng([seed, 1])        # the encoder of each member (libdeflate, pigz-style or zlib): its own stream of draws
     d = "/dev/shm/gzs_soak_%d" % seed
     os.makedirs(d, exist_ok=True)
     p = os.path.join(d, "x.fastq.gz")
-    rec = {"files": 0, "device": 0, "fallback": 0, "resumed_on_host": 0, "mismatches": 0, "errors": 0, "text_bytes": 0, "batches": 0, "fallback_reasons": {}, "fallback_examples": [], "seed": seed}
+    rec = {"files": 0, "device": 0, "fallback": 0, "resumed_on_host": 0, "mismatches": 0, "errors": 0, "text_bytes": 0, "batches": 0, "fallback_reasons": {}, "fallback_examples": [], "seed": seed,
+           "encoders": {"zlib": 0, "libdeflate": 0, "pigz": 0}, "libdeflate_available": D.libdeflate() is not None}
     FIRST0, BATCH0 = dr.DeviceFeeder.FIRST, gz.DeviceStreamGunzip.BATCH
     t0 = time.time()
     while time.time() - t0 < seconds:
         parts, metas = [], []
         for _ in range(int(rng.choice([1, 1, 1, 2, 3]))):
-            m, meta = deflate_member(fastq_text(rng), rng)
+            m, meta = deflate_member(fastq_text(rng), rng, erng)
             parts.append(m); metas.append(meta)
+            rec["encoders"][meta["encoder"]] += 1
             if rng.random() < 0.1:
-                parts.append(deflate_member(b"", rng)[0])
+                parts.append(deflate_member_zlib(b"", rng)[0])
         blob = b"".join(parts) + (bytes(int(rng.integers(1, 600))) if rng.random() < 0.1 else b"")
         want = gzip.decompress(blob).replace(b"\r\n", b"\n")       # (the reader strips line ends like the reference's parser: CR LF -> LF)
         open(p, "wb").write(blob)
