@@ -311,6 +311,41 @@ __device__ __forceinline__ uint32_t gz_x8n(uint32_t nbytes) {   // x^(8 nbytes) 
     return p;
 }
 
+// slicing-by-4 tables, by a workgroup of 256 threads: tab[k][b] = the CRC of byte b followed by k zero bytes (barriers inside)
+__device__ __forceinline__ void gz_crc_tables(uint32_t (&tab)[4][256]) {
+    uint32_t c = threadIdx.x;
+    for (int b = 0; b < 8; ++b) c = (c & 1) ? (c >> 1) ^ 0xedb88320u : c >> 1;
+    tab[0][threadIdx.x] = c;
+    __syncthreads();
+    for (int k = 1; k < 4; ++k) {
+        c = (c >> 8) ^ tab[0][c & 0xffu];
+        tab[k][threadIdx.x] = c;
+    }
+    __syncthreads();
+}
+// CRC-32 of p[0 .. len) by a wave, p[b0 .. b1) by this lane: bytes up to a 16-byte boundary, then 16 bytes per load and four table reads
+// per dword that do not wait for each other; the lanes' pieces are combined with x^(8 n) mod P. Every lane returns the whole CRC.
+__device__ __forceinline__ uint32_t gz_crc_lane(const uint32_t (&tab)[4][256], const uint8_t *p, int b0, int b1, int len) {
+    uint32_t c = 0xffffffffu;
+    int b = b0;
+    for (; b < b1 && ((reinterpret_cast<uintptr_t>(p) + (uintptr_t)b) & 15) != 0; ++b) c = tab[0][(c ^ p[b]) & 0xffu] ^ (c >> 8);
+    for (; b + 16 <= b1; b += 16) {
+        const u32x4 v = *reinterpret_cast<const u32x4 *>(p + b);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t x = c ^ v[j];
+            c = tab[3][x & 0xffu] ^ tab[2][(x >> 8) & 0xffu] ^ tab[1][(x >> 16) & 0xffu] ^ tab[0][x >> 24];
+        }
+    }
+    for (; b < b1; ++b) c = tab[0][(c ^ p[b]) & 0xffu] ^ (c >> 8);
+    c = ~c;
+    if (b1 == b0) c = 0;
+    c = gz_multmodp(gz_x8n((uint32_t)(len - b1)), c);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c ^= (uint32_t)__shfl_xor((int)c, o);
+    return c;
+}
+
 // per-wave symbol counters: two 16-bit counters in a 32-bit word (LDS atomics are 32 bits wide; a part holds < 2^16 tokens)
 __device__ __forceinline__ void gz_count(uint32_t *hist, int sym) { atomicAdd(&hist[sym >> 1], 1u << (16 * (sym & 1))); }
 __device__ __forceinline__ uint32_t gz_counted(const uint32_t *hist, int sym) { return (hist[sym >> 1] >> (16 * (sym & 1))) & 0xffffu; }

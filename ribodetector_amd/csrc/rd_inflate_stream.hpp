@@ -57,308 +57,61 @@ static_assert(sizeof(GzsState) == 64 && sizeof(rd_gzs_state) == 64, "rd_gzs_stat
 
 __device__ __forceinline__ bool gzs_is_text(uint32_t c) { return (c >= 32u && c < 127u) || c == '\n' || c == '\r' || c == '\t'; }
 
+// The two policies of the sections' waves (GziStore and what a policy is: rd_inflate_dev.hpp). Every cause is GZS_DECODE - not DEFLATE, or not
+// what a block start looks like - but for the output's capacity and the input's end, which say something about the batch.
+template <bool WRITE>
+struct GzsCodes {
+    static constexpr bool EARLY = true;
+    static constexpr int code(GziCause c) {
+        return c == GZC_OUTPUT ? GZS_OVERFLOW : (c == GZC_IN_STORED || (WRITE && c == GZC_IN_SYMBOLS)) ? GZS_NOSTOP : GZS_DECODE;
+    }
+};
+struct GzsWrite : GziStore<uint16_t, GZS_WIN, GZS_MARK>, GzsCodes<true> {};      // 16-bit symbols with an unknown window (markers)
+constexpr int GZS_VALIDATE_SYMS = 3072;     // a candidate that decodes this many text symbols with complete codes IS a block start
+struct GzsValidate : GzsCodes<false> {      // nothing is stored: every literal must be a text byte
+    static constexpr bool VALIDATE = true;
+    static constexpr int cap = 1 << 30;
+    bool nontext = false, cut = false;      // cut: enough of the block has been seen (it was not decoded to its end)
+    __device__ __forceinline__ int reach(int op) const { return op + GZS_WIN; }
+    __device__ __forceinline__ bool more(int op) { cut = op >= GZS_VALIDATE_SYMS; return !cut; }
+    __device__ __forceinline__ void probe(int) {}
+    __device__ __forceinline__ void stored(int, int, int, const uint8_t *) {}
+    __device__ __forceinline__ void lits(int lane, uint64_t M, int, uint32_t ent) { nontext = nontext || (((M >> lane) & 1) && !gzs_is_text(ent & 0xffu)); }
+    __device__ __forceinline__ void lit(int, int, int sym) { nontext = nontext || !gzs_is_text((uint32_t)sym); }
+    __device__ __forceinline__ void copy(int, int, int, int) {}
+};
+
 // DEFLATE blocks from bit position p0 of the stream at inb (4-byte aligned; `limit` readable bytes, `end_bits` valid bits), by one wave.
 //   WRITE: 16-bit symbols to out16[0 .. cap) with an unknown window (markers), until the block boundary `stop_bit` is met exactly
 //          (GZS_MISMATCH when a boundary lies behind it), or the final block ends (fin = true);
-//   !WRITE: validation of a block-start candidate: ONE block, dynamic, complete codes, every literal a text byte.
+//   !WRITE: validation of a block-start candidate: ONE block, dynamic, complete codes, every literal a text byte (fin = true: it is
+//          the final block, or was not seen to its end).
 // Returns GZS_*; p_end = the bit behind the last block decoded, n_out = symbols.
-constexpr int GZS_VALIDATE_SYMS = 3072;     // a candidate that decodes this many text symbols with complete codes IS a block start
 template <bool WRITE>
 __device__ __forceinline__ int gzs_blocks(GziWave &S, int lane, const uint8_t *__restrict__ inb, int64_t limit, uint32_t end_bits, uint32_t p0, uint32_t stop_bit,
                           uint16_t *__restrict__ out16, int cap, uint32_t &p_end, int &n_out, bool &fin) {
-    auto load_dw = [&](int k) -> uint32_t {
-        const int64_t b = (int64_t)k * 4;
-        return b + 4 <= limit ? *reinterpret_cast<const uint32_t *>(inb + b) : 0u;
-    };
-    int win = (int)(p0 >> 5);
-    uint32_t cur = load_dw(win + lane), nxt = load_dw(win + GZI_STEP + lane);
+    GziIn in(inb, limit, lane, (int)(p0 >> 5));
     uint32_t p = p0;
     int op = 0;
     int err = GZS_OK;
-    auto ensure = [&](uint32_t q) {
-        while ((int)(q >> 5) - win >= GZI_STEP) {
-            if ((int)(q >> 5) - win >= 2 * GZI_STEP) {
-                win = (int)(q >> 5);
-                cur = load_dw(win + lane);
-            } else {
-                win += GZI_STEP;
-                cur = nxt;
-            }
-            nxt = load_dw(win + GZI_STEP + lane);
-        }
-    };
-    auto peek32 = [&](uint32_t q) -> uint32_t {
-        const int rel = (int)(q >> 5) - win;
-        const uint32_t d0 = gzi_rl(cur, rel), d1 = gzi_rl(cur, rel + 1);
-        return (uint32_t)(((((uint64_t)d1) << 32) | d0) >> (q & 31));
-    };
-    auto peek64 = [&](uint32_t q) -> uint64_t {
-        const int rel = (int)(q >> 5) - win;
-        const uint32_t d0 = gzi_rl(cur, rel), d1 = gzi_rl(cur, rel + 1), d2 = gzi_rl(cur, rel + 2);
-        const uint32_t s = q & 31;
-        const uint32_t lo = (uint32_t)((((uint64_t)d1 << 32) | d0) >> s), hi = (uint32_t)((((uint64_t)d2 << 32) | d1) >> s);
-        return ((uint64_t)hi << 32) | lo;
-    };
     bool last = false;
     fin = false;
-    int blocks = 0;
-    while (err == GZS_OK) {
-        if (WRITE) {
-            if (p == stop_bit) break;                                   // exactly where the next section starts: done
+    if constexpr (WRITE) {
+        GzsWrite k{{out16, cap}, {}};
+        while (p != stop_bit) {                                         // exactly where the next section starts: done
             if (p > stop_bit) { err = GZS_MISMATCH; break; }            // its start was not a block boundary of this stream
-        } else if (blocks == 1) {
-            break;
-        }
-        if (p + 3 > end_bits) { err = WRITE ? GZS_NOSTOP : GZS_DECODE; break; }
-        ensure(p);
-        const uint64_t H = peek64(p);
-        last = (H & 1) != 0;
-        const uint32_t type = (uint32_t)(H >> 1) & 3u;
-        p += 3;
-        ++blocks;
-        if (type == 0) {                                                // stored
-            if (!WRITE) { err = GZS_DECODE; break; }
-            p = (p + 7u) & ~7u;
-            ensure(p);
-            const uint32_t w = peek32(p);
-            const uint32_t ln = w & 0xffffu, nl = w >> 16;
-            p += 32;
-            if ((ln ^ nl) != 0xffffu) { err = GZS_DECODE; break; }
-            const int64_t ib = (int64_t)(p >> 3);
-            if (p + ln * 8 > end_bits) { err = GZS_NOSTOP; break; }
-            if (op + (int)ln > cap) { err = GZS_OVERFLOW; break; }
-            for (int k = lane; k < (int)ln; k += 64) out16[op + k] = inb[ib + k];
-            p += ln * 8; op += (int)ln;
-            if (last) { fin = true; break; }
-            continue;
-        }
-        if (type == 3) { err = GZS_DECODE; break; }
-        int nl, nd;
-        if (type == 1) {                                                // fixed codes
-            if (!WRITE) { err = GZS_DECODE; break; }
-            nl = 288; nd = 32;                                          // (complete codes, as gzi_build wants them)
-            for (int s = lane; s < 288; s += 64) S.len[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8;
-            if (lane < 32) S.len[288 + lane] = 5;
-        } else {
-            nl = (int)((uint32_t)(H >> 3) & 31u) + 257; nd = (int)((uint32_t)(H >> 8) & 31u) + 1;
-            const int nc = (int)((uint32_t)(H >> 13) & 15u) + 4;
-            p += 14;
-            if (nl > 286 || nd > 30) { err = GZS_DECODE; break; }
-            for (int s = lane; s < 320; s += 64) S.len[s] = 0;
-            ensure(p);
-            const uint64_t C = peek64(p);
-            if (lane < nc) S.len[300 + GZ_CLORD[lane]] = (uint8_t)((uint32_t)(C >> (3 * lane)) & 7u);
-            p += 3u * (uint32_t)nc;
-            GziCode cl;
-            {
-                const int L = lane & 15;
-                uint32_t cnt = 0;
-                if (L >= 1 && lane < 16)
-#pragma unroll 1
-                    for (int s = 0; s < 19; ++s) cnt += S.len[300 + s] == L ? 1u : 0u;
-                uint32_t first = 0, offs = 0, code = 0, off = 0;
-                int left = 1;
-                bool over = false;
-                for (int l = 1; l <= 7; ++l) {
-                    const uint32_t c = gzi_rl(cnt, l);
-                    if (L == l) { first = code; offs = off; }
-                    code = (code + c) << 1;
-                    off += c;
-                    left = (left << 1) - (int)c;
-                    over = over || left < 0;
-                }
-                if (__ballot(lane == 1 && (over || left != 0))) { err = GZS_DECODE; break; }      // (zlib: complete, always)
-                cl = GziCode{first, lane < 16 ? cnt : 0u, offs};
-                if (lane < 19) {
-                    const int l = S.len[300 + lane];
-                    if (l) {
-                        uint32_t before = 0, o = 0;
-#pragma unroll 1
-                        for (int t = 0; t < 19; ++t) {
-                            const int lt = S.len[300 + t];
-                            before += (t < lane && lt == l) ? 1u : 0u;
-                            o += (lt != 0 && lt < l) ? 1u : 0u;
-                        }
-                        S.dsym[o + before] = (uint16_t)lane;
-                    }
-                }
-            }
-            int i = 0, prev = 0;
-            // what is left of the two codes' space (units of 2^-15): a length set that over-subscribes its code is rejected where it does
-            // - a bit position that is NOT a block start (the search tries ~60 per section that pass the filter of the code-length code)
-            // gives itself away within a few symbols instead of after 316 of them and the table build's counting
-            int left_l = 1 << 15, left_d = 1 << 15;
-            while (i < nl + nd) {
-                if (p + 14 > end_bits + 64u) { err = GZS_DECODE; break; }
-                ensure(p);
-                int nb = 0;
-                const uint32_t v = peek32(p);
-                const int sym = gzi_decode(v, cl, lane, 0, S.dsym, nb);
-                if (sym < 0) { err = GZS_DECODE; break; }
-                const uint32_t x = v >> nb;
-                int rep = 1, val = sym;
-                if (sym == 16) { if (i == 0) { err = GZS_DECODE; break; } rep = 3 + (int)(x & 3u); val = prev; nb += 2; }
-                else if (sym == 17) { rep = 3 + (int)(x & 7u); val = 0; nb += 3; }
-                else if (sym == 18) { rep = 11 + (int)(x & 127u); val = 0; nb += 7; }
-                p += (uint32_t)nb;
-                if (i + rep > nl + nd) { err = GZS_DECODE; break; }
-                if (val) {
-                    const int in_l = i >= nl ? 0 : (i + rep <= nl ? rep : nl - i);      // symbols of the run in the literal/length code
-                    left_l -= in_l << (15 - val);
-                    left_d -= (rep - in_l) << (15 - val);
-                    if ((left_l | left_d) < 0) { err = GZS_DECODE; break; }
-                }
-                if (lane < rep) S.len[i + lane] = (uint8_t)val;
-                if (lane + 64 < rep) S.len[i + lane + 64] = (uint8_t)val;
-                if (lane + 128 < rep) S.len[i + lane + 128] = (uint8_t)val;
-                i += rep;
-                prev = val;
-            }
+            if (p + 3 > end_bits) { err = GZS_NOSTOP; break; }
+            err = gzi_block(S, in, end_bits, p, op, last, k);
             if (err != GZS_OK) break;
-            if (__builtin_amdgcn_readfirstlane((int)S.len[256]) == 0) { err = GZS_DECODE; break; }
-            if (!WRITE) {
-                // a block START candidate must carry complete codes, as every deflate encoder writes them (a single distance code may
-                // be incomplete; none at all is legal for a block without matches): sum 2^-len == 1
-                uint32_t sl = 0, sd = 0, ndist = 0;
-                for (int s = lane; s < nl; s += 64) { const int l = S.len[s]; sl += l ? (1u << (15 - l)) : 0u; }
-                if (lane < nd) { const int l = S.len[nl + lane]; sd = l ? (1u << (15 - l)) : 0u; ndist = l ? 1u : 0u; }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) { sl += (uint32_t)__shfl_xor((int)sl, o); sd += (uint32_t)__shfl_xor((int)sd, o); ndist += (uint32_t)__shfl_xor((int)ndist, o); }
-                sl = (uint32_t)__builtin_amdgcn_readfirstlane((int)sl);      // (the same in every lane: say so, or the branch - and with it
-                sd = (uint32_t)__builtin_amdgcn_readfirstlane((int)sd);      // every wave-uniform value of the loop - counts as divergent)
-                ndist = (uint32_t)__builtin_amdgcn_readfirstlane((int)ndist);
-                if (sl != (1u << 15) || (ndist > 1 && sd != (1u << 15))) { err = GZS_DECODE; break; }
-            }
+            if (last) { fin = true; break; }
         }
-        GziCode lit, dst;
-        if (!gzi_build(S, nl, nd, lane, lit, dst)) { err = GZS_DECODE; break; }
-        bool eob = false;
-        bool nontext = false;
-        while (!eob && err == GZS_OK) {
-            if (p > end_bits + 64u) { err = WRITE ? GZS_NOSTOP : GZS_DECODE; break; }
-            if (!WRITE && op >= GZS_VALIDATE_SYMS) { fin = true; break; }   // (validation: enough of the block has been seen; fin = "not at its end")
-            ensure(p);
-            uint32_t ent, adv, mres;
-            {
-                const int rel = (int)(p >> 5) - win;
-                const uint32_t d0 = gzi_rl(cur, rel), d1 = gzi_rl(cur, rel + 1), d2 = gzi_rl(cur, rel + 2), d3 = gzi_rl(cur, rel + 3),
-                               d4 = gzi_rl(cur, rel + 4);
-                const uint32_t s = p & 31;
-                const uint32_t A0 = (uint32_t)((((uint64_t)d1 << 32) | d0) >> s), A1 = (uint32_t)((((uint64_t)d2 << 32) | d1) >> s),
-                               A2 = (uint32_t)((((uint64_t)d3 << 32) | d2) >> s), A3 = (uint32_t)((((uint64_t)d4 << 32) | d3) >> s);
-                const bool lowh = lane < 32;
-                const uint32_t x0 = lowh ? A0 : A1, x1 = lowh ? A1 : A2, x2 = lowh ? A2 : A3;
-                const uint32_t sh = (uint32_t)(lane & 31);
-                const uint32_t lo = __builtin_amdgcn_alignbit(x1, x0, sh), hi = __builtin_amdgcn_alignbit(x2, x1, sh);
-                ent = S.llut[lo & ((1u << GZI_LBITS) - 1u)];
-                const uint32_t sym = ent & 511u, cl = ent >> 9;
-                adv = ((ent & 0x100u) == 0 && lane + (int)cl <= 63) ? cl : 0u;
-                const uint32_t ls = sym - 257u, l5 = ls & 31u;
-                const uint32_t le = (l5 < 8u || l5 >= 28u) ? 0u : (l5 >> 2) - 1u;
-                const uint32_t lb = l5 < 8u ? 3u + l5 : l5 >= 28u ? 258u : ((4u + (l5 & 3u)) << le) + 3u;
-                const uint32_t w1 = __builtin_amdgcn_alignbit(hi, lo, cl);
-                const uint32_t len = lb + (w1 & ((1u << le) - 1u));
-                const uint32_t w2 = __builtin_amdgcn_alignbit(hi, lo, cl + le);
-                const uint32_t de = S.dlut[w2 & ((1u << GZI_DBITS) - 1u)];
-                const uint32_t ds = de & 511u, dl = de >> 9;
-                const uint32_t d5 = ds & 31u;
-                const uint32_t dx = d5 < 4u ? 0u : (d5 >> 1) - 1u;
-                const uint32_t db = d5 < 4u ? 1u + d5 : ((2u + (d5 & 1u)) << dx) + 1u;
-                const uint32_t w3 = __builtin_amdgcn_alignbit(hi, lo, cl + le + dl);
-                const uint32_t dist = db + (w3 & ((1u << dx) - 1u));
-                const bool okm = ls < 29u && cl != 0 && dl != 0 && ds < 30u;
-                mres = okm ? (len | (dist << 9) | ((cl + le + dl + dx) << 25)) : 0u;
-            }
-            uint32_t pos = 0;
-            for (;;) {
-                uint64_t M = 0;
-                uint32_t a;
-                do {
-#pragma unroll
-                    for (int h = 0; h < 4; ++h) {
-                        a = gzi_rl(adv, (int)pos);
-                        asm("s_bitset1_b64 %0, %1" : "+s"(M) : "s"(pos));
-                        pos += a;
-                    }
-                } while (a != 0);
-                asm("s_bitset0_b64 %0, %1" : "+s"(M) : "s"(pos));
-                if (M) {
-                    const int n = __builtin_popcountll(M);
-                    if (op + n > cap) { err = GZS_OVERFLOW; break; }
-                    if (WRITE) {
-                        const int r = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
-                        if ((M >> lane) & 1) out16[op + r] = (uint16_t)(ent & 0xffu);
-                    } else {
-                        nontext = nontext || (((M >> lane) & 1) && !gzs_is_text(ent & 0xffu));
-                    }
-                    op += n;
-                }
-                const uint32_t e = gzi_rl(ent, (int)pos);
-                int sym = (int)(e & 511u), cl = (int)(e >> 9);
-                if (cl != 0 && sym < 256) break;
-                int len, dist;
-                const uint32_t mr = gzi_rl(mres, (int)pos);
-                if (mr != 0) {
-                    len = (int)(mr & 511u); dist = (int)((mr >> 9) & 0xffffu);
-                    pos += mr >> 25;
-                } else {
-                    if (cl == 0) {
-                        sym = gzi_decode(peek32(p + pos), lit, lane, 0, S.lsym, cl);
-                        if (sym < 0) { err = GZS_DECODE; break; }
-                    }
-                    if (sym < 256) {
-                        if (op >= cap) { err = GZS_OVERFLOW; break; }
-                        if (WRITE) { if (lane == 0) out16[op] = (uint16_t)sym; }
-                        else nontext = nontext || !gzs_is_text((uint32_t)sym);
-                        ++op;
-                        pos += (uint32_t)cl;
-                        if (pos > 53u) break;
-                        continue;
-                    }
-                    if (sym == 256) { pos += (uint32_t)cl; eob = true; break; }
-                    if (sym > 285) { err = GZS_DECODE; break; }
-                    uint64_t B = peek64(p + pos + (uint32_t)cl);
-                    const int ls = sym - 257;
-                    const int le = ls < 8 || ls == 28 ? 0 : (ls >> 2) - 1;
-                    len = (ls < 8 ? 3 + ls : ls == 28 ? 258 : ((4 + (ls & 3)) << le) + 3) + (int)((uint32_t)B & ((1u << le) - 1u));
-                    B >>= le;
-                    int dl = 0;
-                    const int ds = gzi_decode((uint32_t)B, dst, lane, 16, S.dsym, dl);
-                    if (ds < 0 || ds > 29) { err = GZS_DECODE; break; }
-                    B >>= dl;
-                    const int dx = ds < 4 ? 0 : (ds >> 1) - 1;
-                    dist = (ds < 4 ? 1 + ds : ((2 + (ds & 1)) << dx) + 1) + (int)((uint32_t)B & ((1u << dx) - 1u));
-                    pos += (uint32_t)(cl + le + dl + dx);
-                }
-                if (dist > op + GZS_WIN) { err = GZS_DECODE; break; }    // behind the 32 KiB window: not DEFLATE
-                if (op + len > cap) { err = GZS_OVERFLOW; break; }
-                if (WRITE) {
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    const int j0 = op - dist;                         // (negative: into the unknown window = a marker)
-                    if (dist >= len) {
-                        for (int k = lane; k < len; k += 64) {
-                            const int j = j0 + k;
-                            out16[op + k] = j < 0 ? (uint16_t)(GZS_MARK | (uint32_t)(GZS_WIN + j)) : out16[j];
-                        }
-                    } else if (dist == 1) {
-                        const uint16_t b = j0 < 0 ? (uint16_t)(GZS_MARK | (uint32_t)(GZS_WIN + j0)) : out16[j0];
-                        for (int k = lane; k < len; k += 64) out16[op + k] = b;
-                    } else {
-                        for (int k = lane; k < len; k += 64) {
-                            const int j = j0 + k % dist;
-                            out16[op + k] = j < 0 ? (uint16_t)(GZS_MARK | (uint32_t)(GZS_WIN + j)) : out16[j];
-                        }
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                }
-                op += len;
-                if (pos > 53u) break;
-            }
-            p += pos;
-        }
-        if (err != GZS_OK) break;
-        if (!WRITE && __ballot(nontext)) { err = GZS_DECODE; break; }
-        if (last) { fin = true; break; }
+    } else if (p + 3 > end_bits) {
+        err = GZS_DECODE;
+    } else {
+        GzsValidate k;
+        err = gzi_block(S, in, end_bits, p, op, last, k);
+        if (err == GZS_OK && __ballot(k.nontext)) err = GZS_DECODE;
+        fin = err == GZS_OK && (last || k.cut);
     }
     p_end = p;
     n_out = op;
@@ -394,20 +147,16 @@ __global__ __launch_bounds__(64 * GZS_WAVES) __attribute__((amdgpu_waves_per_eu(
         uint32_t res = GZS_NONE;
         if (lo64 + 80 < end_bits) {
             const uint32_t q_end = hi64 + 80 < end_bits ? (uint32_t)hi64 : end_bits - 80u;
-            auto load_dw = [&](int d) -> uint32_t {
-                const int64_t b = (int64_t)d * 4;
-                return b + 4 <= limit ? *reinterpret_cast<const uint32_t *>(comp + b) : 0u;
-            };
             // the section's bits pass through one register, 64 dwords at a time (one coalesced load per 57 dwords = 28 trips; a load of
             // eight dwords per trip put a memory round trip into every one of a wave's 2,048 trips)
             int wbase = (int)((uint32_t)lo64 >> 5);
-            uint32_t wcur = load_dw(wbase + lane);
+            uint32_t wcur = gzi_load_dw(comp, limit, wbase + lane);
             for (uint32_t q = (uint32_t)lo64; q < q_end && res == GZS_NONE; q += 64) {
                 // lane i: the 96 bits that start at q + i
                 const int d = (int)(q >> 5);
                 if (d - wbase > 64 - 7) {
                     wbase = d;
-                    wcur = load_dw(wbase + lane);
+                    wcur = gzi_load_dw(comp, limit, wbase + lane);
                 }
                 const int rel = d - wbase;
                 const uint32_t d0 = gzi_rl(wcur, rel), d1 = gzi_rl(wcur, rel + 1), d2 = gzi_rl(wcur, rel + 2), d3 = gzi_rl(wcur, rel + 3),
@@ -445,7 +194,7 @@ __global__ __launch_bounds__(64 * GZS_WAVES) __attribute__((amdgpu_waves_per_eu(
                     // with counts in range
                     if (!fin && pe + 17 <= end_bits) {
                         const int dd = (int)(pe >> 5);
-                        const uint32_t e0 = load_dw(dd), e1 = load_dw(dd + 1);
+                        const uint32_t e0 = gzi_load_dw(comp, limit, dd), e1 = gzi_load_dw(comp, limit, dd + 1);
                         const uint32_t hv = (uint32_t)(((((uint64_t)e1) << 32) | e0) >> (pe & 31));
                         const uint32_t bt = (hv >> 1) & 3u;
                         if (bt == 3u || (bt == 2u && (((hv >> 3) & 31u) > 29u || ((hv >> 8) & 31u) > 29u))) continue;
@@ -851,46 +600,17 @@ __global__ __launch_bounds__(256) void rd_gzs_symtext_kernel(const uint16_t *__r
 // global byte load per lane and step, the lanes 1 KiB apart - took 2.1 ms per 300 MB batch.
 constexpr int GZS_CTILE = 65536;
 __global__ __launch_bounds__(256) void rd_gzs_crc_kernel(const uint8_t *__restrict__ text, const GzsState *__restrict__ st, uint32_t *__restrict__ tile_crc) {
-    __shared__ uint32_t tab[4][256];      // tab[k][b]: the CRC of byte b followed by k zero bytes
-    {
-        uint32_t c = threadIdx.x;
-        for (int b = 0; b < 8; ++b) c = (c & 1) ? (c >> 1) ^ 0xedb88320u : c >> 1;
-        tab[0][threadIdx.x] = c;
-        __syncthreads();
-        uint32_t v = c;
-        for (int k = 1; k < 4; ++k) {
-            v = (v >> 8) ^ tab[0][v & 0xffu];
-            tab[k][threadIdx.x] = v;
-        }
-    }
-    __syncthreads();
+    __shared__ uint32_t tab[4][256];
+    gz_crc_tables(tab);
     const int64_t n = st->status == GZS_OK ? st->n_text : 0;
     const int lane = threadIdx.x & 63;
     const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t t0 = tile * GZS_CTILE;
     if (t0 >= n) return;
     const int len = (int)(n - t0 < GZS_CTILE ? n - t0 : GZS_CTILE);
-    const uint8_t *p = text + t0;
     const int per = 1024;
     const int b0 = lane * per < len ? lane * per : len, b1 = b0 + per < len ? b0 + per : len;
-    uint32_t c = 0xffffffffu;
-    int b = b0;
-    if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {                   // (b0 is a multiple of 1,024)
-        for (; b + 16 <= b1; b += 16) {
-            const u32x4 v = *reinterpret_cast<const u32x4 *>(p + b);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t x = c ^ v[j];
-                c = tab[3][x & 0xffu] ^ tab[2][(x >> 8) & 0xffu] ^ tab[1][(x >> 16) & 0xffu] ^ tab[0][x >> 24];
-            }
-        }
-    }
-    for (; b < b1; ++b) c = tab[0][(c ^ p[b]) & 0xffu] ^ (c >> 8);
-    c = ~c;
-    if (b1 == b0) c = 0;
-    c = gz_multmodp(gz_x8n((uint32_t)(len - b1)), c);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c ^= (uint32_t)__shfl_xor((int)c, o);
+    const uint32_t c = gz_crc_lane(tab, text + t0, b0, b1, len);
     if (lane == 0) tile_crc[tile] = c;
 }
 
