@@ -339,6 +339,26 @@ RD_API int rd_report_format(const uint8_t *text, int64_t text_bytes, const int64
                    const int8_t *labels, uint8_t *out, size_t out_cap, int64_t *line_start, int64_t *info, void *workspace, size_t workspace_bytes,
                    void *stream);
 
+/* Paired-end reads from ONE interleaved FASTQ chunk (the CLI's --interleaved, an extension): records 2k and 2k + 1 of the chunk's 2n
+ * records are mate 1 and mate 2 of pair k. text / text_bytes / rec_start [dev] int64[2n + 1] as rd_select_pack; seq_off [dev] int64[2n] and
+ * seq_len [dev] int32[2n] as rd_classify takes them. rd_pair_split writes pair_start [dev] int64[n + 1] = rec_start[2k] (entry n = the
+ * end): a pair is eight contiguous lines, so the pairs are the records of THIS table for rd_select_pack, rd_gz_compress_selected and
+ * rd_report_format; and the mates' sequence tables seq_off1 / seq_len1 / seq_off2 / seq_len2 [dev, n entries each], contiguous arrays
+ * for two rd_classify calls over the one text. check_ids != 0: the mate check - the id of a record is the bytes of its header after '@'
+ * up to the first of {space, \t, \r, \n, \v, \f} (rd_report_format's); two records are mates when their ids are equal, or mate 1's ends
+ * in "/1", mate 2's in "/2" and they are equal in front of those two bytes. info [dev] int64[4]: info[0] = pairs processed, info[1] =
+ * index of the first pair whose ids are not mates or -1, info[3] != 0: nothing is to be trusted - a table entry lies outside the text
+ * or, under check_ids, a record does not start with '@' or its header line runs past the record (check_ids == 0 reads no text).
+ * No workspace; asynchronous on `stream`.
+ * rd_pair_expand_labels: rec_labels [dev] int8[2n], rec_labels[2k + mate] = pair_labels[k] (mate 0 / 1) and the other mate's entry =
+ * RD_LABEL_SKIP, a value no output file selects: the records of ONE mate by label are then rd_select_pack / rd_gz_compress_selected over
+ * the full 2n-record table (they, and librd_host.so's rd_writer_write_selected, test labels for equality only). */
+#define RD_LABEL_SKIP 2
+RD_API int rd_pair_split(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int64_t *seq_off, const int32_t *seq_len, int64_t n_pairs,
+                  int32_t check_ids, int64_t *pair_start, int64_t *seq_off1, int32_t *seq_len1, int64_t *seq_off2, int32_t *seq_len2, int64_t *info,
+                  void *stream);
+RD_API int rd_pair_expand_labels(const int8_t *pair_labels, int64_t n_pairs, int32_t mate, int8_t *rec_labels, void *stream);
+
 /* ONE DEFLATE stream - a plain .gz, the format sequencers write - inflated on the device (round 5; the CLI's default for such FASTQ, RD_DEVICE_INFLATE=members keeps the host's decoders).
  * Replaces, for such files: gzip.open(path, 'rt') of reference data_loader/seq_encoder.py:21-39. The two-pass scheme of pugz (this
  * build's host reader: csrc/rd_pgzip.h) with one wave per SECTION of `section_bytes` compressed bytes: block starts are searched on the

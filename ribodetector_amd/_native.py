@@ -28,7 +28,9 @@ SYMBOLS = [
     "rd_fastq_index_workspace_bytes", "rd_fastq_index", "rd_fastq_gather", "rd_fastq_sample", "rd_fastq_strip_mark", "rd_fasta_index_workspace_bytes", "rd_fasta_index", "rd_fasta_gather", "rd_fasta_sample", "rd_select_workspace_bytes", "rd_select_pack", "rd_stream_create", "rd_stream_destroy", "rd_copy_bytes", "rd_gz_stream_workspace_bytes", "rd_gz_stream_inflate",
     "rd_gz_range_workspace_bytes", "rd_gz_range_decode", "rd_gz_range_resolve_workspace_bytes", "rd_gz_range_resolve",
     "rd_report_workspace_bytes", "rd_report_out_bound", "rd_report_format",
+    "rd_pair_split", "rd_pair_expand_labels",
 ]
+LABEL_SKIP = 2          # include/ribodetector_amd.h RD_LABEL_SKIP: the record label that no output file selects
 
 
 class RdWeights(C.Structure):
@@ -106,6 +108,8 @@ def lib():
     L.rd_report_out_bound.argtypes = [i64, i64]
     L.rd_report_out_bound.restype = sz
     L.rd_report_format.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp]
+    L.rd_pair_split.argtypes = [vp, i64, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.rd_pair_expand_labels.argtypes = [vp, i64, i32, vp, vp]
     L.rd_stream_create.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(vp)]
     L.rd_stream_destroy.argtypes = [vp]
     L.rd_copy_bytes.argtypes = [vp, vp, i64, i32, vp]

@@ -27,6 +27,7 @@
 //   rd_gz_*                            records of one label -> gzip (BGZF) members on the device (rd_deflate.hpp)
 //   rd_fq_* / rd_fa_*                  FASTQ records framed, FASTA batches re-written and indexed in HBM (rd_fastq_index.hpp, rd_fasta_index.hpp)
 //   rd_report_*                        per-read report lines (id, label, probabilities) of a chunk (rd_report.hpp)
+//   rd_pair_*                          the mates of an interleaved chunk: pair table, mates' sequence tables, mate check (rd_pairs.hpp)
 #include <stdlib.h>
 #include "rd_common.hpp"
 #include "rd_prep.hpp"
@@ -42,6 +43,7 @@
 #include "rd_fastq_index.hpp"
 #include "rd_fasta_index.hpp"
 #include "rd_report.hpp"
+#include "rd_pairs.hpp"
 
 // ================================================================================================
 // C ABI
@@ -1012,6 +1014,33 @@ int rd_report_format(const uint8_t *text, int64_t text_bytes, const int64_t *rec
     hipLaunchKernelGGL(rd_report_off_kernel, dim3(p.nb), dim3(256), 0, st, line_start, n, bsum, fault, info);
     hipLaunchKernelGGL(rd_report_write_kernel, dim3((unsigned)((n + RP_LINES - 1) / RP_LINES)), dim3(256), 0, st, text, rec_start, line_start, n, idlen, qs, labels,
                        logits_b ? 3 : 1, out, info);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+// paired-end reads from one interleaved chunk (rd_pairs.hpp): no workspace, one pass over the tables
+int rd_pair_split(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int64_t *seq_off, const int32_t *seq_len, int64_t n_pairs,
+                  int32_t check_ids, int64_t *pair_start, int64_t *seq_off1, int32_t *seq_len1, int64_t *seq_off2, int32_t *seq_len2, int64_t *info,
+                  void *stream) {
+    if (n_pairs < 0 || n_pairs > 0x3fffffffLL || text_bytes < 0) RD_FAIL(RD_E_INVALID, "rd_pair_split: bad n_pairs or text_bytes");
+    if (!info || !rec_start || !pair_start) RD_FAIL(RD_E_INVALID, "rd_pair_split: null info, rec_start or pair_start");
+    if (n_pairs > 0 && ((!text && text_bytes > 0) || !seq_off || !seq_len || !seq_off1 || !seq_len1 || !seq_off2 || !seq_len2))
+        RD_FAIL(RD_E_INVALID, "rd_pair_split: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    RD_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int64_t), st));
+    RD_HIP(hipMemsetAsync(info + 1, 0xff, sizeof(int64_t), st));      // -1: no pair failed the mate check (the kernel takes an unsigned minimum)
+    hipLaunchKernelGGL(rd_pair_split_kernel, dim3((unsigned)((n_pairs + 256 * PS_PAIRS) / (256 * PS_PAIRS))), dim3(256), 0, st, text, text_bytes, rec_start,
+                       seq_off, seq_len, n_pairs, (int)(check_ids != 0), pair_start, seq_off1, seq_len1, seq_off2, seq_len2, info);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+int rd_pair_expand_labels(const int8_t *pair_labels, int64_t n_pairs, int32_t mate, int8_t *rec_labels, void *stream) {
+    if (n_pairs < 0 || n_pairs > 0x3fffffffLL) RD_FAIL(RD_E_INVALID, "rd_pair_expand_labels: bad n_pairs");
+    if (mate != 0 && mate != 1) RD_FAIL(RD_E_INVALID, "rd_pair_expand_labels: mate must be 0 or 1; got %d", mate);
+    if (n_pairs == 0) return RD_OK;
+    if (!pair_labels || !rec_labels) RD_FAIL(RD_E_INVALID, "rd_pair_expand_labels: null pointer");
+    hipLaunchKernelGGL(rd_pair_expand_kernel, dim3((unsigned)((n_pairs + 2047) / 2048)), dim3(256), 0, (hipStream_t)stream, pair_labels, n_pairs, (int)mate, rec_labels);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }

@@ -1120,6 +1120,47 @@ def select_records(chunk, mask):
     return chunk.buf[keep].tobytes()
 
 
+# ---- paired-end reads from ONE interleaved file (the CLI's --interleaved): host views of a chunk of 2n records ----------------------------
+# Records 2k and 2k + 1 are mate 1 and mate 2 of pair k. The device makes the same views (csrc/rd_pairs.hpp); these are what the host
+# writer gets (NativeWriter.write_selected) for plain outputs of host-parsed chunks and for a device piece that did not fit.
+
+def interleaved_pairs(chunk):
+    """pairs in a chunk of an interleaved file (an odd last record has no mate and belongs to no pair)"""
+    return len(chunk.seq_len) // 2
+
+
+def pair_view(chunk):
+    """the chunk with PAIRS as its records: rec_start has every second entry (a pair is eight contiguous lines), seq_off / seq_len are
+    mate 1's. With the pair labels, write_selected writes an interleaved output. The text is shared, not copied."""
+    n = interleaved_pairs(chunk)
+    return chunk._replace(rec_start=np.ascontiguousarray(chunk.rec_start[0:2 * n + 1:2]), seq_off=chunk.seq_off[0:2 * n:2],
+                          seq_len=chunk.seq_len[0:2 * n:2], records=None, tensors=None)
+
+
+def expand_pair_labels(labels, mate):
+    """int8[2n] record labels that select mate 0 / 1's records by the pair labels: the other mate's records get LABEL_SKIP, which no
+    file selects. With them, write_selected over the chunk's full record table writes that mate's file of a split output."""
+    labels = np.asarray(labels, dtype=np.int8)
+    out = np.full(2 * len(labels), N.LABEL_SKIP, dtype=np.int8)
+    out[mate::2] = labels
+    return out
+
+
+def check_even_records(total):
+    """an interleaved input must hold an even number of records"""
+    if total % 2:
+        raise ValueError("interleaved input holds an odd number of records (%d): the last record has no mate" % total)
+
+
+def record_id(buf, start, end):
+    """the id of the record buf[start:end] (bytes): its header after the first byte up to the first white space - the report's read_id"""
+    head = bytes(buf[start + 1:end])
+    for i, c in enumerate(head):
+        if c == 32 or 9 <= c <= 13:
+            return head[:i]
+    return head
+
+
 class NativeWriter:
     """librd_host.so writer: gzip level 5 when the name ends with 'gz', else plain (reference detect.py:729-741)."""
 

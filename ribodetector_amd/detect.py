@@ -18,6 +18,9 @@ A run takes one of three layouts (Predictor._plan_ranks decides; under torchrun,
   * label gather - the other gzip inputs (one DEFLATE stream decoded once per node into shared memory, or by every rank): every
     rank classifies a contiguous shard of each chunk, and rank 0 gathers the 1-byte labels - and the gzip members and report
     lines made of every shard - over RCCL and writes (ribodetector_amd/dist.py).
+--interleaved (an extension): the pairs come from ONE FASTQ file whose records alternate mate 1, mate 2. Its chunks hold twice the
+records; rd_pair_split (csrc/rd_pairs.hpp) turns a chunk's tables into the two mates' sequence tables and a table of the pairs and
+checks the mates' ids, and from there on the run is the paired-end run (under several ranks: always the label gather).
 """
 import argparse
 import functools
@@ -100,6 +103,10 @@ class Piece(NamedTuple):
         if nb <= self.buf.numel():
             return self, nb
         return (None, 0) if self.fallback is None else self.fallback.take()
+
+
+class MateMismatch(RuntimeError):
+    """--interleaved: two consecutive records whose ids are not those of mates (the chunks in front of them have been written)"""
 
 
 class _MateWriter:
@@ -204,6 +211,9 @@ class Predictor:
         self._chunk_reads = None
         self._use_device = None                  # does the text of the inputs stay on the device? decided once per run
         self._report = None                      # --read_report: gz.DeviceReport (run_with_chunks)
+        self.interleaved = bool(getattr(args, 'interleaved', False))     # paired-end reads from ONE interleaved FASTQ file
+        self.mate_check = not getattr(args, 'no_mate_check', False)
+        self._pairs = None                       # --interleaved: gz.DevicePairSplit (run_with_chunks)
         self._install_cleanup()
 
     @property
@@ -361,20 +371,66 @@ class Predictor:
             return chunk.dev[0], chunk.dev[3]
         return arena, chunk.tensors[3][lo:hi + 1].to(self.device, non_blocking=True) - int(chunk.rec_start[lo])
 
+    def _split_pairs(self, chunk, lo, hi, on_dev):
+        """--interleaved: pairs [lo, hi) of a chunk of 2n records as two mates. The split runs once the chunk's tables are on the device
+        (a device chunk: behind its `ready` event; a host chunk: after the H2D of records [2 lo, 2 hi)). Returns (dev_in of the two
+        mates over the ONE text, pairs): pairs = the text with its record table and its pair table, for the outputs and the report, and
+        the pinned verdict of the mate check, which collect_chunk reads after the event it waits for anyway."""
+        cs, cur = self._copy_stream, torch.cuda.current_stream(self.device)
+        if on_dev:
+            cur.wait_event(chunk.ready)
+            text, so, sl, rs = chunk.dev
+        else:
+            text, so, sl = self._to_device(chunk, 2 * lo, 2 * hi, cs)
+            with torch.cuda.stream(cs):
+                rs = chunk.tensors[3][2 * lo:2 * hi + 1].to(self.device, non_blocking=True) - int(chunk.rec_start[2 * lo])
+            cur.wait_stream(cs)
+        ring = self._pair_seq % self.GZ_RING
+        self._pair_seq += 1
+        pair_start, m1, m2, info = self._pairs.split(text, rs, so, sl, hi - lo, check_ids=self.mate_check, slot=ring)
+        pairs = {"text": text, "rec_start": rs, "pair_start": pair_start, "info": _pinned(info), "ring": ring, "lo": lo,
+                 "first_record": self._chunk_first_record, "keep": (so, sl)}
+        return [(text,) + m1, (text,) + m2], pairs
+
+    def _check_pairs(self, chunk, pairs):
+        """the verdict of rd_pair_split on this rank's pairs of a chunk, once the event behind it has passed"""
+        info = pairs["info"]
+        if int(info[3]):
+            raise RuntimeError("device pair split: the chunk's record table does not describe its text")
+        k = int(info[1])
+        if k < 0:
+            return
+        k += pairs["lo"]                             # pair k of the chunk: its records 2 k and 2 k + 1
+        if isinstance(chunk, dr.DeviceChunk):        # (a failing run may wait for the three table entries and the two header lines)
+            rs = chunk.dev[3][2 * k:2 * k + 3].cpu().numpy()
+            buf, rs = chunk.dev[0][int(rs[0]):int(rs[2])].cpu().numpy(), rs - int(rs[0])
+        else:
+            buf, rs = chunk.buf, chunk.rec_start[2 * k:2 * k + 3]
+        ids = [fx.record_id(buf, int(rs[i]), int(rs[i + 1])).decode("latin-1") for i in (0, 1)]
+        first = pairs["first_record"] + 2 * k + 1
+        raise MateMismatch("interleaved input: records {} and {} are not mates (ids '{}' and '{}'): a record is missing or the file is "
+                           "not interleaved; --no_mate_check turns this check off".format(first, first + 1, ids[0], ids[1]))
+
     def submit_chunk(self, chunks):
         """Enqueue one chunk: H2D on the copy stream, kernels on the compute stream, D2H of the labels into pinned memory.
         Nothing here waits for the GPU, so the next chunk's H2D overlaps this chunk's kernels. Returns a ticket for
         collect_chunk()."""
-        n = len(chunks[0].seq_len)
+        n = fx.interleaved_pairs(chunks[0]) if self.interleaved else len(chunks[0].seq_len)
         bounds = None
         if self.gathers_labels:                     # equal bases (= recurrence steps) per rank, not equal read counts
-            work = sum(np.minimum(np.asarray(c.seq_len, dtype=np.int64), self.len) for c in chunks)
+            if self.interleaved:
+                work = np.minimum(np.asarray(chunks[0].seq_len[:2 * n], dtype=np.int64), self.len).reshape(n, 2).sum(1)
+            else:
+                work = sum(np.minimum(np.asarray(c.seq_len, dtype=np.int64), self.len) for c in chunks)
             bounds = rdist.shard_bounds(n, self.world, work)
         lo, hi = (0, n) if bounds is None else (bounds[self.rank], bounds[self.rank + 1])
         cs = self._copy_stream
         cur = torch.cuda.current_stream(self.device)
         on_dev = isinstance(chunks[0], dr.DeviceChunk)      # text and index already in HBM (data_loader/device_reader.py): nothing to copy
-        if on_dev:
+        pairs = None
+        if self.interleaved:
+            dev_in, pairs = self._split_pairs(chunks[0], lo, hi, on_dev)
+        elif on_dev:
             dev_in = [c.dev[:3] for c in chunks]
             for c in chunks:
                 cur.wait_event(c.ready)
@@ -402,18 +458,18 @@ class Predictor:
             else:
                 labels = outs[0][1].view(torch.int8)
             host = None if self.gathers_labels else _pinned(labels)
-            pieces = self._select_chunk(chunks, dev_in, labels, lo, hi, on_dev)
+            pieces = self._select_chunk(chunks, dev_in, labels, lo, hi, on_dev, pairs)
             if self._report is not None:
-                pieces[REPORT] = self._report_chunk(chunks, dev_in, outs, labels, lo, hi)
+                pieces[REPORT] = self._report_chunk(chunks, dev_in, outs, labels, lo, hi, pairs)
             finish = None
             if self.gathers_labels:                 # label gather (1 B per read) queued behind the kernels, collected later
                 _, finish = rdist.gather_labels(labels, n, dst=0, bounds=bounds, async_op=True)
             done = _native_mod.new_event()
             done.record(post)
         return {"n": n, "bounds": bounds, "labels": labels, "host": host, "finish": finish, "done": done, "keep": (dev_in, outs),
-                "pieces": pieces, "totals": [c.total for c in chunks] if on_dev else ()}
+                "pieces": pieces, "pairs": pairs, "chunk": chunks[0], "totals": [c.total for c in chunks] if on_dev else ()}
 
-    def _select_chunk(self, chunks, dev_in, labels, lo, hi, on_dev):
+    def _select_chunk(self, chunks, dev_in, labels, lo, hi, on_dev, pairs=None):
         """{(mate, label): [Piece]}: the label files whose records of this chunk are selected on the device, on the post stream beside
         the next chunk's recurrences, so that only the selected bytes travel to the host. A chunk whose text lives on the device: every
         file's, deflated (.gz outputs: BGZF members, csrc/rd_deflate.hpp) or packed into one text (rd_select_pack). Otherwise the .gz
@@ -431,18 +487,26 @@ class Predictor:
         # the label gather the full bound, every rank must take the same path; a chunk on the device has no host text to fall back to)
         frac = 1.0 if on_dev or self.gathers_labels else 0.5
         pieces = {}
+        views = {}                                  # mate -> (text, record table, labels) that select the records of its files
         for e, lab in files:
-            text, rs = self._device_text(chunks[e], dev_in[e][0], lo, hi)
+            if e not in views:
+                if pairs is None:
+                    views[e] = self._device_text(chunks[e], dev_in[e][0], lo, hi) + (labels.view(torch.int8),)
+                elif len(self.output) == 1:         # interleaved output: the pairs are the records
+                    views[e] = (pairs["text"], pairs["pair_start"], labels.view(torch.int8))
+                else:                               # split output: mate e's records of the full table (the other mate's: RD_LABEL_SKIP)
+                    views[e] = (pairs["text"], pairs["rec_start"], self._pairs.expand(labels.view(torch.int8), e, slot=pairs["ring"]))
+            text, rs, sel = views[e]
             gz = (e, lab) in self._gz_files
             if gz:
-                out, info = self._gz.compress_selected(text, rs, labels.view(torch.int8), lab, slot=(e, lab, ring), out_frac=frac)
+                out, info = self._gz.compress_selected(text, rs, sel, lab, slot=(e, lab, ring), out_frac=frac)
             else:
-                out, info = self._sel.pack_selected(text, rs, labels.view(torch.int8), lab, slot=(e, lab, ring))
+                out, info = self._sel.pack_selected(text, rs, sel, lab, slot=(e, lab, ring))
             info = _pinned(info)
             pieces[(e, lab)] = [Piece(out, info, not gz, info, "gzip" if gz else "select")]
         return pieces
 
-    def _report_chunk(self, chunks, dev_in, outs, labels, lo, hi):
+    def _report_chunk(self, chunks, dev_in, outs, labels, lo, hi, pairs=None):
         """--read_report: the pieces of the lines of records [lo, hi) of the chunk, formatted where mate 1's text, its record starts
         and the final logits already are (rd_report_format, on the post stream after the float64 pass and the pair fusion), then
         deflated there too for a .gz report (its line starts are a record table of the report text: rd_gz_compress_selected of all of
@@ -450,7 +514,7 @@ class Predictor:
         files' slots are not shared."""
         ring = self._rep_seq % self.GZ_RING
         self._rep_seq += 1
-        text, rs = self._device_text(chunks[0], dev_in[0][0], lo, hi)
+        text, rs = self._device_text(chunks[0], dev_in[0][0], lo, hi) if pairs is None else (pairs["text"], pairs["pair_start"])
         rep, line_start, info = self._report.format(text, rs, outs[0][0], outs[1][0] if self.is_paired else None, labels.view(torch.int8), slot=ring)
         fault = _pinned(info)
         piece = Piece(rep, fault, True, fault, "report")
@@ -463,6 +527,9 @@ class Predictor:
     def collect_chunk(self, tk):
         """Labels of a submitted chunk: int8 numpy on rank 0 (whole chunk, input order), None elsewhere."""
         if self.gathers_labels:
+            if tk["pairs"] is not None:              # every rank checks the mates of its own shard
+                _native_mod.wait_event(tk["done"])
+                self._check_pairs(tk["chunk"], tk["pairs"])
             labels = tk["finish"]()
             if tk["pieces"]:
                 self._gather_pieces(tk)
@@ -471,6 +538,8 @@ class Predictor:
         for t in tk.get("totals", ()):
             if int(t[0]) < 0:
                 raise RuntimeError("device chunk assembly failed (rd_fastq_gather)")
+        if tk["pairs"] is not None:
+            self._check_pairs(tk["chunk"], tk["pairs"])
         return tk["host"].numpy()
 
     def _gather_pieces(self, tk):
@@ -503,6 +572,10 @@ class Predictor:
 
     def _reader_queue(self, path, chunk_reads, depth=2, byte_range=None, arena=None, schedule=None):
         q = queue.Queue(maxsize=depth)
+        # --interleaved: every chunk size doubled (the first chunk and the growth steps too), so that a chunk holds an even number of
+        # records and chunk_reads PAIRS - the chunk boundaries of the two-file run, in pairs
+        mul = 2 if self.interleaved else 1
+        chunk_reads, first = chunk_reads * mul, (1 << 17) * mul
 
         def work():
             try:
@@ -511,14 +584,15 @@ class Predictor:
                 # framed there - no parser thread at all (data_loader/device_reader.py; RD_DEVICE_PARSE=0 keeps the host parser)
                 if arena is None and self._device_parse(path):
                     st = self.ingest.setdefault(os.path.basename(str(path)), {"path": "device"})
-                    stream = dr.get_seq_chunks_device(path, chunk_size=chunk_reads, byte_range=byte_range, first_chunk=1 << 17, schedule=schedule,
+                    stream = dr.get_seq_chunks_device(path, chunk_size=chunk_reads, byte_range=byte_range, first_chunk=first, schedule=schedule,
                                                       device=self.device, stats=st)
                 # one plain input file: its parser thread was the slowest stage of the pipeline - two readers over byte segments,
                 # small first chunks (mate files keep one reader each and exact chunk sizes: their chunks must pair up)
-                elif arena is None and len(self.input) == 1 and not fx.file_info(path)[1] and int(self.args.threads) >= 4:
+                # (not an interleaved file: its chunks must hold whole pairs)
+                elif arena is None and len(self.input) == 1 and not self.interleaved and not fx.file_info(path)[1] and int(self.args.threads) >= 4:
                     stream = fx.get_seq_chunks_parallel(path, chunk_size=chunk_reads, byte_range=byte_range, workers=2)
                 else:
-                    stream = fx.get_seq_chunks(path, chunk_size=chunk_reads, byte_range=byte_range, first_chunk=1 << 17, arena=arena,
+                    stream = fx.get_seq_chunks(path, chunk_size=chunk_reads, byte_range=byte_range, first_chunk=first, arena=arena,
                                                schedule=schedule, device=self.device)
                 for c in stream:
                     q.put(c)
@@ -550,7 +624,7 @@ class Predictor:
                 msg = [None]
                 if self.rank == 0:
                     fx.ShmArena.sweep_stale()
-                    chunk = self._chunk_reads or DEFAULT_CHUNK_READS
+                    chunk = (self._chunk_reads or DEFAULT_CHUNK_READS) * (2 if self.interleaved else 1)
                     fits, need = fx.ShmArena.fits(len(self.input), chunk, 2 * max(self.len, 50) + 80)
                     msg = [bool(fits)]
                     if not fits:
@@ -610,6 +684,42 @@ class Predictor:
                 return
             yield tuple(cs)
 
+    def _interleaved_chunks(self, stream):
+        """--interleaved: the chunks of the one file, each with an even number of records. Only the file's last chunk can be odd: its
+        pairs are classified and written like any other's, and the run ends with the error (check_even_records) afterwards."""
+        seen = 0
+        for (c,) in stream:
+            if seen % 2:
+                raise RuntimeError("interleaved input: a chunk with an odd number of records was not the last one")
+            self._chunk_first_record, seen = seen, seen + len(c.seq_len)
+            self._records_seen = seen
+            if fx.interleaved_pairs(c):
+                yield (c,)
+            elif c.release is not None:              # (a lone last record)
+                c.release()
+
+    def _writer_items(self, chunks, labels):
+        """what every writer thread gets of a chunk: (chunk, labels) whose records of one label are its files' - what the host writes
+        itself (fh.write_selected: plain outputs of host-parsed chunks, device pieces that did not fit)"""
+        if not self.interleaved:
+            return [(chunks[e], labels) for e in range(len(self.output))]
+        c = chunks[0]
+        if isinstance(c, dr.DeviceChunk):            # (everything comes from the device; there is no host text)
+            return [(c, labels)] * len(self.output)
+        if len(self.output) == 1:                    # interleaved output: the pairs are the records
+            return [(fx.pair_view(c), labels)]
+        # split output: both writers hold the full chunk, each with its mate's expanded labels; the chunk is released by the second
+        left, lock = [2], threading.Lock()
+
+        def release():
+            with lock:
+                left[0] -= 1
+                last = left[0] == 0
+            if last:
+                c.release()
+        both = c if c.release is None else c._replace(release=release)
+        return [(both, fx.expand_pair_labels(labels, e)) for e in (0, 1)]
+
     def run_with_chunks(self, chunk_reads=None):
         """Classify the input in chunks and write the outputs (reference detect.py:326-523)."""
         if chunk_reads is None:
@@ -633,15 +743,21 @@ class Predictor:
         # writer threads (rank 0; every rank under the sharded parse): one per mate, records of every label file in input order
         errors = []
         writers = [_MateWriter(self, e, [(key, fh) for key, _, fh in files if key[0] == e], errors)
-                   for e in ((0, 1) if self.is_paired else (0,))] if writes else []
+                   for e in range(len(self.output))] if writes else []      # (one per mate file; an interleaved output is one file)
         self._mark("writers_started")
+        stream = self._chunk_stream(chunk_reads)
+        self._records_seen, mismatch = 0, None
         try:
-            for chunks, tk in self._in_flight(self._chunk_stream(chunk_reads)):
+            for chunks, tk in self._in_flight(self._interleaved_chunks(stream) if self.interleaved else stream):
                 t0 = time.perf_counter()
-                labels = self.collect_chunk(tk)
+                try:
+                    labels = self.collect_chunk(tk)
+                except MateMismatch as e:           # the chunks in front of this one are written and the files closed, then the error
+                    mismatch = e
+                    break
                 self._mark("labels")
                 self._stage_s["classify"] += time.perf_counter() - t0
-                counts[0] += len(chunks[0].seq_len)
+                counts[0] += tk["n"]
                 if self._first_chunk is None:
                     self._first_chunk = (time.perf_counter(), counts[0])
                 if writes:
@@ -650,8 +766,8 @@ class Predictor:
                     for i, lab in enumerate((0, 1, -1), 1):
                         counts[i] += int((labels == lab).sum())
                     t0 = time.perf_counter()
-                    for w in writers:
-                        w.q.put((chunks[w.e], labels, tk["pieces"]))
+                    for w, (c, lab) in zip(writers, self._writer_items(chunks, labels)):
+                        w.q.put((c, lab, tk["pieces"]))
                     self._stage_s["wait_writer"] += time.perf_counter() - t0
                     if self.rank == 0:
                         self.logger.info('{}{}{} sequences finished!'.format(colors.OKGREEN, counts[0], colors.ENDC))
@@ -670,6 +786,10 @@ class Predictor:
                 _gzmod.release_stream(st)
         if errors:
             raise errors[0]
+        if mismatch is not None:
+            for _, _, fh in files:
+                fh.close()
+            raise mismatch
         self.thread_cpu_s["main"] = round(time.thread_time() - main_cpu0, 4)
         self._close_arenas()
         if writes:
@@ -686,6 +806,8 @@ class Predictor:
             if self.is_paired and self.args.ensure == 'both':
                 self.logger.info('Discarded {}{}{}{} unclassified sequences'.format(
                     colors.BOLD, colors.OKCYAN, self.num_unknown, colors.ENDC))
+        if self.interleaved:
+            fx.check_even_records(self._records_seen)
 
     def _mark(self, event, t=None):
         """the first events of the run on its timeline, seconds since it started (timing first_chunks_timeline: tools/first_chunk_probe.py)"""
@@ -700,6 +822,14 @@ class Predictor:
     def _plan_ranks(self):
         """How the ranks share the input - the run's layout (module docstring): sets sharded_parse and, under it, this rank's share of
         every input file (_ranges, bytes_parsed). Every rank calls it (collectives)."""
+        if self.interleaved and self.multi:
+            # byte ranges of an interleaved file would have to be cut at even record counts: one decode (per node, or per rank), host
+            # chunks, and every rank classifies a shard of each chunk's PAIRS
+            self.sharded_parse, self.bytes_parsed = False, None
+            if self.rank == 0:
+                self.logger.info('--interleaved input: the ranks take the label-gather layout (one decode, every rank classifies a shard '
+                                 'of the pairs of each chunk)')
+            return
         # plain inputs under several ranks: every rank parses, classifies and writes its own byte range (no label exchange)
         plain = not any(fx.file_info(p)[1] for p in self.input)
         # ... and BGZF FASTQ inputs likewise: their members are independent, so every rank inflates (on its own GPU), parses, classifies
@@ -794,6 +924,7 @@ class Predictor:
         self._out_files = out_files
         if any(self._device_parse(p) for p in self.input):
             self._sel = _gzmod.DeviceSelect(self.device)
+        self._pairs, self._pair_seq = (_gzmod.DevicePairSplit(self.device) if self.interleaved else None), 0
         # --read_report: one line per read (pair), formatted on the device for every chunk; mate 1's writer appends the pieces
         rep_path = getattr(self.args, 'read_report', None)
         self._report = _gzmod.DeviceReport(self.device) if rep_path else None
@@ -856,10 +987,10 @@ class Predictor:
         """(mate, label) of every output file that is written gzip-compressed - by name, like the reference's writer
         (detect.py:738: read_file.endswith('gz')); the '<out>.unclassified.gz' files of --ensure both (detect.py:390-400) always are.
         The same list on every rank (it depends on the arguments only): the files whose records are deflated on the device."""
-        ends = (0, 1) if is_paired else (0,)
-        files = [(e, lab) for lab, names in ((1, rrna), (0, output)) if names is not None for e in ends if names[e].endswith('gz')]
+        # (one file per mate - or, for the pairs of an interleaved input, ONE file per label: its key is mate 0's)
+        files = [(e, lab) for lab, names in ((1, rrna), (0, output)) if names is not None for e, name in enumerate(names) if name.endswith('gz')]
         if is_paired and ensure == 'both':
-            files += [(e, -1) for e in ends]
+            files += [(e, -1) for e in range(len(output))]
         return files
 
     def _close_arenas(self):
@@ -878,17 +1009,11 @@ class Predictor:
         self.output = self.args.output
         self.rrna = self.args.rrna
         self.pack_seq = self.config['arch']['args']['pack_seq']
-        num_inputs = len(self.input)
-        num_rrna_outputs = None if self.rrna is None else len(self.rrna)
-        if num_inputs != len(self.output) or num_inputs > 2 or num_inputs < 1:
-            self.logger.error('{}The number of input and output sequence files is invalid!{}'.format(colors.FAIL, colors.ENDC))
-            raise RuntimeError(
-                "Input or output should have no more than two files and they should have the same number of files.")
-        if num_rrna_outputs is not None and num_rrna_outputs != num_inputs:
-            self.logger.error('{}The number of output rRNA sequence files is invalid!{}'.format(colors.FAIL, colors.ENDC))
-            raise RuntimeError(
-                "Ouput rRNA should have no more than two files and they should the same number with input files.")
-        self.is_paired = (num_inputs == 2)
+        try:
+            self.is_paired = check_file_counts(self.input, self.output, self.rrna, self.interleaved)
+        except RuntimeError as e:
+            self.logger.error('{}{}{}'.format(colors.FAIL, _COUNT_ERRORS.get(str(e), str(e)), colors.ENDC))
+            raise
         check_read_report(self.args.read_report if hasattr(self.args, 'read_report') else None, self.output, self.rrna, self.is_paired,
                           self.args.ensure)
         # reference batch-size heuristic (detect.py:558-568); kept because --chunk_size is expressed in these batches
@@ -916,8 +1041,39 @@ class Predictor:
         return Predictor.separate_reads(r1_reads, lab), Predictor.separate_reads(r2_reads, lab)
 
 
+_COUNT_ERRORS = {       # what the log says in front of the two file-count errors of the reference
+    "Input or output should have no more than two files and they should have the same number of files.":
+        "The number of input and output sequence files is invalid!",
+    "Ouput rRNA should have no more than two files and they should the same number with input files.":
+        "The number of output rRNA sequence files is invalid!"}
+
+
+def check_file_counts(inputs, output, rrna, interleaved=False):
+    """The rules for the numbers of -i / -o / -r files (reference detect.py:525-545); returns whether the run is paired-end. Raises
+    RuntimeError. --interleaved: ONE FASTQ input whose records alternate mate 1, mate 2; one -o path (an interleaved output) or two
+    (mate 1's records and mate 2's), and as many -r paths if any."""
+    n_in, n_out = len(inputs or []), len(output or [])
+    n_rrna = None if rrna is None else len(rrna)
+    if interleaved:
+        if n_in != 1:
+            raise RuntimeError("--interleaved takes exactly one input file (-i), whose records alternate mate 1, mate 2; got {}".format(n_in))
+        if fx.get_seq_format(inputs[0]).startswith("fa"):
+            raise RuntimeError("--interleaved: interleaved FASTA is not supported (the input must be FASTQ)")
+        if n_out not in (1, 2):
+            raise RuntimeError("--interleaved takes one output file (-o: interleaved) or two (mate 1's and mate 2's records); got {}".format(n_out))
+        if n_rrna is not None and n_rrna != n_out:
+            raise RuntimeError("--interleaved: -r takes as many files as -o ({}); got {}".format(n_out, n_rrna))
+        return True
+    if n_in != n_out or n_in > 2 or n_in < 1:
+        raise RuntimeError("Input or output should have no more than two files and they should have the same number of files.")
+    if n_rrna is not None and n_rrna != n_in:
+        raise RuntimeError("Ouput rRNA should have no more than two files and they should the same number with input files.")
+    return n_in == 2
+
+
 def check_read_report(path, output, rrna, is_paired, ensure):
-    """--read_report must not name a file the run writes anyway: an -o / -r file or an '<out>.unclassified.gz' file (-e both, pairs)"""
+    """--read_report must not name a file the run writes anyway: an -o / -r file or an '<out>.unclassified.gz' file (-e both, pairs:
+    one per -o path, also when the pairs come from one interleaved file)"""
     if not path:
         return
     same = lambda a, b: os.path.abspath(a) == os.path.abspath(b)      # noqa: E731
@@ -968,6 +1124,12 @@ none: give label based on the mean probability of read pair.
                            'unclassified (-e both), the output file the read went to; p_rrna = softmax of the final logits\n'
                            '(p_rrna_pair: of the summed logits of the mates, what decides -e none) as 0.dddd / 1.0000.\n'
                            'gzip-compressed when the name ends with gz.')
+    args.add_argument('--interleaved', action='store_true',
+                      help='(extension) -i is ONE FASTQ file (plain or .gz) whose records alternate mate 1, mate 2: a paired-end run.\n'
+                           '-o (and -r) take one path - interleaved output, the selected pairs in input order - or two: mate 1\'s\n'
+                           'records and mate 2\'s, as for two input files. The ids of the two records of a pair (the header up to\n'
+                           'its first whitespace) must be equal, or equal up to a trailing /1 and /2.')
+    args.add_argument('--no_mate_check', action='store_true', help='(extension) with --interleaved: do not compare the ids of the mates')
     args.add_argument('-v', '--version', action='version', version='%(prog)s {version}'.format(version=__version__))
     return args
 
@@ -986,7 +1148,7 @@ def main(argv=None, log_level=None):
         fc = getattr(seq_pred, "_first_chunk", None)      # (time its labels arrived, its records): the rate after the pipeline filled
         steady = None
         if fc is not None and seq_pred.num_read > fc[1] and t2 > fc[0]:
-            steady = len(seq_pred.input) * (seq_pred.num_read - fc[1]) / (t2 - fc[0])
+            steady = (2 if seq_pred.is_paired else 1) * (seq_pred.num_read - fc[1]) / (t2 - fc[0])
         seq_pred.timing = {"load_model_s": t1 - t0, "detect_s": t2 - t1, "prefix_k": seq_pred.model.prefix_k,
                            "reads_per_s_after_first_chunk": steady, "ingest": getattr(seq_pred, "ingest", None),
                            "gz_ranges_s": getattr(seq_pred, "gz_shard_s", None), "pinned_cpus": getattr(seq_pred, "pinned_cpus", None),

@@ -117,6 +117,52 @@ class DeviceSelect:
         return out, info
 
 
+class DevicePairSplit:
+    """Paired-end reads from ONE interleaved chunk (C ABI rd_pair_split / rd_pair_expand_labels, csrc/rd_pairs.hpp): records 2k and
+    2k + 1 of the chunk's 2n records are the mates of pair k. split(text, rec_start, seq_off, seq_len, n_pairs) returns (pair_start
+    int64[n + 1], (seq_off1, seq_len1), (seq_off2, seq_len2), info): the pairs as a record table of the text and the mates' sequence
+    tables, owned by this object until the next call with the same `slot`; info int64[4] on the device = (pairs, first pair whose ids
+    are not mates or -1, 0, fault). expand(pair_labels, mate) returns the int8[2n] record labels that select mate `mate`'s records
+    (the other mate's are N.LABEL_SKIP). Asynchronous on the current stream."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._out = {}
+        self._lab = {}
+
+    def split(self, text, rec_start, seq_off, seq_len, n_pairs, check_ids=True, slot=0):
+        n, tb = int(n_pairs), int(text.numel())
+        if rec_start.dtype != torch.int64 or rec_start.numel() < 2 * n + 1 or not rec_start.is_contiguous():
+            raise TypeError("DevicePairSplit.split: rec_start must be a contiguous int64 tensor of 2 n + 1 entries")
+        if (seq_off.dtype != torch.int64 or seq_len.dtype != torch.int32 or min(seq_off.numel(), seq_len.numel()) < 2 * n
+                or not seq_off.is_contiguous() or not seq_len.is_contiguous() or text.dtype != torch.uint8):
+            raise TypeError("DevicePairSplit.split: seq_off int64[2 n], seq_len int32[2 n] (contiguous) and text uint8")
+        out = self._out.get(slot)
+        if out is None or out[0].numel() < n + 1:
+            self._out[slot] = None
+            cap = max(n + 1, 1024)
+            out = self._out[slot] = (torch.empty(cap, dtype=torch.int64, device=self.device),
+                                     torch.empty((2, cap), dtype=torch.int64, device=self.device), torch.empty((2, cap), dtype=torch.int32, device=self.device))
+        ps, so, sl = out
+        info = torch.empty(4, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().rd_pair_split(N.ptr(text), tb, N.ptr(rec_start), N.ptr(seq_off), N.ptr(seq_len), n, 1 if check_ids else 0, N.ptr(ps),
+                                          N.ptr(so[0]), N.ptr(sl[0]), N.ptr(so[1]), N.ptr(sl[1]), N.ptr(info), N.stream_ptr(self.device)), "rd_pair_split")
+        return ps[:n + 1], (so[0, :n], sl[0, :n]), (so[1, :n], sl[1, :n]), info
+
+    def expand(self, pair_labels, mate, slot=0):
+        n = int(pair_labels.numel())
+        if pair_labels.dtype not in (torch.int8, torch.uint8) or not pair_labels.is_contiguous():
+            raise TypeError("DevicePairSplit.expand: pair_labels must be a contiguous int8 / uint8 tensor")
+        out = self._lab.get((slot, mate))
+        if out is None or out.numel() < 2 * n:
+            self._lab[(slot, mate)] = None
+            out = self._lab[(slot, mate)] = torch.empty(max(2 * n, 2048), dtype=torch.int8, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().rd_pair_expand_labels(N.ptr(pair_labels), n, int(mate), N.ptr(out), N.stream_ptr(self.device)), "rd_pair_expand_labels")
+        return out[:2 * n]
+
+
 REPORT_HEADER_SE = b"#read_id\tlabel\tp_rrna\n"
 REPORT_HEADER_PE = b"#read_id\tlabel\tp_rrna_1\tp_rrna_2\tp_rrna_pair\n"
 
