@@ -359,6 +359,36 @@ RD_API int rd_pair_split(const uint8_t *text, int64_t text_bytes, const int64_t 
                   void *stream);
 RD_API int rd_pair_expand_labels(const int8_t *pair_labels, int64_t n_pairs, int32_t mate, int8_t *rec_labels, void *stream);
 
+/* The QC counters of a run (the CLI's --summary, an extension), accumulated where a chunk's text, sequence tables, final logits and
+ * labels already are. acc [dev] int64[RD_SUM_WORDS], zeroed by the caller at run start; every call ADDS the counters of its chunk, so
+ * the result is exact and does not depend on how the run was cut into chunks, shards or ranks (sum the ranks' arrays). A unit is a read
+ * (text_b == NULL: single-end, mate 0 only) or a pair; class c = label + 1 (0 unclassified, 1 nonrRNA, 2 rRNA) of the UNIT; mate m = 0 / 1.
+ *   RD_SUM_UNITS        [3]          units per label
+ *   RD_SUM_MATE_LABELS  [3][2][2]    pairs by class and (argmax of mate 1's logits, of mate 2's); argmax = l1 > l0 (a tie: 0)
+ *   RD_SUM_LENGTH       [2][3][513]  reads by mate, class and min(seq_len, 512) - the whole read, not the -l truncation
+ *   RD_SUM_P_RRNA       [3][3][100]  source (mate 1, mate 2, the pair's summed logits) x class x bin; bin = min(q / 100, 99) with
+ *                                    q = rint(softmax(logits)[1] * 1e4) in fp32, the value rd_report_format prints
+ *   RD_SUM_BASES        [2][3][5]    bases of the whole read by code: A, C, G, T (with U), other (lowercase included)
+ *   RD_SUM_GC           [2][3][101]  reads by 100 * (C + G) / (A + C + G + T), integer division; no A/C/G/T base: no bin
+ * text_x / bytes_x / seq_off_x [dev] int64[n] / seq_len_x [dev] int32[n] as rd_classify takes them (the two mates may share one text);
+ * logits_x [dev] fp32[n][2]; labels [dev] int8[n] in {-1, 0, 1}. info [dev] int64[4]: info[0] != 0 = NOTHING was added - a label outside
+ * -1..1 (bit 0), a seq_len < 0 (bit 1) or a sequence that does not lie inside its text (bit 2); else info[1] = n. A check pass decides
+ * that before the accumulate pass reads a byte. n == 0: a no-op (info, when given, is zeroed). Asynchronous on `stream`. */
+#define RD_SUM_LEN_BINS 513
+#define RD_SUM_P_BINS 100
+#define RD_SUM_GC_BINS 101
+#define RD_SUM_UNITS 0
+#define RD_SUM_MATE_LABELS 3
+#define RD_SUM_LENGTH 15
+#define RD_SUM_P_RRNA 3093
+#define RD_SUM_BASES 3993
+#define RD_SUM_GC 4023
+#define RD_SUM_WORDS 4629
+RD_API int64_t rd_summary_words(void);
+RD_API int rd_summary_accumulate(const uint8_t *text_a, int64_t bytes_a, const int64_t *seq_off_a, const int32_t *seq_len_a, const float *logits_a,
+                          const uint8_t *text_b, int64_t bytes_b, const int64_t *seq_off_b, const int32_t *seq_len_b, const float *logits_b,
+                          const int8_t *labels, int64_t n, int64_t *acc, int64_t *info, void *stream);
+
 /* ONE DEFLATE stream - a plain .gz, the format sequencers write - inflated on the device (round 5; the CLI's default for such FASTQ, RD_DEVICE_INFLATE=members keeps the host's decoders).
  * Replaces, for such files: gzip.open(path, 'rt') of reference data_loader/seq_encoder.py:21-39. The two-pass scheme of pugz (this
  * build's host reader: csrc/rd_pgzip.h) with one wave per SECTION of `section_bytes` compressed bytes: block starts are searched on the

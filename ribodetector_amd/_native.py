@@ -29,6 +29,7 @@ SYMBOLS = [
     "rd_gz_range_workspace_bytes", "rd_gz_range_decode", "rd_gz_range_resolve_workspace_bytes", "rd_gz_range_resolve",
     "rd_report_workspace_bytes", "rd_report_out_bound", "rd_report_format",
     "rd_pair_split", "rd_pair_expand_labels",
+    "rd_summary_words", "rd_summary_accumulate",
 ]
 LABEL_SKIP = 2          # include/ribodetector_amd.h RD_LABEL_SKIP: the record label that no output file selects
 
@@ -110,6 +111,9 @@ def lib():
     L.rd_report_format.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, sz, vp, vp, vp, sz, vp]
     L.rd_pair_split.argtypes = [vp, i64, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]
     L.rd_pair_expand_labels.argtypes = [vp, i64, i32, vp, vp]
+    L.rd_summary_words.argtypes = []
+    L.rd_summary_words.restype = i64
+    L.rd_summary_accumulate.argtypes = [vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp]
     L.rd_stream_create.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(vp)]
     L.rd_stream_destroy.argtypes = [vp]
     L.rd_copy_bytes.argtypes = [vp, vp, i64, i32, vp]

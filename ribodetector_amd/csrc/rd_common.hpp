@@ -68,6 +68,17 @@ __device__ __forceinline__ float rd_tanh(float x) {     // tanh x = 2 sigmoid(2x
 }
 
 // ------------------------------------------------------------------------------------------------
+// p(rRNA) as the per-read report prints it and the run summary bins it (rd_report.hpp, rd_summary.hpp):
+// q = rint(softmax(l)[1] * 1e4) from d = l1 - l0, in the form that does not overflow for either sign of d
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t rp_q(float d) {
+    const float e = expf(-fabsf(d));
+    const float p = d >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+    const float q = rintf(p * 10000.f);
+    return q >= 0.f ? (q <= 10000.f ? (uint32_t)q : 10000u) : 0u;        // (NaN logits: 0)
+}
+
+// ------------------------------------------------------------------------------------------------
 // model blob (device)
 // ------------------------------------------------------------------------------------------------
 struct DevModel {

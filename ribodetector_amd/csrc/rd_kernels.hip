@@ -28,6 +28,7 @@
 //   rd_fq_* / rd_fa_*                  FASTQ records framed, FASTA batches re-written and indexed in HBM (rd_fastq_index.hpp, rd_fasta_index.hpp)
 //   rd_report_*                        per-read report lines (id, label, probabilities) of a chunk (rd_report.hpp)
 //   rd_pair_*                          the mates of an interleaved chunk: pair table, mates' sequence tables, mate check (rd_pairs.hpp)
+//   rd_summary_*                       the QC counters of a run, added up chunk by chunk (rd_summary.hpp)
 #include <stdlib.h>
 #include "rd_common.hpp"
 #include "rd_prep.hpp"
@@ -44,6 +45,7 @@
 #include "rd_fasta_index.hpp"
 #include "rd_report.hpp"
 #include "rd_pairs.hpp"
+#include "rd_summary.hpp"
 
 // ================================================================================================
 // C ABI
@@ -1041,6 +1043,30 @@ int rd_pair_expand_labels(const int8_t *pair_labels, int64_t n_pairs, int32_t ma
     if (n_pairs == 0) return RD_OK;
     if (!pair_labels || !rec_labels) RD_FAIL(RD_E_INVALID, "rd_pair_expand_labels: null pointer");
     hipLaunchKernelGGL(rd_pair_expand_kernel, dim3((unsigned)((n_pairs + 2047) / 2048)), dim3(256), 0, (hipStream_t)stream, pair_labels, n_pairs, (int)mate, rec_labels);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+// the QC counters of a run (rd_summary.hpp): acc += the counters of this chunk, or nothing when the check pass finds a bad entry
+int64_t rd_summary_words(void) { return RD_SUM_WORDS; }
+
+int rd_summary_accumulate(const uint8_t *text_a, int64_t bytes_a, const int64_t *seq_off_a, const int32_t *seq_len_a, const float *logits_a,
+                          const uint8_t *text_b, int64_t bytes_b, const int64_t *seq_off_b, const int32_t *seq_len_b, const float *logits_b,
+                          const int8_t *labels, int64_t n, int64_t *acc, int64_t *info, void *stream) {
+    if (n < 0 || n > 0x7fffffffLL || bytes_a < 0 || bytes_b < 0) RD_FAIL(RD_E_INVALID, "rd_summary_accumulate: bad n or text bytes");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        if (info) RD_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int64_t), st));
+        return RD_OK;
+    }
+    if (!acc || !info || !labels || (!text_a && bytes_a > 0) || !seq_off_a || !seq_len_a || !logits_a) RD_FAIL(RD_E_INVALID, "rd_summary_accumulate: null pointer");
+    if (text_b && (!seq_off_b || !seq_len_b || !logits_b)) RD_FAIL(RD_E_INVALID, "rd_summary_accumulate: mate 2 needs its tables and logits");
+    if (!text_b) seq_off_b = nullptr;                     // (single-end: the check pass skips mate 2 by this pointer)
+    RD_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int64_t), st));
+    hipLaunchKernelGGL(rd_summary_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, bytes_a, seq_off_a, seq_len_a, bytes_b, seq_off_b, seq_len_b,
+                       labels, n, info);
+    hipLaunchKernelGGL(rd_summary_acc_kernel, dim3((unsigned)((n + SM_UNITS - 1) / SM_UNITS)), dim3(256), 0, st, text_a, seq_off_a, seq_len_a, logits_a, text_b,
+                       seq_off_b, seq_len_b, logits_b, labels, n, acc, info);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }

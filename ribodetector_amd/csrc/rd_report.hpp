@@ -25,13 +25,7 @@ __constant__ int RP_LABEL_LEN[3] = {12, 7, 4};
 
 __device__ __forceinline__ bool rp_ws(uint32_t c) { return c == ' ' || (c >= 9 && c <= 13); }   // space, \t \n \v \f \r
 
-// q = rint(softmax(l)[1] * 1e4) from d = l1 - l0, in the form that does not overflow for either sign of d
-__device__ __forceinline__ uint32_t rp_q(float d) {
-    const float e = expf(-fabsf(d));
-    const float p = d >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-    const float q = rintf(p * 10000.f);
-    return q >= 0.f ? (q <= 10000.f ? (uint32_t)q : 10000u) : 0u;        // (NaN logits: 0)
-}
+// (q = rp_q(l1 - l0): rd_common.hpp - the run summary bins the same value, rd_summary.hpp)
 
 __global__ __launch_bounds__(256) void rd_report_len_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const int64_t *__restrict__ rec_start,
                                                            int64_t n, const float *__restrict__ la, const float *__restrict__ lb,

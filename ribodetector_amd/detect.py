@@ -21,6 +21,8 @@ A run takes one of three layouts (Predictor._plan_ranks decides; under torchrun,
 --interleaved (an extension): the pairs come from ONE FASTQ file whose records alternate mate 1, mate 2. Its chunks hold twice the
 records; rd_pair_split (csrc/rd_pairs.hpp) turns a chunk's tables into the two mates' sequence tables and a table of the pairs and
 checks the mates' ids, and from there on the run is the paired-end run (under several ranks: always the label gather).
+--summary (an extension): every rank adds the QC counters of the units it classified to one int64 array on its GPU, chunk by chunk
+(rd_summary_accumulate, summary.py); the arrays are summed after the last chunk and rank 0 writes them as JSON once the run has ended well.
 """
 import argparse
 import functools
@@ -40,6 +42,7 @@ from . import __version__
 from . import _native as _native_mod
 from . import dist as rdist
 from . import gz as _gzmod
+from . import summary as _summod
 from .data_loader import device_reader as dr
 from .data_loader import fastx_parser as fx
 from .model import model as module_arch
@@ -214,6 +217,7 @@ class Predictor:
         self.interleaved = bool(getattr(args, 'interleaved', False))     # paired-end reads from ONE interleaved FASTQ file
         self.mate_check = not getattr(args, 'no_mate_check', False)
         self._pairs = None                       # --interleaved: gz.DevicePairSplit (run_with_chunks)
+        self._summary = None                     # --summary: summary.DeviceSummary (run_with_chunks)
         self._install_cleanup()
 
     @property
@@ -461,13 +465,17 @@ class Predictor:
             pieces = self._select_chunk(chunks, dev_in, labels, lo, hi, on_dev, pairs)
             if self._report is not None:
                 pieces[REPORT] = self._report_chunk(chunks, dev_in, outs, labels, lo, hi, pairs)
+            sum_info = None
+            if self._summary is not None:           # --summary: this rank's units of the chunk, counted where they are (rd_summary_accumulate)
+                sum_info = _pinned(self._summary.add(dev_in[0], outs[0][0], dev_in[1] if self.is_paired else None,
+                                                     outs[1][0] if self.is_paired else None, labels.view(torch.int8)))
             finish = None
             if self.gathers_labels:                 # label gather (1 B per read) queued behind the kernels, collected later
                 _, finish = rdist.gather_labels(labels, n, dst=0, bounds=bounds, async_op=True)
             done = _native_mod.new_event()
             done.record(post)
         return {"n": n, "bounds": bounds, "labels": labels, "host": host, "finish": finish, "done": done, "keep": (dev_in, outs),
-                "pieces": pieces, "pairs": pairs, "chunk": chunks[0], "totals": [c.total for c in chunks] if on_dev else ()}
+                "pieces": pieces, "pairs": pairs, "chunk": chunks[0], "totals": [c.total for c in chunks] if on_dev else (), "summary": sum_info}
 
     def _select_chunk(self, chunks, dev_in, labels, lo, hi, on_dev, pairs=None):
         """{(mate, label): [Piece]}: the label files whose records of this chunk are selected on the device, on the post stream beside
@@ -527,9 +535,11 @@ class Predictor:
     def collect_chunk(self, tk):
         """Labels of a submitted chunk: int8 numpy on rank 0 (whole chunk, input order), None elsewhere."""
         if self.gathers_labels:
-            if tk["pairs"] is not None:              # every rank checks the mates of its own shard
+            if tk["pairs"] is not None or tk["summary"] is not None:     # every rank checks the mates and the counters of its own shard
                 _native_mod.wait_event(tk["done"])
+            if tk["pairs"] is not None:
                 self._check_pairs(tk["chunk"], tk["pairs"])
+            self._check_summary(tk)
             labels = tk["finish"]()
             if tk["pieces"]:
                 self._gather_pieces(tk)
@@ -540,7 +550,15 @@ class Predictor:
                 raise RuntimeError("device chunk assembly failed (rd_fastq_gather)")
         if tk["pairs"] is not None:
             self._check_pairs(tk["chunk"], tk["pairs"])
+        self._check_summary(tk)
         return tk["host"].numpy()
+
+    @staticmethod
+    def _check_summary(tk):
+        """the verdict of rd_summary_accumulate on this rank's units of a chunk, once the event behind it has passed"""
+        if tk["summary"] is not None and int(tk["summary"][0]):
+            raise RuntimeError("device summary: the chunk's sequence tables or labels are not what the counters can take (fault %d); "
+                               "nothing of the chunk was counted" % int(tk["summary"][0]))
 
     def _gather_pieces(self, tk):
         """label gather: the pieces every rank made of its shard travel to rank 0, which appends them in rank order = input order
@@ -808,6 +826,28 @@ class Predictor:
                     colors.BOLD, colors.OKCYAN, self.num_unknown, colors.ENDC))
         if self.interleaved:
             fx.check_even_records(self._records_seen)
+        if self._summary is not None:
+            self._write_summary()
+
+    def _write_summary(self):
+        """--summary, at the end of a run that went well (every output file is closed): the ranks' counters summed, checked against
+        the run's own counts and written by rank 0 as JSON"""
+        acc = self._summary.acc
+        if self.multi:                             # every rank counted its own shard / byte range
+            acc = rdist.reduce_counts(acc)
+        if self.rank != 0:
+            return
+        acc = acc.cpu().numpy()
+        units = [int(x) for x in _summod.sections(acc)["units"]]
+        if units != [self.num_unknown, self.num_nonrrna, self.num_rrna]:
+            raise RuntimeError("--summary: the device counted {} unclassified / non-rRNA / rRNA units, the run {}".format(
+                units, [self.num_unknown, self.num_nonrrna, self.num_rrna]))
+        path = self.args.summary
+        doc = _summod.to_json(acc, {"version": __version__, "paired": bool(self.is_paired), "interleaved": self.interleaved, "len": int(self.len),
+                                    "ensure": self.args.ensure, "model": self.state_key, "inputs": list(self.input)})
+        _summod.write_json(path, doc)
+        frac = doc["reads"]["rRNA_fraction"]
+        self.logger.info('rRNA fraction: {} (summary: {})'.format("n/a" if frac is None else "%.6f" % frac, path))
 
     def _mark(self, event, t=None):
         """the first events of the run on its timeline, seconds since it started (timing first_chunks_timeline: tools/first_chunk_probe.py)"""
@@ -930,6 +970,8 @@ class Predictor:
         self._report = _gzmod.DeviceReport(self.device) if rep_path else None
         self._rep_gz = bool(rep_path) and self.gzip_on_device and rep_path.endswith('gz')      # (else the host's writer deflates a .gz report)
         self._rep_seq = 0
+        # --summary: the run's QC counters, one int64 array per rank that every chunk adds to on the post stream
+        self._summary = _summod.DeviceSummary(self.device) if getattr(self.args, 'summary', None) else None
         if self._gz_files or self._rep_gz:
             self._gz = _gzmod.DeviceGzip(self.device)
 
@@ -1016,6 +1058,8 @@ class Predictor:
             raise
         check_read_report(self.args.read_report if hasattr(self.args, 'read_report') else None, self.output, self.rrna, self.is_paired,
                           self.args.ensure)
+        check_summary(getattr(self.args, 'summary', None), self.output, self.rrna, self.is_paired, self.args.ensure,
+                      getattr(self.args, 'read_report', None))
         # reference batch-size heuristic (detect.py:558-568); kept because --chunk_size is expressed in these batches
         denom = (2 * self.len * 6.4) if self.is_paired else (self.len * 6.4)
         self.batch_size = 2 ** math.floor(math.log2(((self.args.memory - 2) * 1024 * 1024) / denom))
@@ -1086,6 +1130,21 @@ def check_read_report(path, output, rrna, is_paired, ensure):
                 raise RuntimeError("--read_report {} is the unclassified pairs' output file".format(path))
 
 
+def check_summary(path, output, rrna, is_paired, ensure, read_report=None):
+    """--summary must not name a file the run writes anyway: an -o / -r file, an '<out>.unclassified.gz' file (-e both, pairs) or the
+    --read_report"""
+    if not path:
+        return
+    taken = [(o, "an output sequence file (-o / -r)") for o in list(output or []) + list(rrna or [])]
+    if is_paired and ensure == 'both':
+        taken += [(o + '.unclassified.gz', "the unclassified pairs' output file") for o in output or []]
+    if read_report:
+        taken.append((read_report, "the --read_report file"))
+    for o, what in taken:
+        if os.path.abspath(path) == os.path.abspath(o):
+            raise RuntimeError("--summary {} is also {}".format(path, what))
+
+
 def build_parser():
     args = argparse.ArgumentParser(description='rRNA sequence detector', formatter_class=RawTextHelpFormatter)
     args.add_argument('-c', '--config', default=None, type=str, help='Path of config file')
@@ -1124,6 +1183,10 @@ none: give label based on the mean probability of read pair.
                            'unclassified (-e both), the output file the read went to; p_rrna = softmax of the final logits\n'
                            '(p_rrna_pair: of the summed logits of the mates, what decides -e none) as 0.dddd / 1.0000.\n'
                            'gzip-compressed when the name ends with gz.')
+    args.add_argument('--summary', default=None, type=str,
+                      help='(extension) write the run\'s QC counters to this file as JSON when the run has ended well: reads per label and\n'
+                           'the rRNA fraction; per mate and label the histograms of read length, GC content and p_rrna (of each mate and\n'
+                           'of the pair), the base composition; for pairs how often the mates agree. Counted on the GPU, chunk by chunk.')
     args.add_argument('--interleaved', action='store_true',
                       help='(extension) -i is ONE FASTQ file (plain or .gz) whose records alternate mate 1, mate 2: a paired-end run.\n'
                            '-o (and -r) take one path - interleaved output, the selected pairs in input order - or two: mate 1\'s\n'
