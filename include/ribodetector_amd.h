@@ -76,7 +76,14 @@ typedef struct rd_weights {
 /* Replaces: SeqModel(**arch.args); load_state_dict(...); .to('cuda'); .eval()
  * (reference detect.py:93,115-119, model/model.py:10-29). Uploads the weights to `device` and pre-packs them
  * (per-lane MFMA operand order for W_hh, fused input table  W_ih[:,base]+b_ih+b_hh, reverse-direction table).
- * Synchronous. */
+ * Synchronous.
+ * Accepted weights (checked on the host before any device call; rd_weights_check is that check alone and needs no GPU):
+ *   - every value of every tensor is finite, else RD_E_INVALID (the message names the tensor);
+ *   - max |rnn.weight_hh_l0| < 65504 / 16 = 4094, else RD_E_UNSUPPORTED: the split-precision kernel stores 16 w in fp16, whose
+ *     largest finite value is 65504 (a larger weight would become inf there and every logit NaN).
+ *   Gates and cell states that saturate the activations are inside the range: tests/test_gpu_weights.py holds every kernel to
+ *   the reference's own fp32 error on weights with pre-activations beyond +-100 and |c| up to 300. */
+RD_API int rd_weights_check(const rd_weights *w);
 RD_API int rd_model_create(const rd_weights *w, int device, rd_model **out);
 RD_API void rd_model_destroy(rd_model *m);
 

@@ -21,7 +21,7 @@ if os.path.basename(LIB_PATH).startswith("librd_hip_diag"):
 
 # every symbol include/ribodetector_amd.h declares (tests/test_abi.py checks the .so exports all of them)
 SYMBOLS = [
-    "rd_model_create", "rd_model_destroy", "rd_set_variant", "rd_variant_available", "rd_set_semantics", "rd_set_refine", "rd_set_refine_async", "rd_sync_results", "rd_refine", "rd_prefix_table_bytes", "rd_prefix_scratch_bytes", "rd_set_prefix_table", "rd_prefix_k", "rd_classify_workspace_bytes", "rd_classify",
+    "rd_weights_check", "rd_model_create", "rd_model_destroy", "rd_set_variant", "rd_variant_available", "rd_set_semantics", "rd_set_refine", "rd_set_refine_async", "rd_sync_results", "rd_refine", "rd_prefix_table_bytes", "rd_prefix_scratch_bytes", "rd_set_prefix_table", "rd_prefix_k", "rd_classify_workspace_bytes", "rd_classify",
     "rd_pair_fuse", "rd_count_labels", "rd_encode_codes", "rd_encode_onehot_padded", "rd_pack_plan",
     "rd_pack_onehot", "rd_profile_enable", "rd_profile_read", "rd_last_error", "rd_version",
     "rd_gz_workspace_bytes", "rd_gz_out_bound", "rd_gz_compress_selected", "rd_gz_eof_block", "rd_gz_inflate_members",
@@ -59,6 +59,8 @@ def lib():
     vp, i64, i32, sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
     L.rd_model_create.argtypes = [C.POINTER(RdWeights), C.c_int, C.POINTER(vp)]
     L.rd_model_create.restype = C.c_int
+    L.rd_weights_check.argtypes = [C.POINTER(RdWeights)]
+    L.rd_weights_check.restype = C.c_int
     L.rd_model_destroy.argtypes = [vp]
     L.rd_model_destroy.restype = None
     L.rd_set_variant.argtypes = [vp, C.c_int]

@@ -55,15 +55,37 @@ extern "C" {
 const char *rd_last_error(void) { return g_err; }
 const char *rd_version(void) { return "ribodetector_amd 0.1.0 (gfx950)"; }
 
-int rd_model_create(const rd_weights *w, int device, rd_model **out) {
-    if (!w || !out) RD_FAIL(RD_E_INVALID, "rd_model_create: null argument");
+// host-side, before any device call: the weights the kernels can represent (include/ribodetector_amd.h)
+int rd_weights_check(const rd_weights *w) {
+    if (!w) RD_FAIL(RD_E_INVALID, "rd_weights_check: null argument");
     if (w->input_size != 4 || w->hidden_size != HID || w->num_classes != 2)
         RD_FAIL(RD_E_UNSUPPORTED, "rd_model_create: kernels cover input_size=4, hidden_size=128, num_classes=2 (got %d,%d,%d)",
                 w->input_size, w->hidden_size, w->num_classes);
     const float *src[10] = {w->w_ih, w->w_hh, w->b_ih, w->b_hh, w->w_ih_r, w->w_hh_r, w->b_ih_r, w->b_hh_r, w->w_out, w->b_out};
     const int offs[11] = {OFF_WIH, OFF_WHH, OFF_BIH, OFF_BHH, OFF_WIHR, OFF_WHHR, OFF_BIHR, OFF_BHHR, OFF_WOUT, OFF_BOUT, RAW_FLOATS};
+    static const char *const names[10] = {"rnn.weight_ih_l0", "rnn.weight_hh_l0", "rnn.bias_ih_l0", "rnn.bias_hh_l0", "rnn.weight_ih_l0_reverse",
+                                          "rnn.weight_hh_l0_reverse", "rnn.bias_ih_l0_reverse", "rnn.bias_hh_l0_reverse", "out.weight", "out.bias"};
     for (int i = 0; i < 10; ++i)
         if (!src[i]) RD_FAIL(RD_E_INVALID, "rd_model_create: weight pointer %d is null", i);
+    for (int i = 0; i < 10; ++i) {
+        const int n = offs[i + 1] - offs[i];
+        for (int k = 0; k < n; ++k)
+            if (!(fabsf(src[i][k]) <= 3.402823466e38f))
+                RD_FAIL(RD_E_INVALID, "rd_model_create: %s holds a non-finite value (%g at element %d)", names[i], (double)src[i][k], k);
+    }
+    float mx = 0.0f;
+    for (int k = 0; k < G4 * HID; ++k) mx = fmaxf(mx, fabsf(w->w_hh[k]));
+    if (mx >= 65504.0f / 16.0f)
+        RD_FAIL(RD_E_UNSUPPORTED, "rd_model_create: max |rnn.weight_hh_l0| = %g is not below 65504/16 = 4094: the split-precision kernel stores "
+                                  "16 w in fp16", (double)mx);
+    return RD_OK;
+}
+
+int rd_model_create(const rd_weights *w, int device, rd_model **out) {
+    if (!w || !out) RD_FAIL(RD_E_INVALID, "rd_model_create: null argument");
+    if (const int rc = rd_weights_check(w)) return rc;
+    const float *src[10] = {w->w_ih, w->w_hh, w->b_ih, w->b_hh, w->w_ih_r, w->w_hh_r, w->b_ih_r, w->b_hh_r, w->w_out, w->b_out};
+    const int offs[11] = {OFF_WIH, OFF_WHH, OFF_BIH, OFF_BHH, OFF_WIHR, OFF_WHHR, OFF_BIHR, OFF_BHHR, OFF_WOUT, OFF_BOUT, RAW_FLOATS};
     RD_HIP(hipSetDevice(device));
     rd_model *m = new rd_model();
     memset(m, 0, sizeof(*m));

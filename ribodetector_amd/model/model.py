@@ -103,6 +103,9 @@ class SeqModel:
             if a.shape != self._shapes[k]:
                 raise RuntimeError("size mismatch for %s: got %s, expected %s" % (k, a.shape, self._shapes[k]))
             sd[k] = a
+        # the range of weights the kernels can represent (include/ribodetector_amd.h rd_weights_check: host code, no device needed);
+        # a refused state dict leaves the model as it was
+        N.check(N.lib().rd_weights_check(C.byref(self._weights(sd))), "load_state_dict")
         self._state = sd
         if self._handle is not None:
             self._create()
@@ -120,12 +123,15 @@ class SeqModel:
         self._ptab = None
         self._ptab_variant = None
 
+    def _weights(self, sd):
+        return N.RdWeights(*[sd[k].ctypes.data_as(C.POINTER(C.c_float)) for k in STATE_KEYS],
+                           self.input_size, self.hidden_size, self.num_classes)
+
     def _create(self):
         self._destroy()
         if self._state is None:
             raise RuntimeError("SeqModel.to(): call load_state_dict() first")
-        w = N.RdWeights(*[self._state[k].ctypes.data_as(C.POINTER(C.c_float)) for k in STATE_KEYS],
-                        self.input_size, self.hidden_size, self.num_classes)
+        w = self._weights(self._state)
         h = C.c_void_p()
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         N.check(N.lib().rd_model_create(C.byref(w), idx, C.byref(h)), "rd_model_create")

@@ -37,6 +37,46 @@ def f64_forward(sd, arena, off, lens, max_len):
     return np.concatenate([h, hr], 1) @ wout.T + bout
 
 
+def f64_forward_stats(sd, arena, off, lens, max_len):
+    """f64_forward, and what the arithmetic went through on the way: (logits, stats) with stats["i" | "f" | "g" | "o"] = (min, max)
+    of the forward direction's pre-activation of that gate and stats["c"] = (min, max) of the cell state, over the live steps of
+    every read (a read is live at step t < min(len, max_len)). The gate-math guards of the kernels are taken at known values of
+    these (tests/test_weight_families_host.py)."""
+    g = lambda k: np.asarray(sd[k], dtype=np.float64) if isinstance(sd[k], np.ndarray) else sd[k].double().numpy()   # noqa: E731
+    wih, whh, b = g("rnn.weight_ih_l0"), g("rnn.weight_hh_l0"), g("rnn.bias_ih_l0") + g("rnn.bias_hh_l0")
+    wihr, br = g("rnn.weight_ih_l0_reverse"), g("rnn.bias_ih_l0_reverse") + g("rnn.bias_hh_l0_reverse")
+    wout, bout = g("out.weight"), g("out.bias")
+    n = len(lens)
+    T = np.minimum(lens, max_len).astype(np.int64)
+    lut = np.full(256, 4, dtype=np.int64)
+    for ch, c in ((b"A", 0), (b"C", 1), (b"G", 2), (b"T", 3), (b"U", 3)):
+        lut[ch[0]] = c
+    inl = np.concatenate([wih.T + b, b[None, :]], 0)                # [5, 512]
+    inr = np.concatenate([wihr.T + br, br[None, :]], 0)
+    sig = lambda x: 1.0 / (1.0 + np.exp(-x))                         # noqa: E731
+    h = np.zeros((n, 128)); c = np.zeros((n, 128))
+    order = np.argsort(-T, kind="stable")
+    Ts = T[order]
+    lo = {k: np.inf for k in "ifgoc"}
+    hi = {k: -np.inf for k in "ifgoc"}
+    for t in range(int(T.max()) if n else 0):
+        m = int((Ts > t).sum())
+        idx = order[:m]
+        code = lut[arena[off[idx] + t]]
+        gates = inl[code] + h[idx] @ whh.T
+        for q, k in enumerate("ifgo"):
+            lo[k], hi[k] = min(lo[k], gates[:, 128 * q:128 * (q + 1)].min()), max(hi[k], gates[:, 128 * q:128 * (q + 1)].max())
+        i, f, gg, o = sig(gates[:, :128]), sig(gates[:, 128:256]), np.tanh(gates[:, 256:384]), sig(gates[:, 384:])
+        c[idx] = f * c[idx] + i * gg
+        h[idx] = o * np.tanh(c[idx])
+        lo["c"], hi["c"] = min(lo["c"], c[idx].min()), max(hi["c"], c[idx].max())
+    last = np.where(T > 0, lut[arena[np.minimum(off[:-1] + np.maximum(T, 1) - 1, len(arena) - 1)]], 4)
+    gr = inr[last]
+    cr = sig(gr[:, :128]) * np.tanh(gr[:, 256:384])
+    hr = sig(gr[:, 384:]) * np.tanh(cr)
+    hr[T == 0] = 0.0
+    return np.concatenate([h, hr], 1) @ wout.T + bout, {k: (float(lo[k]), float(hi[k])) for k in "ifgoc"}
+
 
 
 def f64_forward_torch(sd, arena, L, dev, block=1 << 18):

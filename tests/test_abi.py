@@ -76,6 +76,61 @@ def test_argument_errors_without_gpu():
     assert rc == -1
 
 
+def _weights(N, sd):
+    import ctypes as C
+    from ribodetector_amd.model.model import STATE_KEYS
+    return N.RdWeights(*[sd[k].ctypes.data_as(C.POINTER(C.c_float)) for k in STATE_KEYS], 4, 128, 2)
+
+
+def test_weights_outside_the_accepted_range_are_refused_without_gpu():
+    """rd_model_create checks the weights on the host before its first device call (include/ribodetector_amd.h): a non-finite value
+    is RD_E_INVALID and the message names the tensor; max |weight_hh_l0| >= 65504/16 is RD_E_UNSUPPORTED (16 w is stored in fp16:
+    such weights used to give inf there and silent NaN logits). SeqModel.load_state_dict raises RuntimeError and keeps its state."""
+    import ctypes as C
+    import sys
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import weight_families as WF
+    from ribodetector_amd import _native as N
+    from ribodetector_amd.model import model as M
+    L = N.lib()
+    good = WF.family("random_wide")
+    assert L.rd_weights_check(C.byref(_weights(N, good))) == 0
+    assert L.rd_weights_check(None) == -1
+    m = M.SeqModel(4, 128, 1, 2)
+    m.load_state_dict(good)
+
+    def refused(sd, rc, *words):
+        h = C.c_void_p()
+        assert L.rd_model_create(C.byref(_weights(N, sd)), 0, C.byref(h)) == rc and not h.value
+        msg = L.rd_last_error().decode()
+        assert all(w in msg for w in words), msg
+        assert L.rd_weights_check(C.byref(_weights(N, sd))) == rc
+        with pytest.raises(RuntimeError, match=words[0]):
+            m.load_state_dict(sd)
+        assert all(np.array_equal(m._state[k], good[k]) for k in good)
+
+    for key, at in (("rnn.weight_ih_l0", (511, 3)), ("rnn.weight_hh_l0", (0, 0)), ("rnn.bias_hh_l0", (17,)), ("rnn.weight_hh_l0_reverse", (300, 127)),
+                    ("rnn.bias_ih_l0_reverse", (511,)), ("out.weight", (1, 255)), ("out.bias", (1,))):
+        for bad in (np.nan, np.inf, -np.inf):
+            sd = {k: v.copy() for k, v in good.items()}
+            sd[key][at] = bad
+            refused(sd, -1, key + " holds a non-finite value")
+    limit = np.float32(65504.0 / 16.0)
+    for w, ok in ((limit, False), (-limit, False), (np.float32(1e6), False), (np.nextafter(limit, np.float32(0)), True)):
+        sd = {k: v.copy() for k, v in good.items()}
+        sd["rnn.weight_hh_l0"][511, 127] = w
+        if ok:
+            assert L.rd_weights_check(C.byref(_weights(N, sd))) == 0
+        else:
+            refused(sd, -3, "weight_hh_l0", "16 w in fp16")
+    # large values elsewhere are inside the range: only W_hh goes through fp16
+    sd = {k: v.copy() for k, v in good.items()}
+    sd["rnn.weight_hh_l0_reverse"][0, 0] = 1e6
+    sd["rnn.bias_ih_l0"][5] = -1e6
+    assert L.rd_weights_check(C.byref(_weights(N, sd))) == 0
+
+
 def test_product_build_has_no_diagnostic_variants():
     """librd_hip.so contains the three kernels that compute the function and nothing else: the A/B and diagnostic
     instantiations (ids >= 10, several wrong by design) and the removed id 3 / 5 must be refused (VERDICT r1 weak #9)."""
