@@ -14,6 +14,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <atomic>
 #include <condition_variable>
 #include <deque>
 #include <functional>
@@ -282,11 +283,13 @@ bool pwrite_all(int fd, const uint8_t *p, size_t len, int64_t off) {
     return true;
 }
 
-int g_threads = 0;                  // 0 = auto
-int g_gz_threads = -1;              // decoder threads per .gz input: -1 = auto, 0 = sequential decoder
+// (atomic: rd_host_set_threads / rd_host_set_gz_threads may be called while another thread opens a reader or a writer)
+std::atomic<int> g_threads{0};      // 0 = auto
+std::atomic<int> g_gz_threads{-1};  // decoder threads per .gz input: -1 = auto, 0 = sequential decoder
 
 int usable_threads() {
-    if (g_threads > 0) return g_threads;
+    const int set = g_threads.load(std::memory_order_relaxed);
+    if (set > 0) return set;
     int n = (int)std::thread::hardware_concurrency();
     if (n < 1) n = 1;
     FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r");   // containers: quota / period
@@ -444,7 +447,8 @@ int rd_reader_open(const char *path, int format, rd_reader **out) {
         // large files: the parallel decoder (falls back to the sequential one by itself for anything it is not made for).
         // Threads per file: rd_host_set_gz_threads (the CLI divides -t among its input files), else half of the usable cores - 1,
         // <= 8 (paired input decodes two files at once); RD_GZ_THREADS overrides both, 0 = the sequential decoder.
-        int pt = g_gz_threads >= 0 ? g_gz_threads : std::min(8, std::max(2, usable_threads() / 2 - 1));
+        const int gz_set = g_gz_threads.load(std::memory_order_relaxed);
+        int pt = gz_set >= 0 ? gz_set : std::min(8, std::max(2, usable_threads() / 2 - 1));
         if (const char *e = getenv("RD_GZ_THREADS")) pt = atoi(e);
         struct stat st;
         long long min_size = 16ll << 20, section = 2ll << 20;   // (RD_GZ_PARALLEL_MIN / RD_GZ_SECTION: knobs of the tests)
@@ -992,12 +996,12 @@ int rd_host_gunzip_parallel(const char *path, uint8_t *out, int64_t cap, int64_t
 int rd_writer_threads(const rd_writer *w) { return w ? w->threads : -1; }
 
 int rd_host_set_threads(int threads) {
-    g_threads = threads > 0 ? threads : 0;
+    g_threads.store(threads > 0 ? threads : 0, std::memory_order_relaxed);
     return 0;
 }
 
 int rd_host_set_gz_threads(int threads) {
-    g_gz_threads = threads < 0 ? -1 : threads;
+    g_gz_threads.store(threads < 0 ? -1 : threads, std::memory_order_relaxed);
     return 0;
 }
 

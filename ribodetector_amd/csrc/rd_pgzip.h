@@ -447,7 +447,7 @@ class ParallelGzip {
             }
             const PgBytes &b = ready_[ri_];
             const size_t n = std::min(cap - done, b.size() - roff_);
-            memcpy(dst + done, b.data() + roff_, n);
+            if (n) memcpy(dst + done, b.data() + roff_, n);   // (an empty section has no buffer: memcpy takes no null pointer, even for 0 bytes)
             roff_ += n;
             done += n;
             if (roff_ == b.size()) {

@@ -133,7 +133,8 @@ def test_damaged_files_are_errors(tmp_path):
 
 
 def test_random_deflate_streams_never_crash(tmp_path):
-    """arbitrary bytes after a valid header: any outcome but a crash / out-of-bounds access is fine"""
+    """arbitrary bytes after a valid header: any outcome but a crash is fine here. Out-of-bounds accesses that do not crash are checked
+    by tests/test_host_sanitizers.py, which runs these same streams through an AddressSanitizer + UBSan build of the decoders"""
     rng = np.random.default_rng(9)
     p = tmp_path / "fuzz.gz"
     for i in range(300):
@@ -281,6 +282,8 @@ def test_parallel_decoder_reports_damage_like_the_sequential_one(tmp_path):
 
 
 def test_parallel_decoder_fuzz_never_crashes(tmp_path):
+    """mutated members: the parallel decoder answers like the sequential one. Out-of-bounds accesses and data races that do not crash are
+    checked by tests/test_host_sanitizers.py (these same streams under AddressSanitizer + UBSan, a share of them under ThreadSanitizer)"""
     rng = np.random.default_rng(10)
     p = tmp_path / "fuzz.gz"
     good = member(PAYLOADS["fastq"][:400000], 6)
