@@ -29,6 +29,7 @@ import torch
 
 from .. import _native as N
 from .. import gz
+from .member_batches import TRUNCATED, Tail, member_batches, pread_exactly, skip_zero_padding, zlib_member_texts
 
 PAD = 16 << 20                 # bytes in front of a batch's new text: room for the carry (= the longest record the device path frames)
 LINE_DIV = 4                   # the line table of a batch holds window / LINE_DIV lines (a FASTQ line of reads is >= 4 bytes; a batch of
@@ -612,13 +613,7 @@ class DeviceFeeder:
                 tm["members"] += 1
                 if end is None or end >= size:
                     return
-                # zero padding behind a member is skipped (Python's gzip module does); what follows must be another member
-                while end < size:
-                    rest = os.pread(fd, 1 << 16, end)
-                    k = len(rest) - len(rest.lstrip(b"\0"))
-                    end += k
-                    if k < len(rest):
-                        break
+                end = skip_zero_padding(fd, end, size)      # (what follows the padding must be another member)
                 if end >= size:
                     return
                 base = end
@@ -630,7 +625,7 @@ class DeviceFeeder:
         size = os.fstat(fd).st_size
         hl = gz.gzip_header_len(os.pread(fd, 1 << 16, base))
         if hl is None:
-            raise ValueError("Compressed file ended before the end-of-stream marker was reached")
+            raise ValueError(TRUNCATED)
         pos, first, batch = base, hl * 8, min(int(os.environ.get("RD_GZS_FIRST", self.STREAM_FIRST or (self.FIRST if self.FIRST != DeviceFeeder.FIRST_DEFAULT else dsg.BATCH))) if base == 0 else dsg.BATCH, dsg.BATCH)
         flight = deque()                                  # (ticket, text, pinned slot, file offset of the batch)
         member_end = None
@@ -663,7 +658,7 @@ class DeviceFeeder:
                 end = at + (r["end_bit"] + 7) // 8
                 tr = os.pread(fd, 8, end)
                 if len(tr) < 8:
-                    raise ValueError("Compressed file ended before the end-of-stream marker was reached")
+                    raise ValueError(TRUNCATED)
                 if int.from_bytes(tr[:4], "little") != r["crc"]:
                     raise ValueError("CRC check failed")
                 if int.from_bytes(tr[4:], "little") != (r["total_len"] & 0xffffffff):
@@ -692,12 +687,7 @@ class DeviceFeeder:
                 break
             slot = free.pop()
             t1 = time.perf_counter()
-            have = 0
-            while have < valid:
-                k = os.preadv(fd, [memoryview(views[slot])[have:valid]], pos + have)
-                if k <= 0:
-                    raise ValueError("Compressed file ended before the end-of-stream marker was reached")
-                have += k
+            pread_exactly(fd, views[slot], valid, pos)
             t2 = time.perf_counter()
             text = self.ix.alloc_text(dsg.text_cap(data))
             if dsg.stream is not self.ix.stream:          # (the buffer comes from the indexer's stream's pool: whatever last used it there is over first)
@@ -719,7 +709,7 @@ class DeviceFeeder:
                 return None
         if member_end is None:
             if not self._stop:
-                raise ValueError("Compressed file ended before the end-of-stream marker was reached")
+                raise ValueError(TRUNCATED)
             return None
         return member_end
 
@@ -738,7 +728,7 @@ class DeviceFeeder:
             if len(raw) == 0 or self._stop:
                 if self._stop:
                     return None
-                raise ValueError("Compressed file ended before the end-of-stream marker was reached")
+                raise ValueError(TRUNCATED)
             arr = np.frombuffer(raw, dtype=np.uint8)
             n = len(arr) - 1 if len(arr) == PIECE + 1 else len(arr)
             if k:
@@ -780,115 +770,37 @@ class DeviceFeeder:
     def _host_tail(self, fh, data):
         """the rest of a file whose members stop carrying their size (`cat a.bgzf.gz b.gz` is a legal .gz): zlib, member after member,
         the text shipped to the device in pieces and framed behind the batches in flight"""
-        import zlib
-        d, inside = zlib.decompressobj(31), False
-        while not self._stop:
-            if not data:
-                data = fh.read(4 << 20)
-                if not data:
-                    if inside:
-                        raise ValueError("Compressed file ended before the end-of-stream marker was reached")
-                    return
-            if not inside and not data.strip(b"\0"):       # zero padding behind the last member (Python's gzip module skips it too)
-                data = b""
-                continue
-            try:
-                out = d.decompress(data, 16 << 20)          # (at most 16 MB of text per call)
-            except zlib.error as e:
-                raise ValueError(str(e))
-            inside = True
-            if out:
-                src = torch.from_numpy(np.frombuffer(out, dtype=np.uint8).copy()).pin_memory()
-                b = self._submit_text(src, len(out), None)
-                b.orig = src                                  # (keeps the pinned bytes alive until the batch is consumed)
-                if not self._put(b):
-                    return
-            if d.eof:
-                data, d, inside = d.unused_data, zlib.decompressobj(31), False
-            else:
-                data = d.unconsumed_tail
+        for out in zlib_member_texts(fh, data, lambda: self._stop):
+            src = torch.from_numpy(np.frombuffer(out, dtype=np.uint8).copy()).pin_memory()
+            b = self._submit_text(src, len(out), None)
+            b.orig = src                                  # (keeps the pinned bytes alive until the batch is consumed)
+            if not self._put(b):
+                return
+
+    def _acquire_slot(self):
+        slot = self.slot_free.get()                       # (its previous batch has left the GPU: next_batch() finished it)
+        return None if self._stop else slot
 
     def _run_bgzf(self):
         tm = self.stage_s
         dg = self.dg
         pinned = [torch.empty(self.BATCH + (1 << 20), dtype=torch.uint8, pin_memory=True) for _ in range(self.SLOTS)]
         bufs = [t.numpy() for t in pinned]
-        carry = None                                    # bytes of an incomplete member, to go in front of the next batch
-        batch = min(self.FIRST, self.BATCH)
         with open(self.path, "rb", buffering=0) as fh:
-            eof = False
-            file_left = text_left = None
-            skip_text = 0
-            if self.span is not None:           # a share of the file: whole members [c0, c1), text trimmed at both ends
-                fh.seek(self.span[0])
-                file_left, skip_text, text_left = self.span[1] - self.span[0], self.span[2], self.span[3]
-                eof = file_left <= 0
-            while not self._stop:
-                t0 = time.perf_counter()
-                slot = self.slot_free.get()                  # (its previous batch has left the GPU: next_batch() finished it)
-                if self._stop:
+            for ev in member_batches(fh, lambda buf, have, slot: dg.index(buf, have, slot=slot, max_members=self.MAX_MEMBERS), self._acquire_slot,
+                                     self.slot_free.put, bufs, self.FIRST, self.BATCH, span=self.span, stopped=lambda: self._stop, tm=tm):
+                if isinstance(ev, Tail):
+                    self._host_tail(fh, ev.data)
                     break
-                t1 = time.perf_counter()
-                buf, have = bufs[slot], 0
-                if carry is not None:
-                    have = len(carry)
-                    buf[:have] = carry
-                    carry = None
-                while have < batch and not eof:
-                    cap = batch + (1 << 20) if file_left is None else min(batch + (1 << 20), have + file_left)
-                    k = fh.readinto(memoryview(buf)[have:cap])
-                    if not k:
-                        eof = True
-                    else:
-                        have += k
-                        if file_left is not None:
-                            file_left -= k
-                            eof = file_left <= 0
-                if have == 0:
-                    self.slot_free.put(slot)
-                    break
-                t2 = time.perf_counter()
-                n, consumed, out_bytes, streaming = dg.index(buf, have, slot=slot, max_members=self.MAX_MEMBERS)
                 t3 = time.perf_counter()
-                tm["wait_slot"] += t1 - t0
-                tm["read"] += t2 - t1
-                tm["index"] += t3 - t2
-                if streaming and n == 0:
-                    self.slot_free.put(slot)
-                    self._host_tail(fh, bytes(buf[consumed:have]))
-                    break
-                if n == 0 or consumed == 0:
-                    if eof:
-                        if consumed < have:
-                            raise ValueError("Compressed file ended before the end-of-stream marker was reached")
-                        self.slot_free.put(slot)
-                        break
-                    if consumed == 0 and have >= self.BATCH:       # a member that claims to be larger than the batch buffer: no progress possible
-                        raise ValueError("gzip member larger than %d bytes: not a BGZF file (RD_DEVICE_INFLATE=0 reads it with the host's "
-                                         "decoders)" % self.BATCH)
-                if consumed < have:
-                    carry = buf[consumed:have].copy()
-                if n:
-                    text = self.ix.alloc_text(out_bytes)
-                    dg.submit(buf, consumed, n, out_bytes, slot=slot, text_out=text[PAD:PAD + out_bytes])
-                    drop = min(skip_text, out_bytes)
-                    skip_text -= drop
-                    end = PAD + out_bytes
-                    if text_left is not None:
-                        take = min(out_bytes - drop, text_left)
-                        text_left -= take
-                        end = PAD + drop + take
-                    b = self.ix.index(text, PAD + drop, end)
-                    b.slot, b.gz_slot = slot, slot
-                    tm["submit"] += time.perf_counter() - t3
-                    tm["batches"] += 1
-                    tm["bytes"] += out_bytes
-                    if not self._put(b):
-                        break
-                else:
-                    self.slot_free.put(slot)
-                batch = min(2 * batch, self.BATCH)
-                if text_left is not None and text_left <= 0:
+                text = self.ix.alloc_text(ev.out_bytes)
+                dg.submit(bufs[ev.slot], ev.nbytes, ev.n, ev.out_bytes, slot=ev.slot, text_out=text[PAD:PAD + ev.out_bytes])
+                b = self.ix.index(text, PAD + ev.drop, PAD + ev.drop + ev.take)
+                b.slot, b.gz_slot = ev.slot, ev.slot
+                tm["submit"] += time.perf_counter() - t3
+                tm["batches"] += 1
+                tm["bytes"] += ev.out_bytes
+                if not self._put(b):
                     break
 
 

@@ -19,6 +19,7 @@ from pathlib import Path
 import numpy as np
 
 from .. import _native as N
+from .member_batches import TRUNCATED, Tail, error_bytes, member_batches, zlib_member_texts
 
 FA_EXTS = [".fasta", ".fa", ".fna", ".fas"]
 FQ_EXTS = [".fq", ".fastq"]
@@ -389,29 +390,6 @@ class _DeviceInflateFeeder:
     def join(self):
         self.th.join()
 
-    def _host_tail(self, fh, data, full):
-        """the rest of a file whose members stop carrying their size: zlib, member after member, text queued behind the GPU batches"""
-        import zlib
-        d, inside = zlib.decompressobj(31), False
-        while not self._stop:
-            if not data:
-                data = fh.read(4 << 20)
-                if not data:
-                    if inside:
-                        raise ValueError("Compressed file ended before the end-of-stream marker was reached")
-                    return
-            try:
-                out = d.decompress(data, 16 << 20)          # (at most 16 MB of text per call)
-            except zlib.error as e:
-                raise ValueError(str(e))
-            inside = True
-            if out:
-                full.put((None, np.frombuffer(out, dtype=np.uint8), len(out)))
-            if d.eof:
-                data, d, inside = d.unused_data, zlib.decompressobj(31), False
-            else:
-                data = d.unconsumed_tail
-
     def _run(self):
         """Two threads per file. This one reads the file, walks the member headers and QUEUES the batch on the GPU (H2D of the members,
         one wave per member, D2H of the text into a pinned buffer: gz.DeviceGunzip.submit) - without waiting for it: the recurrence
@@ -441,8 +419,7 @@ class _DeviceInflateFeeder:
                 item = full.get()
                 if item is None:
                     break
-                slot, i, nbytes = item[:3]
-                skip = item[3] if len(item) > 3 else 0
+                slot, i, nbytes, skip = item
                 if slot is None:                    # text inflated on the host (the tail of a mixed file): i is a numpy array
                     if not state["closed"] and L.rd_reader_feed(self.h, i.ctypes.data, nbytes) != 0:
                         state["closed"] = True
@@ -453,7 +430,7 @@ class _DeviceInflateFeeder:
                     dg.finish(slot)
                 except BaseException as e:      # a damaged member: the records of the batches before it are delivered, then the error
                     if not state["err"]:
-                        state["err"] = (str(e) or repr(e)).encode()[:400]
+                        state["err"] = error_bytes(e)
                     state["closed"] = True
                     self._stop = True
                 slot_free.put(slot)
@@ -472,85 +449,27 @@ class _DeviceInflateFeeder:
             ft.start()
             pinned = [torch.empty(self.BATCH + (1 << 20), dtype=torch.uint8, pin_memory=True) for _ in range(SLOTS)]
             bufs = [t.numpy() for t in pinned]
-            carry = None                                    # bytes of an incomplete member, to go in front of the next batch
-            batch = min(self.FIRST, self.BATCH)
             with open(self.path, "rb", buffering=0) as fh:
-                eof = False
-                file_left = skip_text = text_left = None
-                if self.span is not None:           # a share of the file: whole members [c0, c1), text trimmed at both ends
-                    fh.seek(self.span[0])
-                    file_left, skip_text, text_left = self.span[1] - self.span[0], self.span[2], self.span[3]
-                    eof = file_left <= 0
-                while not self._stop:
-                    t0 = time.perf_counter()
-                    slot = slot_free.get()                  # (its previous batch has left the GPU: finish() returned)
-                    t1 = time.perf_counter()
-                    buf, have = bufs[slot], 0
-                    if carry is not None:
-                        have = len(carry)
-                        buf[:have] = carry
-                        carry = None
-                    while have < batch and not eof:
-                        cap = batch + (1 << 20) if file_left is None else min(batch + (1 << 20), have + file_left)
-                        k = fh.readinto(memoryview(buf)[have:cap])
-                        if not k:
-                            eof = True
-                        else:
-                            have += k
-                            if file_left is not None:
-                                file_left -= k
-                                eof = file_left <= 0
-                    if have == 0:
-                        slot_free.put(slot)
+                for ev in member_batches(fh, lambda buf, have, slot: dg.index(buf, have, slot=slot), slot_free.get, slot_free.put, bufs,
+                                         self.FIRST, self.BATCH, span=self.span, stopped=lambda: self._stop, tm=tm):
+                    if isinstance(ev, Tail):        # text inflated on the host, fed behind the batches in flight
+                        for out in zlib_member_texts(fh, ev.data, lambda: self._stop):
+                            full.put((None, np.frombuffer(out, dtype=np.uint8), len(out), 0))
                         break
-                    t2 = time.perf_counter()
-                    n, consumed, out_bytes, streaming = dg.index(buf, have, slot=slot)
                     t3 = time.perf_counter()
-                    tm["wait_slot"] += t1 - t0
-                    tm["read"] += t2 - t1
-                    tm["index"] += t3 - t2
-                    if streaming and n == 0:
-                        # a member without a size subfield behind the BGZF blocks (`cat a.bgzf.gz b.gz` is a legal .gz): the rest of the
-                        # file is inflated here, on the host, one zlib stream after the other, and fed behind the batches in flight
-                        slot_free.put(slot)
-                        self._host_tail(fh, bytes(buf[consumed:have]), full)
-                        break
-                    if (n == 0 or consumed == 0) and eof:
-                        if consumed < have:
-                            raise ValueError("Compressed file ended before the end-of-stream marker was reached")
-                        slot_free.put(slot)
-                        break
-                    if consumed == 0 and have >= self.BATCH:      # (nothing more can be read into the buffer: the loop would spin)
-                        raise ValueError("gzip member larger than %d bytes: not a BGZF file (RD_DEVICE_INFLATE=0 reads it with the host's "
-                                         "decoders)" % self.BATCH)
-                    if consumed < have:
-                        carry = buf[consumed:have].copy()
-                    if n:
-                        i = free.get()
-                        t4 = time.perf_counter()
-                        if texts[i] is None or texts[i].numel() < out_bytes:
-                            texts[i] = None
-                            texts[i] = torch.empty(int(out_bytes * 1.25) + 4096, dtype=torch.uint8, pin_memory=True)
-                        dg.submit(buf, consumed, n, out_bytes, slot=slot, host_text=texts[i])
-                        if text_left is None:
-                            full.put((slot, i, out_bytes))
-                        else:
-                            drop = min(skip_text, out_bytes)
-                            take = min(out_bytes - drop, text_left)
-                            skip_text -= drop
-                            text_left -= take
-                            full.put((slot, i, take, drop))
-                        tm["wait_buffer"] += t4 - t3
-                        tm["submit"] += time.perf_counter() - t4
-                        tm["batches"] += 1
-                    else:
-                        slot_free.put(slot)
-                    batch = min(2 * batch, self.BATCH)
-                    if text_left is not None and text_left <= 0:
-                        break
+                    i = free.get()
+                    t4 = time.perf_counter()
+                    if texts[i] is None or texts[i].numel() < ev.out_bytes:
+                        texts[i] = None
+                        texts[i] = torch.empty(int(ev.out_bytes * 1.25) + 4096, dtype=torch.uint8, pin_memory=True)
+                    dg.submit(bufs[ev.slot], ev.nbytes, ev.n, ev.out_bytes, slot=ev.slot, host_text=texts[i])
+                    full.put((ev.slot, i, ev.take, ev.drop))
+                    tm["wait_buffer"] += t4 - t3
+                    tm["submit"] += time.perf_counter() - t4
+                    tm["batches"] += 1
         except BaseException as e:      # reported by rd_reader_next on the consumer's thread, after the records before the damage
             if not state["err"]:
-                state["err"] = (str(e) or repr(e)).encode()[:400]
+                state["err"] = error_bytes(e)
         full.put(None)
         if ft.ident is not None:
             ft.join()
@@ -758,7 +677,7 @@ class BgzfView:
                 raise ValueError(L.rd_host_last_error().decode())
             if rc == 1 and n.value == 0 or consumed.value == 0:
                 raise ValueError("%s: a gzip member without a size subfield at byte %d" % (path, pos + consumed.value) if rc == 1 else
-                                 "Compressed file ended before the end-of-stream marker was reached")
+                                 TRUNCATED)
             e = ent[: n.value]
             il = (e[:, 2] & 0xffffffff).astype(np.int64)
             ol = (e[:, 2] >> 32).astype(np.int64)

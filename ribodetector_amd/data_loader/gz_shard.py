@@ -33,6 +33,7 @@ import torch
 from .. import _native as N
 from .. import gz
 from . import device_reader as dr
+from .member_batches import TRUNCATED, pread_exactly, skip_zero_padding
 
 WIN = 32768
 MIN_RANGE = 1 << 20            # compressed bytes per rank below which a file is not worth sharing (RD_GZ_SHARD_MIN)
@@ -155,7 +156,7 @@ class _Phase1:
                 end = at + (r["end_bit"] + 7) // 8
                 tr = os.pread(fd, 8, end)
                 if len(tr) < 8:
-                    m["status"], m["why"] = -3, "Compressed file ended before the end-of-stream marker was reached"
+                    m["status"], m["why"] = -3, TRUNCATED
                     return
                 seg["final"], seg["trailer"] = True, tr
                 member_end = end + 8
@@ -168,20 +169,14 @@ class _Phase1:
                     while flight:
                         finish_one()
                     self.segs.append(seg)
-                    e = member_end
-                    while e < self.size:                 # zero padding between members is skipped (Python's gzip module does)
-                        rest = os.pread(fd, 1 << 16, e)
-                        k = len(rest) - len(rest.lstrip(b"\0"))
-                        e += k
-                        if k < len(rest):
-                            break
+                    e = skip_zero_padding(fd, member_end, self.size)
                     seg = None
                     if e >= self.size:
                         m["ended"] = True
                         break
                     hl = gz.gzip_header_len(os.pread(fd, 1 << 16, e))      # (ValueError: not a gzip member - the host path reports it)
                     if hl is None:
-                        raise ValueError("Compressed file ended before the end-of-stream marker was reached")
+                        raise ValueError(TRUNCATED)
                     m["fresh_after"] = True
                     if e >= self.hi:                     # the next member starts in the next rank's share: exactly there, or the ranks disagree
                         m["next_abs"] = (e + hl) * 8
@@ -209,12 +204,7 @@ class _Phase1:
                 if m["status"] or member_end is not None:
                     continue
                 slot = free.pop()
-                have = 0
-                while have < valid:
-                    k = os.preadv(fd, [memoryview(views[slot])[have:valid]], pos + have)
-                    if k <= 0:
-                        raise ValueError("Compressed file ended before the end-of-stream marker was reached")
-                    have += k
+                pread_exactly(fd, views[slot], valid, pos)
                 tk = dg.submit(pinned[slot], valid, data, first, at_eof)
                 flight.append((tk, slot, pos))
                 pos += data
@@ -263,7 +253,7 @@ def _verdict_x1(metas, world, sizes):
                 if m["next_abs"] != metas[r + 1][f]["first_abs"]:
                     return "the share of rank %d does not start where rank %d says the stream goes on" % (r + 1, r)
             elif not m["ended"]:
-                return "Compressed file ended before the end-of-stream marker was reached"
+                return TRUNCATED
     return None
 
 
@@ -331,7 +321,7 @@ def prepare(paths, rank, world, device, fasta, all_gather, shift_to_prev, log=No
             with open(path, "rb") as fh:
                 hl = gz.gzip_header_len(fh.read(1 << 16))
             if hl is None:
-                raise ValueError("Compressed file ended before the end-of-stream marker was reached")
+                raise ValueError(TRUNCATED)
             first = hl * 8
         ph.append(_Phase1(path, b[rank], b[rank + 1], sizes[f], first, device, streams[f]))
 
@@ -427,7 +417,7 @@ def prepare(paths, rank, world, device, fasta, all_gather, shift_to_prev, log=No
                         return give_up("Incorrect length of data produced")
                     crc, total = 0, 0
         if total:
-            return give_up("Compressed file ended before the end-of-stream marker was reached")
+            return give_up(TRUNCATED)
     # ---- P3: framing; the head of the next rank closes this rank's last record ----------------------------------------------------------------
     ranges, counts = [], []
     for f, path in enumerate(paths):

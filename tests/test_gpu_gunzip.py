@@ -217,21 +217,78 @@ def test_reader_with_device_inflate_equals_the_host_reader(tmp_path, fmt, monkey
         read_all()
 
 
+EOF_BLOCK = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def _host_records(chunks):
+    """(record text, sequence lengths, offset of every sequence in its record) of fastx_parser chunks, concatenated"""
+    cs = [(c.buf[c.rec_start[0]:c.rec_start[-1]].tobytes(), np.asarray(c.seq_len), np.asarray(c.seq_off) - np.asarray(c.rec_start)[:-1]) for c in chunks]
+    return b"".join(c[0] for c in cs), np.concatenate([c[1] for c in cs]), np.concatenate([c[2] for c in cs])
+
+
+def _device_records(chunks):
+    cs = []
+    for c in chunks:
+        text, rs, so, sl = c.to_host()
+        cs.append((text.tobytes(), np.asarray(sl), np.asarray(so) - np.asarray(rs)[:-1]))
+    return b"".join(c[0] for c in cs), np.concatenate([c[1] for c in cs]), np.concatenate([c[2] for c in cs])
+
+
+@pytest.mark.parametrize("fmt", ["fq", "fa"])
+def test_rank_shares_of_a_bgzf_file_through_both_feeders(tmp_path, fmt, monkeypatch):
+    """a BgzfRange share (plan_ranges over a BgzfView, world 3) read by the host-parse feeder and by the device feeder, in batches
+    that start at 50 bytes: the ranks' records concatenated are the host reader's records of the whole file, on both routes"""
+    from ribodetector_amd import synth
+    from ribodetector_amd.data_loader import device_reader as dr
+    from ribodetector_amd.data_loader import fastx_parser as fx
+    arena, off, lens = synth.reads_numpy(3000, (40, 150), seed=9)
+    seqs = synth.as_strings(arena, off)
+    if fmt == "fq":
+        text = "".join("@read%d some text\n%s\n+\n%s\n" % (i, s, "F" * len(s)) for i, s in enumerate(seqs)).encode()
+    else:
+        text = "".join(">read%d\n%s\n" % (i, s) for i, s in enumerate(seqs)).encode()
+    path = str(tmp_path / ("in.%s.gz" % ("fastq" if fmt == "fq" else "fasta")))
+    with open(path, "wb") as fh:
+        fh.write(b"".join(_member(text[i:i + 700]) for i in range(0, len(text), 700)) + EOF_BLOCK)
+    monkeypatch.setattr(fx._DeviceInflateFeeder, "FIRST", 50)
+    monkeypatch.setattr(dr.DeviceFeeder, "FIRST", 50)
+    monkeypatch.setenv("RD_DEVICE_INFLATE", "0")
+    whole = _host_records(fx.get_seq_chunks(path, chunk_size=997))
+    monkeypatch.delenv("RD_DEVICE_INFLATE")
+    assert len(whole[1]) == 3000 and whole[0] == text
+    view = fx.BgzfView(path)
+    shares = [fx.plan_ranges([path], rank, 3, views=[view])[0] for rank in range(3)]
+    assert all(isinstance(sh, fx.BgzfRange) and sh[1] > sh[0] for sh in shares)
+    host = [_host_records(fx.get_seq_chunks(path, chunk_size=997, byte_range=sh)) for sh in shares]
+    dev = [_device_records(dr.get_seq_chunks_device(path, chunk_size=997, byte_range=sh, device=DEV)) for sh in shares]
+    for route in (host, dev):
+        assert b"".join(r[0] for r in route) == whole[0]
+        assert np.array_equal(np.concatenate([r[1] for r in route]), whole[1])
+        assert np.array_equal(np.concatenate([r[2] for r in route]), whole[2])
+    assert [len(r[1]) for r in host] == [len(r[1]) for r in dev]              # every rank delivers the same number of records on both routes
+    assert [r[0] for r in host] == [text[a:b] for a, b in shares]
+
+
 def test_members_without_a_size_behind_bgzf_blocks_go_to_the_host(tmp_path, monkeypatch):
-    """`cat a.bgzf.gz b.gz`: the BGZF blocks are inflated on the GPU, the plain gzip members behind them by zlib on the host, in order"""
+    """`cat a.bgzf.gz b.gz`: the BGZF blocks are inflated on the GPU, the plain gzip members behind them by zlib on the host, in order -
+    through the host-parse feeder and through the device feeder, with and without zero padding behind the last member"""
+    from ribodetector_amd.data_loader import device_reader as dr
     from ribodetector_amd.data_loader import fastx_parser as fx
     recs = ["@r%d\n%s\n+\n%s\n" % (i, "ACGT" * 20, "F" * 80) for i in range(9000)]
     a, b, c = "".join(recs[:5000]).encode(), "".join(recs[5000:7000]).encode(), "".join(recs[7000:]).encode()
-    path = str(tmp_path / "mixed.fastq.gz")
-    with open(path, "wb") as fh:
-        for i in range(0, len(a), 65280):
-            fh.write(_member(a[i:i + 65280]))
-        fh.write(gzip.compress(b) + gzip.compress(c))
+    path, padded = str(tmp_path / "mixed.fastq.gz"), str(tmp_path / "padded.fastq.gz")
+    blob = b"".join(_member(a[i:i + 65280]) for i in range(0, len(a), 65280)) + gzip.compress(b) + gzip.compress(c)
+    open(path, "wb").write(blob)
+    open(padded, "wb").write(blob + b"\0" * 4096)
     monkeypatch.delenv("RD_DEVICE_INFLATE", raising=False)
-    assert fx.device_inflate_wanted(path)
-    got = b"".join(ch.buf[ch.rec_start[0]:ch.rec_start[-1]].tobytes() for ch in fx.get_seq_chunks(path, chunk_size=4000))
-    assert got == a + b + c
+    for p in (path, padded):
+        assert fx.device_inflate_wanted(p)
+        got = b"".join(ch.buf[ch.rec_start[0]:ch.rec_start[-1]].tobytes() for ch in fx.get_seq_chunks(p, chunk_size=4000))
+        assert got == a + b + c
+        assert _device_records(dr.get_seq_chunks_device(p, chunk_size=4000, device=DEV))[0] == a + b + c
     with open(path, "ab") as fh:
         fh.write(gzip.compress(b"@x\nAC\n+\nFF\n")[:-6])               # and a truncated member at the very end is an error, not silence
     with pytest.raises(ValueError, match="ended before the end-of-stream marker"):
         list(fx.get_seq_chunks(path, chunk_size=4000))
+    with pytest.raises(ValueError, match="ended before the end-of-stream marker"):
+        list(dr.get_seq_chunks_device(path, chunk_size=4000, device=DEV))

@@ -2,7 +2,8 @@
 """The chunk reader alone, no classification: 4 Mi sequencer-like records as a plain file, as BGZF through the device inflate (with the
 feeder's stage times: RD_FEED_TRACE) and as BGZF through the host's member decoder - records/s and CPU seconds of each. Shows what
 the reader can deliver when nothing else wants the GPU (inside a run the inflate batches wait for the gaps between the recurrence
-launches: data_loader/fastx_parser.py:_DeviceInflateFeeder keeps two of them in flight for that reason).   python tools/feed_probe.py"""
+launches: data_loader/fastx_parser.py:_DeviceInflateFeeder keeps two of them in flight for that reason; the batching loop itself is
+data_loader/member_batches.py:member_batches).   python tools/feed_probe.py"""
 import os, sys, time, json
 sys.path.insert(0, os.getcwd())
 import numpy as np, torch
