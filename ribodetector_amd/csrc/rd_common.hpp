@@ -95,6 +95,24 @@ struct DevModel {
     uint8_t *zero_row;  // one all-zero prefix-table row (1 KiB): where every read starts while no prefix-state table is attached
 };
 
+// ------------------------------------------------------------------------------------------------
+// host: a workspace handed out piece by piece, every piece 256-byte aligned. With a null base nothing is handed out and `off`
+// only adds up the sizes, so ONE walk both sizes a workspace (*_workspace_bytes) and carves it (the entry point)
+// ------------------------------------------------------------------------------------------------
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+struct Carver {
+    char *base;
+    size_t off;
+    explicit Carver(void *workspace) : base((char *)workspace), off(0) {}
+    template <typename T>
+    T *take(size_t count) {
+        T *p = base ? (T *)(base + off) : nullptr;
+        off += align_up(count * sizeof(T), 256);
+        return p;
+    }
+};
+
 }  // namespace
 
 struct rd_model {

@@ -282,22 +282,26 @@ __global__ __launch_bounds__(FQ_THREADS) void rd_fa_sample_kernel(const int64_t 
     for (int64_t k = (int64_t)blockIdx.x * FQ_THREADS + threadIdx.x; k < cap; k += stride) samples[k] = k * every <= n ? (int32_t)rec_tab[k * every] : -1;
 }
 
-struct FaPlan {
-    FqPlan fq;
+struct FaWs {
+    FqWs fq;
     int nblk;
-    size_t a_off, k_off, blk_off, sc_off, total;
+    int32_t *info_a;
+    uint32_t *info_k;
+    unsigned long long *blk;
+    FaScratch *sc;
+    size_t total;
 };
-FaPlan fa_plan(int64_t text_end, int64_t cap_lines) {
-    FaPlan p;
-    p.fq = fq_plan(text_end);
+FaWs fa_ws(void *workspace, int64_t text_end, int64_t cap_lines) {
+    FaWs p;
+    Carver c(workspace);
+    p.fq = fq_ws(c, text_end);
     p.nblk = (int)((cap_lines + FA_BLOCK - 1) / FA_BLOCK);
     if (p.nblk < 1) p.nblk = 1;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    p.a_off = up(p.fq.total);
-    p.k_off = p.a_off + up((size_t)cap_lines * 4);
-    p.blk_off = p.k_off + up((size_t)cap_lines * 4);
-    p.sc_off = p.blk_off + up((size_t)p.nblk * 8);
-    p.total = p.sc_off + 256;
+    p.info_a = c.take<int32_t>((size_t)cap_lines);
+    p.info_k = c.take<uint32_t>((size_t)cap_lines);
+    p.blk = c.take<unsigned long long>((size_t)p.nblk);
+    p.sc = c.take<FaScratch>(1);
+    p.total = c.off;
     return p;
 }
 

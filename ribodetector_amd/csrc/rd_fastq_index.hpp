@@ -320,17 +320,77 @@ __global__ __launch_bounds__(COPY_THREADS) void rd_copy_kernel(uint8_t *__restri
     if (tail0 + gtid < n && gtid < 16) dst[tail0 + gtid] = src[tail0 + gtid];
 }
 
-struct FqPlan {
+// ------------------------------------------------------------------------------------------------
+// host: what the FASTQ and the FASTA entry points of the C ABI share (rd_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+// the workspace of rd_fastq_index, and the head of rd_fasta_index's (rd_fasta_index.hpp): the newline count of every tile
+struct FqWs {
     int ntiles;
-    size_t count_bytes, total;
+    uint32_t *tiles;
+    size_t total;
 };
-FqPlan fq_plan(int64_t text_end) {
-    FqPlan p;
+FqWs fq_ws(Carver &c, int64_t text_end) {
+    FqWs p;
     p.ntiles = (int)((text_end + 1 + FQ_TILE - 1) / FQ_TILE);
     if (p.ntiles < 1) p.ntiles = 1;
-    p.count_bytes = ((size_t)p.ntiles * 4 + 255) / 256 * 256;
-    p.total = p.count_bytes;
+    p.tiles = c.take<uint32_t>((size_t)p.ntiles);
+    p.total = c.off;
     return p;
+}
+FqWs fq_ws(void *workspace, int64_t text_end) {
+    Carver c(workspace);
+    return fq_ws(c, text_end);
+}
+
+// the argument checks of rd_fastq_index and rd_fasta_index (`fn`). fa_null / fa_bad: what FASTA's own tables add to the first two;
+// norm: FASTA's re-written text (null: FASTQ)
+int fq_index_check(const char *fn, const uint8_t *text, int64_t pad, int64_t end, const uint8_t *prev_text, const rd_fq_summary *prev, const int32_t *line_end,
+                   int64_t cap_lines, const rd_fq_summary *summary, const void *workspace, bool fa_null, bool fa_bad, const uint8_t *norm) {
+    if (!text || !line_end || !summary || !workspace || fa_null) RD_FAIL(RD_E_INVALID, "%s: null pointer", fn);
+    if (pad < 0 || end < pad || end >= 0x7fffffffLL - 64 || cap_lines < 0 || fa_bad)
+        RD_FAIL(RD_E_INVALID, "%s: bad pad / end / cap_lines%s (a batch buffer is < 2 GiB)", fn, norm ? " / norm_cap / cap_records" : "");
+    if ((prev == nullptr) != (prev_text == nullptr)) RD_FAIL(RD_E_INVALID, "%s: prev and prev_text go together", fn);
+    if (((uintptr_t)text & 63) || ((uintptr_t)workspace & 255) || ((uintptr_t)norm & 15))
+        RD_FAIL(RD_E_INVALID, "%s: text must be 64-byte aligned, workspace 256-byte aligned%s", fn, norm ? ", norm 16-byte aligned" : "");
+    return RD_OK;
+}
+
+// the line table of a batch: where its text begins behind the carry, newlines per tile, their scan, line_end[]
+void fq_line_table(uint8_t *text, int64_t pad, int64_t end, const uint8_t *prev_text, const rd_fq_summary *prev, int32_t final, int32_t *line_end, int64_t cap_lines,
+                   FqSummary *sum, const FqWs &w, hipStream_t st) {
+    hipLaunchKernelGGL(rd_fq_begin_kernel, dim3(1), dim3(FQ_THREADS), 0, st, text, pad, end, prev_text, (const FqSummary *)prev, (int)final, sum);
+    hipLaunchKernelGGL(rd_fq_count_kernel, dim3(w.ntiles), dim3(FQ_THREADS), 0, st, text, sum, w.tiles);
+    hipLaunchKernelGGL(rd_fq_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, st, w.tiles, w.ntiles, sum, cap_lines);
+    hipLaunchKernelGGL(rd_fq_fill_kernel, dim3(w.ntiles), dim3(FQ_THREADS), 0, st, text, sum, w.tiles, line_end);
+}
+
+// rd_fastq_gather / rd_fasta_gather (`fn`): the checks, the grid and the launch of `kernel`, which takes the format's `tables` first
+template <typename K, typename... T>
+int fq_gather(const char *fn, K kernel, const rd_fq_summary *summary, int64_t rec_lo, int64_t rec_hi, int64_t max_bytes, uint8_t *out_text, int64_t out_cap,
+              const int64_t *cursor_in, int64_t *cursor_out, int64_t *rec_start, int64_t *seq_off, int32_t *seq_len, void *stream, T... tables) {
+    if ((... || !tables) || !summary || !out_text || !cursor_in || !cursor_out || !rec_start || !seq_off || !seq_len) RD_FAIL(RD_E_INVALID, "%s: null pointer", fn);
+    if (rec_lo < 0 || rec_hi < rec_lo || max_bytes < 0 || out_cap < 0 || cursor_in == cursor_out) RD_FAIL(RD_E_INVALID, "%s: bad range", fn);
+    if ((uintptr_t)out_text & 15) RD_FAIL(RD_E_INVALID, "%s: out_text must be 16-byte aligned", fn);
+    int64_t grid = max_bytes / (16 * FQ_THREADS * 4) + 1;       // four 16-byte pieces per thread
+    const int64_t grid_r = (rec_hi - rec_lo) / FQ_THREADS + 1;
+    if (grid < grid_r) grid = grid_r;
+    if (grid > 8192) grid = 8192;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(FQ_THREADS), 0, (hipStream_t)stream, tables..., (const FqSummary *)summary, rec_lo, rec_hi, out_text, out_cap,
+                       cursor_in, cursor_out, rec_start, seq_off, seq_len);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+// rd_fastq_sample / rd_fasta_sample (`fn`): the same for the sample kernels, which read one `table`
+template <typename K, typename T>
+int fq_sample(const char *fn, K kernel, const T *table, const rd_fq_summary *summary, int64_t every, int32_t *samples, int64_t cap, void *stream) {
+    if (!table || !summary || !samples || every < 1 || cap < 0) RD_FAIL(RD_E_INVALID, "%s: bad argument", fn);
+    if (cap == 0) return RD_OK;
+    int64_t grid = cap / FQ_THREADS + 1;
+    if (grid > 1024) grid = 1024;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(FQ_THREADS), 0, (hipStream_t)stream, table, (const FqSummary *)summary, every, samples, cap);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
 }
 
 }  // namespace

@@ -645,29 +645,35 @@ __global__ __launch_bounds__(64) void rd_gzs_fold_kernel(const uint32_t *__restr
     }
 }
 
-struct GzsPlan {
+// the workspace of one batch (rd_gz_stream_inflate / rd_gz_range_decode) and the launch dimensions that go with it
+struct GzsWs {
     int nsec, tiles_per_sec, ctiles, ngroups;
-    size_t found_bytes, sec_bytes, off_bytes, wslot_bytes, plist_bytes, crc_bytes, windows_bytes, gmaps_bytes, gwin_bytes, syms_bytes, total;
+    uint32_t *found, *tcrc;                     // (tcrc: unused by a range decode, whose CRC comes with rd_gz_range_resolve)
+    GzsSec *sec;
+    int64_t *off;
+    int32_t *wslot, *plist;
+    uint16_t *windows16, *gmaps, *gwin, *syms;  // (windows: 16-bit entries, a window relative to its group's)
+    size_t total;
 };
-GzsPlan gzs_plan(int64_t data_bytes, int32_t section_bytes, int32_t cap_syms, int64_t text_cap) {
-    GzsPlan p;
+GzsWs gzs_ws(void *workspace, int64_t data_bytes, int32_t section_bytes, int32_t cap_syms, int64_t text_cap) {
+    GzsWs p;
+    Carver c(workspace);
     p.nsec = (int)((data_bytes + section_bytes - 1) / section_bytes);
     if (p.nsec < 1) p.nsec = 1;
     p.tiles_per_sec = (cap_syms + GZS_RTILE - 1) / GZS_RTILE;
     p.ctiles = (int)((text_cap + GZS_CTILE - 1) / GZS_CTILE) + 1;
     p.ngroups = (p.nsec + GZS_GROUP - 1) / GZS_GROUP;
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    p.found_bytes = al((size_t)(p.nsec + 1) * 4);
-    p.sec_bytes = al((size_t)p.nsec * sizeof(GzsSec));
-    p.off_bytes = al((size_t)(p.nsec + 1) * 8);
-    p.wslot_bytes = al((size_t)(p.nsec + 1) * 4);
-    p.plist_bytes = al((size_t)(p.nsec + 1) * 4);
-    p.crc_bytes = al((size_t)p.ctiles * 4);
-    p.windows_bytes = al((size_t)(p.nsec + 1) * GZS_WIN * 2);      // (16-bit entries: a window relative to its group's)
-    p.gmaps_bytes = al((size_t)p.ngroups * GZS_WIN * 2);
-    p.gwin_bytes = al((size_t)(p.ngroups + 1) * GZS_WIN * 2);
-    p.syms_bytes = al((size_t)p.nsec * (size_t)cap_syms * 2);
-    p.total = p.found_bytes + p.sec_bytes + p.off_bytes + p.wslot_bytes + p.plist_bytes + p.crc_bytes + p.windows_bytes + p.gmaps_bytes + p.gwin_bytes + p.syms_bytes;
+    p.found = c.take<uint32_t>((size_t)(p.nsec + 1));
+    p.sec = c.take<GzsSec>((size_t)p.nsec);
+    p.off = c.take<int64_t>((size_t)(p.nsec + 1));
+    p.wslot = c.take<int32_t>((size_t)(p.nsec + 1));
+    p.plist = c.take<int32_t>((size_t)(p.nsec + 1));
+    p.tcrc = c.take<uint32_t>((size_t)p.ctiles);
+    p.windows16 = c.take<uint16_t>((size_t)(p.nsec + 1) * GZS_WIN);
+    p.gmaps = c.take<uint16_t>((size_t)p.ngroups * GZS_WIN);
+    p.gwin = c.take<uint16_t>((size_t)(p.ngroups + 1) * GZS_WIN);
+    p.syms = c.take<uint16_t>((size_t)p.nsec * (size_t)cap_syms);
+    p.total = c.off;
     return p;
 }
 

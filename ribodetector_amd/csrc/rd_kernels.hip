@@ -362,7 +362,7 @@ int rd_set_prefix_table(rd_model *m, int32_t k, void *table, size_t table_bytes,
 
 size_t rd_classify_workspace_bytes(int64_t n, int32_t max_len) {
     if (n < 0 || max_len < 1) return 0;
-    return sort_plan(n, max_len).total;
+    return sort_ws(nullptr, n, max_len).total;
 }
 
 int rd_profile_enable(rd_model *m, int enable) {
@@ -404,8 +404,8 @@ int rd_classify(const rd_model *cm, const uint8_t *arena, const int64_t *seq_off
     if (n == 0) return RD_OK;
     if (!arena || !seq_off || !seq_len || !workspace) RD_FAIL(RD_E_INVALID, "rd_classify: null input pointer");
     hipStream_t st = (hipStream_t)stream;
-    const SortPlan sp = sort_plan(n, max_len);
-    if (workspace_bytes < sp.total) RD_FAIL(RD_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, sp.total);
+    const size_t need = sort_ws(nullptr, n, max_len).total;
+    if (workspace_bytes < need) RD_FAIL(RD_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
     // deferred float64 pass (rd_set_refine_async): not inside a stream capture (a captured call stays self-contained)
     bool deferred = false;
     int join_after_launch = -1;
@@ -587,33 +587,65 @@ int rd_pack_onehot(const uint8_t *arena, const int64_t *seq_off, const int32_t *
 
 // ---- device-side gzip of the label-partitioned records (rd_deflate.hpp) ------------------------------------------------------------
 namespace {
-struct GzPlan {
+// the workspace of rd_gz_compress_selected; its head, the selection scan's part, is all of rd_select_pack's. Sizes that the entry
+// points refuse (n < 0, text_bytes < 0) give an empty layout: total = 0, what the *_workspace_bytes functions answer to them
+struct GzWs {
     int nb;                 // scan blocks
     int64_t cap_members;    // members the chunk can have at most (every record selected)
     int grid;               // workgroups of the deflate kernel
-    size_t off_bytes, bsum_bytes, plain_bytes, toks_bytes, slots_bytes, msize_bytes, moff_bytes, total;
+    int64_t *out_off, *bsum, *moff;
+    uint8_t *plain, *slots;
+    uint32_t *toks, *msize;
+    size_t sel_total, total;    // sel_total: the bytes of out_off + bsum, the selection scan's part
 };
-GzPlan gz_plan(int64_t n, int64_t text_bytes) {
-    GzPlan p;
+GzWs gz_ws(void *workspace, int64_t n, int64_t text_bytes) {
+    GzWs p{};
+    if (n < 0 || text_bytes < 0) return p;
+    Carver c(workspace);
     p.nb = (int)((n + 1 + GZ_SCAN_ITEMS - 1) / GZ_SCAN_ITEMS);
     p.cap_members = (text_bytes + GZ_MEMBER - 1) / GZ_MEMBER;
     if (p.cap_members < 1) p.cap_members = 1;
     p.grid = (int)(p.cap_members < GZ_MAX_GRID ? p.cap_members : GZ_MAX_GRID);
-    p.off_bytes = align_up((size_t)(n + 1) * 8, 256);
-    p.bsum_bytes = align_up((size_t)p.nb * 8, 256);
-    p.plain_bytes = align_up((size_t)p.cap_members * GZ_MEMBER + 256, 256);
-    p.toks_bytes = align_up((size_t)p.grid * GZ_MEMBER * 4, 256);
-    p.slots_bytes = (size_t)p.cap_members * GZ_SLOT;
-    p.msize_bytes = align_up((size_t)p.cap_members * 4, 256);
-    p.moff_bytes = align_up((size_t)p.cap_members * 8, 256);
-    p.total = p.off_bytes + p.bsum_bytes + p.plain_bytes + p.toks_bytes + p.slots_bytes + p.msize_bytes + p.moff_bytes;
+    p.out_off = c.take<int64_t>((size_t)(n + 1));
+    p.bsum = c.take<int64_t>((size_t)p.nb);
+    p.sel_total = c.off;
+    p.plain = c.take<uint8_t>((size_t)p.cap_members * GZ_MEMBER + 256);
+    p.toks = c.take<uint32_t>((size_t)p.grid * GZ_MEMBER);
+    p.slots = c.take<uint8_t>((size_t)p.cap_members * GZ_SLOT);
+    p.msize = c.take<uint32_t>((size_t)p.cap_members);
+    p.moff = c.take<int64_t>((size_t)p.cap_members);
+    p.total = c.off;
     return p;
+}
+
+// What rd_gz_compress_selected and rd_select_pack (`fn`) share: the argument checks, the n == 0 path, and the selection scan that
+// packs the selected records into `dst` (more selected bytes than `limit`: info[3] = 1, nothing packed). `need` = the bytes of the
+// caller's workspace, `out` must be out_align-byte aligned. The caller goes on only when n > 0.
+int sel_scan_pack(const char *fn, const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int8_t *labels, int64_t n, int32_t label,
+                  const uint8_t *out, unsigned out_align, int64_t *info, const void *workspace, size_t workspace_bytes, size_t need, const GzWs &s,
+                  uint8_t *dst, int64_t limit, hipStream_t st) {
+    if (n < 0 || n > 0x7fffffffLL || text_bytes < 0) RD_FAIL(RD_E_INVALID, "%s: bad n or text_bytes", fn);
+    if (!info) RD_FAIL(RD_E_INVALID, "%s: null info", fn);
+    if (label < -128 || label > 127) RD_FAIL(RD_E_INVALID, "%s: label %d is not an int8 value", fn, label);
+    if (n == 0) {
+        RD_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int64_t), st));
+        return RD_OK;
+    }
+    if ((!text && text_bytes > 0) || !rec_start || !labels || !out || !workspace) RD_FAIL(RD_E_INVALID, "%s: null pointer", fn);
+    if (((uintptr_t)workspace & 255) || ((uintptr_t)out & (out_align - 1)))
+        RD_FAIL(RD_E_INVALID, "%s: workspace must be 256-byte aligned, out %u-byte aligned", fn, out_align);
+    if (workspace_bytes < need) RD_FAIL(RD_E_WORKSPACE, "%s: workspace too small: %zu < %zu", fn, workspace_bytes, need);
+    hipLaunchKernelGGL(rd_gz_sel_sum_kernel, dim3(s.nb), dim3(256), 0, st, rec_start, labels, n, label, s.bsum);
+    hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, s.bsum, s.nb, info, limit);
+    hipLaunchKernelGGL(rd_gz_sel_off_kernel, dim3(s.nb), dim3(256), 0, st, rec_start, labels, n, label, s.bsum, s.out_off);
+    hipLaunchKernelGGL(rd_gz_pack_kernel, dim3((unsigned)((n + GZ_PACK_RECS - 1) / GZ_PACK_RECS)), dim3(256), 0, st, text, rec_start, s.out_off, n, dst, info);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
 }
 }  // namespace
 
 size_t rd_gz_workspace_bytes(int64_t n, int64_t text_bytes) {
-    if (n < 0 || text_bytes < 0) return 0;
-    return gz_plan(n, text_bytes).total;
+    return gz_ws(nullptr, n, text_bytes).total;
 }
 
 size_t rd_gz_out_bound(int64_t text_bytes) {
@@ -632,35 +664,29 @@ int rd_gz_eof_block(uint8_t *dst, size_t cap) {   // BGZF's end-of-file marker: 
 int rd_gz_compress_selected(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int8_t *labels, int64_t n,
                             int32_t label, uint8_t *out, size_t out_cap, int64_t *info, void *workspace, size_t workspace_bytes,
                             void *stream) {
-    if (n < 0 || n > 0x7fffffffLL || text_bytes < 0) RD_FAIL(RD_E_INVALID, "rd_gz_compress_selected: bad n or text_bytes");
-    if (!info) RD_FAIL(RD_E_INVALID, "rd_gz_compress_selected: null info");
-    if (label < -128 || label > 127) RD_FAIL(RD_E_INVALID, "rd_gz_compress_selected: label %d is not an int8 value", label);
     hipStream_t st = (hipStream_t)stream;
-    if (n == 0) {
-        RD_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int64_t), st));
-        return RD_OK;
-    }
-    if ((!text && text_bytes > 0) || !rec_start || !labels || !out || !workspace) RD_FAIL(RD_E_INVALID, "rd_gz_compress_selected: null pointer");
-    if (((uintptr_t)workspace & 255) || ((uintptr_t)out & 255)) RD_FAIL(RD_E_INVALID, "rd_gz_compress_selected: workspace and out must be 256-byte aligned");
-    const GzPlan p = gz_plan(n, text_bytes);
-    if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "rd_gz_compress_selected: workspace too small: %zu < %zu", workspace_bytes, p.total);
-    char *w = (char *)workspace;
-    int64_t *out_off = (int64_t *)w; w += p.off_bytes;
-    int64_t *bsum = (int64_t *)w; w += p.bsum_bytes;
-    uint8_t *plain = (uint8_t *)w; w += p.plain_bytes;
-    uint32_t *toks = (uint32_t *)w; w += p.toks_bytes;
-    uint8_t *slots = (uint8_t *)w; w += p.slots_bytes;
-    uint32_t *msize = (uint32_t *)w; w += p.msize_bytes;
-    int64_t *moff = (int64_t *)w;
-    hipLaunchKernelGGL(rd_gz_sel_sum_kernel, dim3(p.nb), dim3(256), 0, st, rec_start, labels, n, label, bsum);
-    hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, bsum, p.nb, info, text_bytes);
-    hipLaunchKernelGGL(rd_gz_sel_off_kernel, dim3(p.nb), dim3(256), 0, st, rec_start, labels, n, label, bsum, out_off);
-    hipLaunchKernelGGL(rd_gz_pack_kernel, dim3((unsigned)((n + GZ_PACK_RECS - 1) / GZ_PACK_RECS)), dim3(256), 0, st, text, rec_start, out_off, n, plain, info);
-    hipLaunchKernelGGL(rd_gz_deflate_kernel, dim3(p.grid), dim3(GZ_THREADS), 0, st, plain, info, toks, slots, msize);
-    hipLaunchKernelGGL(rd_gz_moff_kernel, dim3(1), dim3(256), 0, st, msize, moff, info);
-    hipLaunchKernelGGL(rd_gz_compact_kernel, dim3(p.grid), dim3(256), 0, st, slots, msize, moff, info, out, (int64_t)out_cap);
+    const GzWs p = gz_ws(workspace, n, text_bytes);
+    const int rc = sel_scan_pack("rd_gz_compress_selected", text, text_bytes, rec_start, labels, n, label, out, 256, info, workspace, workspace_bytes,
+                                 p.total, p, p.plain, text_bytes, st);
+    if (rc || n == 0) return rc;
+    hipLaunchKernelGGL(rd_gz_deflate_kernel, dim3(p.grid), dim3(GZ_THREADS), 0, st, p.plain, info, p.toks, p.slots, p.msize);
+    hipLaunchKernelGGL(rd_gz_moff_kernel, dim3(1), dim3(256), 0, st, p.msize, p.moff, info);
+    hipLaunchKernelGGL(rd_gz_compact_kernel, dim3(p.grid), dim3(256), 0, st, p.slots, p.msize, p.moff, info, out, (int64_t)out_cap);
     RD_HIP(hipGetLastError());
     return RD_OK;
+}
+
+// the selected records of a chunk as one contiguous text (the selection scan and the pack kernel of the device gzip, without the deflate)
+size_t rd_select_workspace_bytes(int64_t n) {
+    return gz_ws(nullptr, n, 0).sel_total;
+}
+
+int rd_select_pack(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int8_t *labels, int64_t n, int32_t label, uint8_t *out,
+                   size_t out_cap, int64_t *info, void *workspace, size_t workspace_bytes, void *stream) {
+    const GzWs p = gz_ws(workspace, n, 0);
+    const int64_t limit = text_bytes < (int64_t)out_cap ? text_bytes : (int64_t)out_cap;   // more selected bytes than text, or than `out` holds
+    return sel_scan_pack("rd_select_pack", text, text_bytes, rec_start, labels, n, label, out, 16, info, workspace, workspace_bytes, p.sel_total, p, out, limit,
+                         (hipStream_t)stream);
 }
 
 int rd_gz_inflate_members(const uint8_t *comp, int64_t comp_bytes, const rd_gz_member *members, int64_t n, uint8_t *text, int64_t text_bytes,
@@ -677,99 +703,87 @@ int rd_gz_inflate_members(const uint8_t *comp, int64_t comp_bytes, const rd_gz_m
     return RD_OK;
 }
 
-// ---- one DEFLATE stream inflated on the device (rd_inflate_stream.hpp) ----------------------------------------------------------------------
-size_t rd_gz_stream_workspace_bytes(int64_t data_bytes, int32_t section_bytes, int32_t cap_syms, int64_t text_cap) {
+// ---- one DEFLATE stream inflated on the device (rd_inflate_stream.hpp): rd_gz_stream_inflate gives a batch's text as bytes behind the
+// carried window; rd_gz_range_decode (a range of a stream) gives it as symbols, bytes once the window in front of the range is known
+namespace {
+size_t gzs_workspace_bytes(int64_t data_bytes, int32_t section_bytes, int32_t cap_syms, int64_t text_cap) {
     if (data_bytes < 0 || section_bytes < 1024 || cap_syms < 1024 || text_cap < 0) return 0;
-    return gzs_plan(data_bytes, section_bytes, cap_syms, text_cap).total;
+    return gzs_ws(nullptr, data_bytes, section_bytes, cap_syms, text_cap).total;
+}
+
+// CRC-32 and length of text[0, S->n_text) folded into the state
+void gzs_crc_fold(const uint8_t *text, int ctiles, GzsState *S, uint32_t *tcrc, hipStream_t st) {
+    hipLaunchKernelGGL(rd_gzs_crc_kernel, dim3((unsigned)((ctiles + 3) / 4)), dim3(256), 0, st, text, S, tcrc);
+    hipLaunchKernelGGL(rd_gzs_fold_kernel, dim3(1), dim3(64), 0, st, tcrc, S);
+}
+
+// One batch for both entry points (`fn`): validation, carve, block-start search, section decode, scan, then the window chain on symbols
+// (the groups of sections side by side, then the groups in order) and the resolve pass. range = false: `carried_in` / `carried_out` are
+// the 32 KiB window as bytes and `text_out` receives bytes, with their CRC; true: 16-bit maps and symbols, and no CRC yet.
+int gzs_batch(const char *fn, bool range, const uint8_t *comp, int64_t comp_bytes, int64_t data_bytes, int64_t valid_bytes, int32_t section_bytes,
+              int32_t cap_syms, uint32_t first_start_bit, const rd_gzs_state *carry, int64_t carry_delta_bits, int32_t at_eof, const void *carried_in,
+              void *carried_out, void *text_out, int64_t text_cap, rd_gzs_state *state, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *out_name = range ? "sym_text" : "text";
+    const unsigned out_align = range ? 16 : 8;
+    if (!comp || !carried_out || !text_out || !state || !workspace) RD_FAIL(RD_E_INVALID, "%s: null pointer", fn);
+    if (((uintptr_t)comp & 3) || ((uintptr_t)workspace & 255) || ((uintptr_t)text_out & (out_align - 1)))
+        RD_FAIL(RD_E_INVALID, "%s: comp must be 4-byte aligned, %s %u-byte aligned, workspace 256-byte aligned", fn, out_name, out_align);
+    if (data_bytes <= 0 || valid_bytes < data_bytes || comp_bytes < valid_bytes || valid_bytes >= (1LL << 28) || section_bytes < 1024 || (section_bytes & 3) ||
+        cap_syms < 1024 || text_cap < 0)
+        RD_FAIL(RD_E_INVALID, "%s: bad sizes (a batch holds < 256 MiB of compressed bytes)", fn);
+    if (range && (carry == nullptr) != (carried_in == nullptr))
+        RD_FAIL(RD_E_INVALID, "%s: carry and map_in go together (both null: the range's first batch)", fn);
+    const GzsWs p = gzs_ws(workspace, data_bytes, section_bytes, cap_syms, text_cap);
+    if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "%s: workspace too small: %zu < %zu", fn, workspace_bytes, p.total);
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t end_bits = (uint32_t)(valid_bytes * 8), sec_bits = (uint32_t)section_bytes * 8u;
+    GzsState *S = (GzsState *)state;
+    const GzsState *C = (const GzsState *)carry;
+    const int search0 = (range && C == nullptr && first_start_bit == GZS_SEARCH) ? 1 : 0;
+    const dim3 resolve_grid((unsigned)(p.nsec * p.tiles_per_sec));
+    hipLaunchKernelGGL(rd_gzs_search_kernel, dim3((unsigned)((p.nsec + 1 + GZS_WAVES - 1) / GZS_WAVES)), dim3(64 * GZS_WAVES), 0, st, comp, comp_bytes, end_bits, sec_bits,
+                       p.nsec, first_start_bit, C, carry_delta_bits, p.found);
+    hipLaunchKernelGGL(rd_gzs_decode_kernel, dim3((unsigned)((p.nsec + GZS_WAVES - 1) / GZS_WAVES)), dim3(64 * GZS_WAVES), 0, st, comp, comp_bytes, end_bits, p.nsec, p.found,
+                       p.syms, (int)cap_syms, p.sec);
+    hipLaunchKernelGGL(rd_gzs_scan_kernel, dim3(1), dim3(64), 0, st, p.sec, p.found, p.nsec, (int)at_eof, text_cap, p.off, p.wslot, p.plist, S, C, search0);
+    hipLaunchKernelGGL(rd_gzs_symwin_kernel, dim3((unsigned)p.ngroups), dim3(1024), 0, st, p.syms, (int)cap_syms, p.sec, p.plist, p.wslot, p.nsec, S, p.windows16, p.gmaps);
+    if (!range) {
+        hipLaunchKernelGGL(rd_gzs_chain_kernel, dim3(1), dim3(1024), 0, st, p.gmaps, p.wslot, p.nsec, S, (const uint8_t *)carried_in, (const uint16_t *)nullptr, 1, p.gwin,
+                           (uint16_t *)nullptr, (uint8_t *)carried_out);
+        hipLaunchKernelGGL(rd_gzs_resolve_kernel<false>, resolve_grid, dim3(256), 0, st, p.syms, (int)cap_syms, p.sec, p.found, p.off, p.wslot, p.tiles_per_sec, p.windows16,
+                           p.gwin, S, (uint8_t *)text_out, (uint16_t *)nullptr);
+        gzs_crc_fold((const uint8_t *)text_out, p.ctiles, S, p.tcrc, st);
+    } else {
+        hipLaunchKernelGGL(rd_gzs_chain_kernel, dim3(1), dim3(1024), 0, st, p.gmaps, p.wslot, p.nsec, S, (const uint8_t *)nullptr, (const uint16_t *)carried_in, 0, p.gwin,
+                           (uint16_t *)carried_out, (uint8_t *)nullptr);
+        hipLaunchKernelGGL(rd_gzs_resolve_kernel<true>, resolve_grid, dim3(256), 0, st, p.syms, (int)cap_syms, p.sec, p.found, p.off, p.wslot, p.tiles_per_sec, p.windows16,
+                           p.gwin, S, (uint8_t *)nullptr, (uint16_t *)text_out);
+    }
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+}  // namespace
+
+size_t rd_gz_stream_workspace_bytes(int64_t data_bytes, int32_t section_bytes, int32_t cap_syms, int64_t text_cap) {
+    return gzs_workspace_bytes(data_bytes, section_bytes, cap_syms, text_cap);
 }
 
 int rd_gz_stream_inflate(const uint8_t *comp, int64_t comp_bytes, int64_t data_bytes, int64_t valid_bytes, int32_t section_bytes, int32_t cap_syms,
                          uint32_t first_start_bit, const rd_gzs_state *carry, int64_t carry_delta_bits, int32_t at_eof, const uint8_t *win_in,
                          uint8_t *win_out, uint8_t *text, int64_t text_cap, rd_gzs_state *state, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!comp || !win_out || !text || !state || !workspace) RD_FAIL(RD_E_INVALID, "rd_gz_stream_inflate: null pointer");
-    if (((uintptr_t)comp & 3) || ((uintptr_t)workspace & 255) || ((uintptr_t)text & 7))
-        RD_FAIL(RD_E_INVALID, "rd_gz_stream_inflate: comp must be 4-byte aligned, text 8-byte aligned, workspace 256-byte aligned");
-    if (data_bytes <= 0 || valid_bytes < data_bytes || comp_bytes < valid_bytes || valid_bytes >= (1LL << 28) || section_bytes < 1024 || (section_bytes & 3) ||
-        cap_syms < 1024 || text_cap < 0)
-        RD_FAIL(RD_E_INVALID, "rd_gz_stream_inflate: bad sizes (a batch holds < 256 MiB of compressed bytes)");
-    const GzsPlan p = gzs_plan(data_bytes, section_bytes, cap_syms, text_cap);
-    if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "rd_gz_stream_inflate: workspace too small: %zu < %zu", workspace_bytes, p.total);
-    char *w = (char *)workspace;
-    uint32_t *found = (uint32_t *)w; w += p.found_bytes;
-    GzsSec *sec = (GzsSec *)w; w += p.sec_bytes;
-    int64_t *off = (int64_t *)w; w += p.off_bytes;
-    int32_t *wslot = (int32_t *)w; w += p.wslot_bytes;
-    int32_t *plist = (int32_t *)w; w += p.plist_bytes;
-    uint32_t *tcrc = (uint32_t *)w; w += p.crc_bytes;
-    uint16_t *windows16 = (uint16_t *)w; w += p.windows_bytes;
-    uint16_t *gmaps = (uint16_t *)w; w += p.gmaps_bytes;
-    uint16_t *gwin = (uint16_t *)w; w += p.gwin_bytes;
-    uint16_t *syms = (uint16_t *)w;
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t end_bits = (uint32_t)(valid_bytes * 8), sec_bits = (uint32_t)section_bytes * 8u;
-    GzsState *S = (GzsState *)state;
-    const GzsState *C = (const GzsState *)carry;
-    hipLaunchKernelGGL(rd_gzs_search_kernel, dim3((unsigned)((p.nsec + 1 + GZS_WAVES - 1) / GZS_WAVES)), dim3(64 * GZS_WAVES), 0, st, comp, comp_bytes, end_bits, sec_bits,
-                       p.nsec, first_start_bit, C, carry_delta_bits, found);
-    hipLaunchKernelGGL(rd_gzs_decode_kernel, dim3((unsigned)((p.nsec + GZS_WAVES - 1) / GZS_WAVES)), dim3(64 * GZS_WAVES), 0, st, comp, comp_bytes, end_bits, p.nsec, found,
-                       syms, (int)cap_syms, sec);
-    hipLaunchKernelGGL(rd_gzs_scan_kernel, dim3(1), dim3(64), 0, st, sec, found, p.nsec, (int)at_eof, text_cap, off, wslot, plist, S, C, 0);
-    // the window chain on symbols: the groups of sections side by side, then the groups in order (rd_inflate_stream.hpp)
-    hipLaunchKernelGGL(rd_gzs_symwin_kernel, dim3((unsigned)p.ngroups), dim3(1024), 0, st, syms, (int)cap_syms, sec, plist, wslot, p.nsec, S, windows16, gmaps);
-    hipLaunchKernelGGL(rd_gzs_chain_kernel, dim3(1), dim3(1024), 0, st, gmaps, wslot, p.nsec, S, win_in, (const uint16_t *)nullptr, 1, gwin, (uint16_t *)nullptr, win_out);
-    hipLaunchKernelGGL(rd_gzs_resolve_kernel<false>, dim3((unsigned)(p.nsec * p.tiles_per_sec)), dim3(256), 0, st, syms, (int)cap_syms, sec, found, off, wslot,
-                       p.tiles_per_sec, windows16, gwin, S, text, (uint16_t *)nullptr);
-    hipLaunchKernelGGL(rd_gzs_crc_kernel, dim3((unsigned)((p.ctiles + 3) / 4)), dim3(256), 0, st, text, S, tcrc);
-    hipLaunchKernelGGL(rd_gzs_fold_kernel, dim3(1), dim3(64), 0, st, tcrc, S);
-    RD_HIP(hipGetLastError());
-    return RD_OK;
+    return gzs_batch("rd_gz_stream_inflate", false, comp, comp_bytes, data_bytes, valid_bytes, section_bytes, cap_syms, first_start_bit, carry, carry_delta_bits,
+                     at_eof, win_in, win_out, text, text_cap, state, workspace, workspace_bytes, stream);
 }
 
-// ---- a range of one DEFLATE stream: symbols first, bytes once the window in front of the range is known (rd_inflate_stream.hpp) -----------
 size_t rd_gz_range_workspace_bytes(int64_t data_bytes, int32_t section_bytes, int32_t cap_syms, int64_t text_cap) {
-    if (data_bytes < 0 || section_bytes < 1024 || cap_syms < 1024 || text_cap < 0) return 0;
-    return gzs_plan(data_bytes, section_bytes, cap_syms, text_cap).total;
+    return gzs_workspace_bytes(data_bytes, section_bytes, cap_syms, text_cap);
 }
 
 int rd_gz_range_decode(const uint8_t *comp, int64_t comp_bytes, int64_t data_bytes, int64_t valid_bytes, int32_t section_bytes, int32_t cap_syms,
                        uint32_t first_start_bit, const rd_gzs_state *carry, int64_t carry_delta_bits, int32_t at_eof, const uint16_t *map_in, uint16_t *map_out,
                        uint16_t *sym_text, int64_t text_cap, rd_gzs_state *state, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!comp || !map_out || !sym_text || !state || !workspace) RD_FAIL(RD_E_INVALID, "rd_gz_range_decode: null pointer");
-    if (((uintptr_t)comp & 3) || ((uintptr_t)workspace & 255) || ((uintptr_t)sym_text & 15))
-        RD_FAIL(RD_E_INVALID, "rd_gz_range_decode: comp must be 4-byte aligned, sym_text 16-byte aligned, workspace 256-byte aligned");
-    if (data_bytes <= 0 || valid_bytes < data_bytes || comp_bytes < valid_bytes || valid_bytes >= (1LL << 28) || section_bytes < 1024 || (section_bytes & 3) ||
-        cap_syms < 1024 || text_cap < 0)
-        RD_FAIL(RD_E_INVALID, "rd_gz_range_decode: bad sizes (a batch holds < 256 MiB of compressed bytes)");
-    if ((carry == nullptr) != (map_in == nullptr)) RD_FAIL(RD_E_INVALID, "rd_gz_range_decode: carry and map_in go together (both null: the range's first batch)");
-    const GzsPlan p = gzs_plan(data_bytes, section_bytes, cap_syms, text_cap);
-    if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "rd_gz_range_decode: workspace too small: %zu < %zu", workspace_bytes, p.total);
-    char *w = (char *)workspace;
-    uint32_t *found = (uint32_t *)w; w += p.found_bytes;
-    GzsSec *sec = (GzsSec *)w; w += p.sec_bytes;
-    int64_t *off = (int64_t *)w; w += p.off_bytes;
-    int32_t *wslot = (int32_t *)w; w += p.wslot_bytes;
-    int32_t *plist = (int32_t *)w; w += p.plist_bytes;
-    w += p.crc_bytes;
-    uint16_t *windows16 = (uint16_t *)w; w += p.windows_bytes;
-    uint16_t *gmaps = (uint16_t *)w; w += p.gmaps_bytes;
-    uint16_t *gwin = (uint16_t *)w; w += p.gwin_bytes;
-    uint16_t *syms = (uint16_t *)w;
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t end_bits = (uint32_t)(valid_bytes * 8), sec_bits = (uint32_t)section_bytes * 8u;
-    GzsState *S = (GzsState *)state;
-    const GzsState *C = (const GzsState *)carry;
-    const int search0 = (C == nullptr && first_start_bit == GZS_SEARCH) ? 1 : 0;
-    hipLaunchKernelGGL(rd_gzs_search_kernel, dim3((unsigned)((p.nsec + 1 + GZS_WAVES - 1) / GZS_WAVES)), dim3(64 * GZS_WAVES), 0, st, comp, comp_bytes, end_bits, sec_bits,
-                       p.nsec, first_start_bit, C, carry_delta_bits, found);
-    hipLaunchKernelGGL(rd_gzs_decode_kernel, dim3((unsigned)((p.nsec + GZS_WAVES - 1) / GZS_WAVES)), dim3(64 * GZS_WAVES), 0, st, comp, comp_bytes, end_bits, p.nsec, found,
-                       syms, (int)cap_syms, sec);
-    hipLaunchKernelGGL(rd_gzs_scan_kernel, dim3(1), dim3(64), 0, st, sec, found, p.nsec, (int)at_eof, text_cap, off, wslot, plist, S, C, search0);
-    hipLaunchKernelGGL(rd_gzs_symwin_kernel, dim3((unsigned)p.ngroups), dim3(1024), 0, st, syms, (int)cap_syms, sec, plist, wslot, p.nsec, S, windows16, gmaps);
-    hipLaunchKernelGGL(rd_gzs_chain_kernel, dim3(1), dim3(1024), 0, st, gmaps, wslot, p.nsec, S, (const uint8_t *)nullptr, map_in, 0, gwin, map_out, (uint8_t *)nullptr);
-    hipLaunchKernelGGL(rd_gzs_resolve_kernel<true>, dim3((unsigned)(p.nsec * p.tiles_per_sec)), dim3(256), 0, st, syms, (int)cap_syms, sec, found, off, wslot,
-                       p.tiles_per_sec, windows16, gwin, S, (uint8_t *)nullptr, sym_text);
-    RD_HIP(hipGetLastError());
-    return RD_OK;
+    return gzs_batch("rd_gz_range_decode", true, comp, comp_bytes, data_bytes, valid_bytes, section_bytes, cap_syms, first_start_bit, carry, carry_delta_bits,
+                     at_eof, map_in, map_out, sym_text, text_cap, state, workspace, workspace_bytes, stream);
 }
 
 size_t rd_gz_range_resolve_workspace_bytes(int64_t n) { return n < 0 ? 0 : ((size_t)(n / GZS_CTILE + 2) * 4 + 255) / 256 * 256; }
@@ -785,9 +799,7 @@ int rd_gz_range_resolve(const uint16_t *sym_text, int64_t n, const uint8_t *wind
     int64_t grid = n / (8 * 256 * 4) + 1;
     if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(rd_gzs_symtext_kernel, dim3((unsigned)grid), dim3(256), 0, st, sym_text, n, window, win_valid, text, S);
-    const int ctiles = (int)((n + GZS_CTILE - 1) / GZS_CTILE) + 1;
-    hipLaunchKernelGGL(rd_gzs_crc_kernel, dim3((unsigned)((ctiles + 3) / 4)), dim3(256), 0, st, text, S, (uint32_t *)workspace);
-    hipLaunchKernelGGL(rd_gzs_fold_kernel, dim3(1), dim3(64), 0, st, (const uint32_t *)workspace, S);
+    gzs_crc_fold(text, (int)((n + GZS_CTILE - 1) / GZS_CTILE) + 1, S, (uint32_t *)workspace, st);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }
@@ -824,27 +836,20 @@ int rd_copy_bytes(void *dst, const void *src, int64_t n, int32_t workgroups, voi
     return RD_OK;
 }
 
-// ---- FASTQ record index on the device (rd_fastq_index.hpp) ----------------------------------------------------------------------------------
+// ---- FASTQ record index on the device, FASTA batches re-written and indexed (rd_fastq_index.hpp, which ends in the host code the two share; rd_fasta_index.hpp)
 size_t rd_fastq_index_workspace_bytes(int64_t text_end) {
     if (text_end < 0 || text_end >= 0x7fffffffLL) return 0;
-    return fq_plan(text_end).total;
+    return fq_ws(nullptr, text_end).total;
 }
 
 int rd_fastq_index(uint8_t *text, int64_t pad, int64_t end, const uint8_t *prev_text, const rd_fq_summary *prev, int32_t final, int32_t *line_end,
                    int64_t cap_lines, rd_fq_summary *summary, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!text || !line_end || !summary || !workspace) RD_FAIL(RD_E_INVALID, "rd_fastq_index: null pointer");
-    if (pad < 0 || end < pad || end >= 0x7fffffffLL - 64 || cap_lines < 0) RD_FAIL(RD_E_INVALID, "rd_fastq_index: bad pad / end / cap_lines (a batch buffer is < 2 GiB)");
-    if ((prev == nullptr) != (prev_text == nullptr)) RD_FAIL(RD_E_INVALID, "rd_fastq_index: prev and prev_text go together");
-    if (((uintptr_t)text & 63) || ((uintptr_t)workspace & 255)) RD_FAIL(RD_E_INVALID, "rd_fastq_index: text must be 64-byte aligned, workspace 256-byte aligned");
-    const FqPlan p = fq_plan(end);
+    if (const int rc = fq_index_check("rd_fastq_index", text, pad, end, prev_text, prev, line_end, cap_lines, summary, workspace, false, false, nullptr)) return rc;
+    const FqWs p = fq_ws(workspace, end);
     if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "rd_fastq_index: workspace too small: %zu < %zu", workspace_bytes, p.total);
     hipStream_t st = (hipStream_t)stream;
-    uint32_t *tiles = (uint32_t *)workspace;
     FqSummary *sum = (FqSummary *)summary;
-    hipLaunchKernelGGL(rd_fq_begin_kernel, dim3(1), dim3(FQ_THREADS), 0, st, text, pad, end, prev_text, (const FqSummary *)prev, (int)final, sum);
-    hipLaunchKernelGGL(rd_fq_count_kernel, dim3(p.ntiles), dim3(FQ_THREADS), 0, st, text, sum, tiles);
-    hipLaunchKernelGGL(rd_fq_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, st, tiles, p.ntiles, sum, cap_lines);
-    hipLaunchKernelGGL(rd_fq_fill_kernel, dim3(p.ntiles), dim3(FQ_THREADS), 0, st, text, sum, tiles, line_end);
+    fq_line_table(text, pad, end, prev_text, prev, final, line_end, cap_lines, sum, p, st);
     int grid = (int)((end - pad) / (64 * FQ_THREADS)) + 1;      // one thread per ~64 bytes of new text is more than one per record
     if (grid > 2048) grid = 2048;
     hipLaunchKernelGGL(rd_fq_check_kernel, dim3(grid), dim3(FQ_THREADS), 0, st, text, line_end, sum, (int)final);
@@ -856,28 +861,12 @@ int rd_fastq_index(uint8_t *text, int64_t pad, int64_t end, const uint8_t *prev_
 int rd_fastq_gather(const uint8_t *text, const int32_t *line_end, const rd_fq_summary *summary, int64_t rec_lo, int64_t rec_hi, int64_t max_bytes,
                     uint8_t *out_text, int64_t out_cap, const int64_t *cursor_in, int64_t *cursor_out, int64_t *rec_start, int64_t *seq_off,
                     int32_t *seq_len, void *stream) {
-    if (!text || !line_end || !summary || !out_text || !cursor_in || !cursor_out || !rec_start || !seq_off || !seq_len)
-        RD_FAIL(RD_E_INVALID, "rd_fastq_gather: null pointer");
-    if (rec_lo < 0 || rec_hi < rec_lo || max_bytes < 0 || out_cap < 0 || cursor_in == cursor_out) RD_FAIL(RD_E_INVALID, "rd_fastq_gather: bad range");
-    if ((uintptr_t)out_text & 15) RD_FAIL(RD_E_INVALID, "rd_fastq_gather: out_text must be 16-byte aligned");
-    int64_t grid = max_bytes / (16 * FQ_THREADS * 4) + 1;       // four 16-byte pieces per thread
-    const int64_t grid_r = (rec_hi - rec_lo) / FQ_THREADS + 1;
-    if (grid < grid_r) grid = grid_r;
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(rd_fq_gather_kernel, dim3((unsigned)grid), dim3(FQ_THREADS), 0, (hipStream_t)stream, text, line_end, (const FqSummary *)summary, rec_lo,
-                       rec_hi, out_text, out_cap, cursor_in, cursor_out, rec_start, seq_off, seq_len);
-    RD_HIP(hipGetLastError());
-    return RD_OK;
+    return fq_gather("rd_fastq_gather", rd_fq_gather_kernel, summary, rec_lo, rec_hi, max_bytes, out_text, out_cap, cursor_in, cursor_out, rec_start, seq_off, seq_len,
+                     stream, text, line_end);
 }
 
 int rd_fastq_sample(const int32_t *line_end, const rd_fq_summary *summary, int64_t every, int32_t *samples, int64_t cap, void *stream) {
-    if (!line_end || !summary || !samples || every < 1 || cap < 0) RD_FAIL(RD_E_INVALID, "rd_fastq_sample: bad argument");
-    if (cap == 0) return RD_OK;
-    int64_t grid = cap / FQ_THREADS + 1;
-    if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(rd_fq_sample_kernel, dim3((unsigned)grid), dim3(FQ_THREADS), 0, (hipStream_t)stream, line_end, (const FqSummary *)summary, every, samples, cap);
-    RD_HIP(hipGetLastError());
-    return RD_OK;
+    return fq_sample("rd_fastq_sample", rd_fq_sample_kernel, line_end, summary, every, samples, cap, stream);
 }
 
 int rd_fastq_strip_mark(const uint8_t *text, const int32_t *line_end, const rd_fq_summary *summary, int64_t max_lines, uint8_t *del, void *stream) {
@@ -891,36 +880,24 @@ int rd_fastq_strip_mark(const uint8_t *text, const int32_t *line_end, const rd_f
 
 size_t rd_fasta_index_workspace_bytes(int64_t text_end, int64_t cap_lines) {
     if (text_end < 0 || text_end >= 0x7fffffffLL || cap_lines < 0) return 0;
-    return fa_plan(text_end, cap_lines).total;
+    return fa_ws(nullptr, text_end, cap_lines).total;
 }
 
 int rd_fasta_index(uint8_t *text, int64_t pad, int64_t end, const uint8_t *prev_text, const rd_fq_summary *prev, int32_t final, int32_t *line_end,
                    int64_t cap_lines, uint8_t *norm, int64_t norm_cap, int64_t *rec_tab, int32_t *hdr_tab, int64_t cap_records, rd_fq_summary *summary,
                    void *workspace, size_t workspace_bytes, void *stream) {
-    if (!text || !line_end || !norm || !rec_tab || !hdr_tab || !summary || !workspace) RD_FAIL(RD_E_INVALID, "rd_fasta_index: null pointer");
-    if (pad < 0 || end < pad || end >= 0x7fffffffLL - 64 || cap_lines < 0 || norm_cap < 0 || cap_records < 1)
-        RD_FAIL(RD_E_INVALID, "rd_fasta_index: bad pad / end / cap_lines / norm_cap / cap_records (a batch buffer is < 2 GiB)");
-    if ((prev == nullptr) != (prev_text == nullptr)) RD_FAIL(RD_E_INVALID, "rd_fasta_index: prev and prev_text go together");
-    if (((uintptr_t)text & 63) || ((uintptr_t)workspace & 255) || ((uintptr_t)norm & 15))
-        RD_FAIL(RD_E_INVALID, "rd_fasta_index: text must be 64-byte aligned, workspace 256-byte aligned, norm 16-byte aligned");
-    const FaPlan p = fa_plan(end, cap_lines);
+    if (const int rc = fq_index_check("rd_fasta_index", text, pad, end, prev_text, prev, line_end, cap_lines, summary, workspace, !norm || !rec_tab || !hdr_tab,
+                                      norm_cap < 0 || cap_records < 1, norm))
+        return rc;
+    const FaWs p = fa_ws(workspace, end, cap_lines);
     if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "rd_fasta_index: workspace too small: %zu < %zu", workspace_bytes, p.total);
     hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    uint32_t *tiles = (uint32_t *)ws;
-    int32_t *info_a = (int32_t *)(ws + p.a_off);
-    uint32_t *info_k = (uint32_t *)(ws + p.k_off);
-    unsigned long long *blk = (unsigned long long *)(ws + p.blk_off);
-    FaScratch *sc = (FaScratch *)(ws + p.sc_off);
     FqSummary *sum = (FqSummary *)summary;
-    hipLaunchKernelGGL(rd_fq_begin_kernel, dim3(1), dim3(FQ_THREADS), 0, st, text, pad, end, prev_text, (const FqSummary *)prev, (int)final, sum);
-    hipLaunchKernelGGL(rd_fq_count_kernel, dim3(p.fq.ntiles), dim3(FQ_THREADS), 0, st, text, sum, tiles);
-    hipLaunchKernelGGL(rd_fq_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, st, tiles, p.fq.ntiles, sum, cap_lines);
-    hipLaunchKernelGGL(rd_fq_fill_kernel, dim3(p.fq.ntiles), dim3(FQ_THREADS), 0, st, text, sum, tiles, line_end);
-    hipLaunchKernelGGL(rd_fa_init_kernel, dim3(1), dim3(FQ_THREADS), 0, st, sc);
-    hipLaunchKernelGGL(rd_fa_lines_kernel, dim3(p.nblk), dim3(FQ_THREADS), 0, st, text, line_end, sum, info_a, info_k, blk, sc);
-    hipLaunchKernelGGL(rd_fa_base_kernel, dim3(1), dim3(FQ_THREADS), 0, st, blk, line_end, sum, sc, (int)final, norm_cap, cap_records, norm, rec_tab, hdr_tab);
-    hipLaunchKernelGGL(rd_fa_emit_kernel, dim3(p.nblk), dim3(FQ_THREADS), 0, st, text, info_a, info_k, blk, sum, sc, (int)final, norm, rec_tab, hdr_tab);
+    fq_line_table(text, pad, end, prev_text, prev, final, line_end, cap_lines, sum, p.fq, st);
+    hipLaunchKernelGGL(rd_fa_init_kernel, dim3(1), dim3(FQ_THREADS), 0, st, p.sc);
+    hipLaunchKernelGGL(rd_fa_lines_kernel, dim3(p.nblk), dim3(FQ_THREADS), 0, st, text, line_end, sum, p.info_a, p.info_k, p.blk, p.sc);
+    hipLaunchKernelGGL(rd_fa_base_kernel, dim3(1), dim3(FQ_THREADS), 0, st, p.blk, line_end, sum, p.sc, (int)final, norm_cap, cap_records, norm, rec_tab, hdr_tab);
+    hipLaunchKernelGGL(rd_fa_emit_kernel, dim3(p.nblk), dim3(FQ_THREADS), 0, st, text, p.info_a, p.info_k, p.blk, sum, p.sc, (int)final, norm, rec_tab, hdr_tab);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }
@@ -928,83 +905,39 @@ int rd_fasta_index(uint8_t *text, int64_t pad, int64_t end, const uint8_t *prev_
 int rd_fasta_gather(const uint8_t *norm, const int64_t *rec_tab, const int32_t *hdr_tab, const rd_fq_summary *summary, int64_t rec_lo, int64_t rec_hi,
                     int64_t max_bytes, uint8_t *out_text, int64_t out_cap, const int64_t *cursor_in, int64_t *cursor_out, int64_t *rec_start,
                     int64_t *seq_off, int32_t *seq_len, void *stream) {
-    if (!norm || !rec_tab || !hdr_tab || !summary || !out_text || !cursor_in || !cursor_out || !rec_start || !seq_off || !seq_len)
-        RD_FAIL(RD_E_INVALID, "rd_fasta_gather: null pointer");
-    if (rec_lo < 0 || rec_hi < rec_lo || max_bytes < 0 || out_cap < 0 || cursor_in == cursor_out) RD_FAIL(RD_E_INVALID, "rd_fasta_gather: bad range");
-    if ((uintptr_t)out_text & 15) RD_FAIL(RD_E_INVALID, "rd_fasta_gather: out_text must be 16-byte aligned");
-    int64_t grid = max_bytes / (16 * FQ_THREADS * 4) + 1;
-    const int64_t grid_r = (rec_hi - rec_lo) / FQ_THREADS + 1;
-    if (grid < grid_r) grid = grid_r;
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(rd_fa_gather_kernel, dim3((unsigned)grid), dim3(FQ_THREADS), 0, (hipStream_t)stream, norm, rec_tab, hdr_tab, (const FqSummary *)summary,
-                       rec_lo, rec_hi, out_text, out_cap, cursor_in, cursor_out, rec_start, seq_off, seq_len);
-    RD_HIP(hipGetLastError());
-    return RD_OK;
+    return fq_gather("rd_fasta_gather", rd_fa_gather_kernel, summary, rec_lo, rec_hi, max_bytes, out_text, out_cap, cursor_in, cursor_out, rec_start, seq_off, seq_len,
+                     stream, norm, rec_tab, hdr_tab);
 }
 
 int rd_fasta_sample(const int64_t *rec_tab, const rd_fq_summary *summary, int64_t every, int32_t *samples, int64_t cap, void *stream) {
-    if (!rec_tab || !summary || !samples || every < 1 || cap < 0) RD_FAIL(RD_E_INVALID, "rd_fasta_sample: bad argument");
-    if (cap == 0) return RD_OK;
-    int64_t grid = cap / FQ_THREADS + 1;
-    if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(rd_fa_sample_kernel, dim3((unsigned)grid), dim3(FQ_THREADS), 0, (hipStream_t)stream, rec_tab, (const FqSummary *)summary, every, samples, cap);
-    RD_HIP(hipGetLastError());
-    return RD_OK;
-}
-
-// the selected records of a chunk as one contiguous text (the selection scan and the pack kernel of the device gzip, without the deflate)
-size_t rd_select_workspace_bytes(int64_t n) {
-    if (n < 0) return 0;
-    const GzPlan p = gz_plan(n, 0);
-    return p.off_bytes + p.bsum_bytes;
-}
-
-int rd_select_pack(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int8_t *labels, int64_t n, int32_t label, uint8_t *out,
-                   size_t out_cap, int64_t *info, void *workspace, size_t workspace_bytes, void *stream) {
-    if (n < 0 || n > 0x7fffffffLL || text_bytes < 0) RD_FAIL(RD_E_INVALID, "rd_select_pack: bad n or text_bytes");
-    if (!info) RD_FAIL(RD_E_INVALID, "rd_select_pack: null info");
-    if (label < -128 || label > 127) RD_FAIL(RD_E_INVALID, "rd_select_pack: label %d is not an int8 value", label);
-    hipStream_t st = (hipStream_t)stream;
-    if (n == 0) {
-        RD_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int64_t), st));
-        return RD_OK;
-    }
-    if ((!text && text_bytes > 0) || !rec_start || !labels || !out || !workspace) RD_FAIL(RD_E_INVALID, "rd_select_pack: null pointer");
-    if (((uintptr_t)workspace & 255) || ((uintptr_t)out & 15)) RD_FAIL(RD_E_INVALID, "rd_select_pack: workspace must be 256-byte aligned, out 16-byte aligned");
-    const GzPlan p = gz_plan(n, 0);
-    if (workspace_bytes < p.off_bytes + p.bsum_bytes) RD_FAIL(RD_E_WORKSPACE, "rd_select_pack: workspace too small: %zu < %zu", workspace_bytes, p.off_bytes + p.bsum_bytes);
-    int64_t *out_off = (int64_t *)workspace;
-    int64_t *bsum = (int64_t *)((char *)workspace + p.off_bytes);
-    const int64_t limit = text_bytes < (int64_t)out_cap ? text_bytes : (int64_t)out_cap;   // more selected bytes than text, or than `out` holds: info[3] = 1, nothing packed
-    hipLaunchKernelGGL(rd_gz_sel_sum_kernel, dim3(p.nb), dim3(256), 0, st, rec_start, labels, n, label, bsum);
-    hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, bsum, p.nb, info, limit);
-    hipLaunchKernelGGL(rd_gz_sel_off_kernel, dim3(p.nb), dim3(256), 0, st, rec_start, labels, n, label, bsum, out_off);
-    hipLaunchKernelGGL(rd_gz_pack_kernel, dim3((unsigned)((n + GZ_PACK_RECS - 1) / GZ_PACK_RECS)), dim3(256), 0, st, text, rec_start, out_off, n, out, info);
-    RD_HIP(hipGetLastError());
-    return RD_OK;
+    return fq_sample("rd_fasta_sample", rd_fa_sample_kernel, rec_tab, summary, every, samples, cap, stream);
 }
 
 // the per-read report of a chunk (rd_report.hpp): one line per record, and the lines' starts as a record table of the report text
 namespace {
-struct ReportPlan {
+struct ReportWs {
     int nb;
-    size_t idlen_bytes, q_bytes, bsum_bytes, fault_bytes, total;
+    int32_t *idlen, *fault;
+    uint64_t *qs;
+    int64_t *bsum;
+    size_t total;
 };
-ReportPlan report_plan(int64_t n) {
-    ReportPlan p;
+ReportWs report_ws(void *workspace, int64_t n) {
+    ReportWs p;
+    Carver c(workspace);
     p.nb = (int)((n + 1 + GZ_SCAN_ITEMS - 1) / GZ_SCAN_ITEMS);
-    p.idlen_bytes = align_up((size_t)n * 4, 256);
-    p.q_bytes = align_up((size_t)n * 8, 256);
-    p.bsum_bytes = align_up((size_t)p.nb * 8, 256);
-    p.fault_bytes = 256;
-    p.total = p.idlen_bytes + p.q_bytes + p.bsum_bytes + p.fault_bytes;
+    p.idlen = c.take<int32_t>((size_t)n);
+    p.qs = c.take<uint64_t>((size_t)n);
+    p.bsum = c.take<int64_t>((size_t)p.nb);
+    p.fault = c.take<int32_t>(1);
+    p.total = c.off;
     return p;
 }
 }  // namespace
 
 size_t rd_report_workspace_bytes(int64_t n) {
     if (n < 0) return 0;
-    return report_plan(n).total;
+    return report_ws(nullptr, n).total;
 }
 
 size_t rd_report_out_bound(int64_t n, int64_t text_bytes) {
@@ -1025,18 +958,13 @@ int rd_report_format(const uint8_t *text, int64_t text_bytes, const int64_t *rec
     }
     if ((!text && text_bytes > 0) || !rec_start || !logits_a || !labels || !out || !workspace) RD_FAIL(RD_E_INVALID, "rd_report_format: null pointer");
     if (((uintptr_t)workspace & 255) || ((uintptr_t)out & 15)) RD_FAIL(RD_E_INVALID, "rd_report_format: workspace must be 256-byte aligned, out 16-byte aligned");
-    const ReportPlan p = report_plan(n);
+    const ReportWs p = report_ws(workspace, n);
     if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "rd_report_format: workspace too small: %zu < %zu", workspace_bytes, p.total);
-    char *w = (char *)workspace;
-    int32_t *idlen = (int32_t *)w; w += p.idlen_bytes;
-    uint64_t *qs = (uint64_t *)w; w += p.q_bytes;
-    int64_t *bsum = (int64_t *)w; w += p.bsum_bytes;
-    int32_t *fault = (int32_t *)w;
-    RD_HIP(hipMemsetAsync(fault, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(rd_report_len_kernel, dim3(p.nb), dim3(256), 0, st, text, text_bytes, rec_start, n, logits_a, logits_b, labels, line_start, idlen, qs, bsum, fault);
-    hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, bsum, p.nb, info, (int64_t)(out_cap < (size_t)INT64_MAX ? out_cap : (size_t)INT64_MAX));
-    hipLaunchKernelGGL(rd_report_off_kernel, dim3(p.nb), dim3(256), 0, st, line_start, n, bsum, fault, info);
-    hipLaunchKernelGGL(rd_report_write_kernel, dim3((unsigned)((n + RP_LINES - 1) / RP_LINES)), dim3(256), 0, st, text, rec_start, line_start, n, idlen, qs, labels,
+    RD_HIP(hipMemsetAsync(p.fault, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(rd_report_len_kernel, dim3(p.nb), dim3(256), 0, st, text, text_bytes, rec_start, n, logits_a, logits_b, labels, line_start, p.idlen, p.qs, p.bsum, p.fault);
+    hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, p.bsum, p.nb, info, (int64_t)(out_cap < (size_t)INT64_MAX ? out_cap : (size_t)INT64_MAX));
+    hipLaunchKernelGGL(rd_report_off_kernel, dim3(p.nb), dim3(256), 0, st, line_start, n, p.bsum, p.fault, info);
+    hipLaunchKernelGGL(rd_report_write_kernel, dim3((unsigned)((n + RP_LINES - 1) / RP_LINES)), dim3(256), 0, st, text, rec_start, line_start, n, p.idlen, p.qs, labels,
                        logits_b ? 3 : 1, out, info);
     RD_HIP(hipGetLastError());
     return RD_OK;

@@ -279,22 +279,26 @@ __global__ __launch_bounds__(256) void rd_bucket_scatter_kernel(const int32_t *_
 // ------------------------------------------------------------------------------------------------
 // host helpers
 // ------------------------------------------------------------------------------------------------
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-struct SortPlan {
+// the workspace of both users below (one layout: steps / pfx at the tail belong to run_steps_and_buckets)
+struct SortWs {
     int nblk;
-    size_t hist_bytes, order_bytes, lenstart_bytes, steps_bytes, pfx_bytes, total;
+    uint32_t *hist;
+    int64_t *len_start;             // len_start + cum scratch
+    int32_t *order, *steps, *pfx;   // pfx: table row per read (rd_steps_kernel)
+    size_t total;
 };
-inline SortPlan sort_plan(int64_t n, int max_len) {
-    SortPlan p;
+inline SortWs sort_ws(void *workspace, int64_t n, int max_len) {
+    SortWs p;
+    Carver c(workspace);
     p.nblk = (int)((n + SORT_ITEMS - 1) / SORT_ITEMS);
     if (p.nblk < 1) p.nblk = 1;
-    p.hist_bytes = align_up((size_t)(max_len + 1) * p.nblk * sizeof(uint32_t), 256);
-    p.order_bytes = align_up((size_t)(n > 0 ? n : 1) * sizeof(int32_t), 256);
-    p.lenstart_bytes = align_up((size_t)(max_len + 1) * sizeof(int64_t) * 2, 256);   // len_start + cum scratch
-    p.steps_bytes = align_up((size_t)(n > 0 ? n : 1) * sizeof(int32_t), 256);
-    p.pfx_bytes = p.steps_bytes;                                                      // table row per read (rd_steps_kernel)
-    p.total = p.hist_bytes + p.order_bytes + p.lenstart_bytes + p.steps_bytes + p.pfx_bytes;
+    const size_t n1 = (size_t)(n > 0 ? n : 1);
+    p.hist = c.take<uint32_t>((size_t)(max_len + 1) * p.nblk);
+    p.order = c.take<int32_t>(n1);
+    p.len_start = c.take<int64_t>((size_t)(max_len + 1) * 2);
+    p.steps = c.take<int32_t>(n1);
+    p.pfx = c.take<int32_t>(n1);
+    p.total = c.off;
     return p;
 }
 
@@ -303,12 +307,11 @@ constexpr int MAX_LEN_LIMIT = 16000;   // LDS histogram of max_len+1 uint32 must
 int run_sort(const int32_t *seq_len, int64_t n, int max_len, void *workspace, size_t wbytes, int32_t *&order,
              int64_t *sorted_idx, int64_t *unsorted_idx, int64_t *batch_sizes, int64_t *total_steps, int64_t *&len_start,
              hipStream_t st) {
-    SortPlan p = sort_plan(n, max_len);
+    const SortWs p = sort_ws(workspace, n, max_len);
     if (wbytes < p.total) RD_FAIL(RD_E_WORKSPACE, "workspace too small: %zu < %zu", wbytes, p.total);
-    char *w = (char *)workspace;
-    uint32_t *hist = (uint32_t *)w;
-    order = (int32_t *)(w + p.hist_bytes);
-    len_start = (int64_t *)(w + p.hist_bytes + p.order_bytes);
+    uint32_t *hist = p.hist;
+    order = p.order;
+    len_start = p.len_start;
     const size_t sh = (size_t)(max_len + 1) * sizeof(uint32_t);
     hipLaunchKernelGGL(rd_len_hist_kernel, dim3(p.nblk), dim3(SORT_BLOCK), sh, st, seq_len, n, max_len, p.nblk, hist);
     uint32_t *row_total = (uint32_t *)(len_start + (max_len + 1));              // second half of the lenstart area
@@ -324,14 +327,13 @@ int run_sort(const int32_t *seq_len, int64_t n, int max_len, void *workspace, si
 // steps[] + order[] for rd_classify: steps kernel (with histogram) -> bucket starts -> scatter
 int run_steps_and_buckets(const uint8_t *arena, const int64_t *seq_off, const int32_t *seq_len, int64_t n, int max_len, int sem,
                           void *workspace, size_t wbytes, int32_t *&steps, int32_t *&order, int pk, int32_t *&pfx, hipStream_t st) {
-    SortPlan p = sort_plan(n, max_len);
+    const SortWs p = sort_ws(workspace, n, max_len);
     if (wbytes < p.total) RD_FAIL(RD_E_WORKSPACE, "workspace too small: %zu < %zu", wbytes, p.total);
-    char *w = (char *)workspace;
-    uint32_t *ghist = (uint32_t *)w;                                          // (max_len+1) u32 fit in hist_bytes
-    order = (int32_t *)(w + p.hist_bytes);
-    uint32_t *cursor = (uint32_t *)(w + p.hist_bytes + p.order_bytes);        // (max_len+1) u32 fit in lenstart_bytes
-    steps = (int32_t *)(w + p.total - p.pfx_bytes - p.steps_bytes);
-    pfx = pk > 0 ? (int32_t *)(w + p.total - p.pfx_bytes) : nullptr;
+    uint32_t *ghist = p.hist;                           // (max_len+1) u32 fit in the histogram area
+    order = p.order;
+    uint32_t *cursor = (uint32_t *)p.len_start;         // (max_len+1) u32 fit in the len_start area
+    steps = p.steps;
+    pfx = pk > 0 ? p.pfx : nullptr;
     const size_t sh = (size_t)(max_len + 1) * sizeof(uint32_t);
     RD_HIP(hipMemsetAsync(ghist, 0, sh, st));
     // one workgroup per CU at most: every workgroup ends with one global atomic per non-empty bin, and with fixed-length

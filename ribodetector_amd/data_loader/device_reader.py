@@ -150,6 +150,20 @@ class FastqIndexer:
         with torch.cuda.stream(self.stream):
             return torch.empty(((PAD + int(new_bytes) + 64 + 127) // 64) * 64, dtype=torch.uint8, device=self.device)
 
+    line_div = LINE_DIV
+
+    def _n_samples(self, window, cap_lines):
+        """the record-offset samples a batch of `window` bytes can need (the meta buffer is sized before the hook below runs)"""
+        return window // (4 * EVERY) + 3
+
+    def _frame(self, b, start, end, prev, final, window, cap_lines, ns):
+        """the hook of index(): the format's own tables, and the calls that frame the batch and sample its record offsets.
+        prev: the device pointers of (text, summary) of the batch it chains to, or (None, None)"""
+        ws = torch.empty(max(int(self.lib.rd_fastq_index_workspace_bytes(end)), 256), dtype=torch.uint8, device=self.device)
+        N.check(self.lib.rd_fastq_index(N.ptr(b.text), start, end, prev[0], prev[1], 1 if final else 0, N.ptr(b.line_end), cap_lines, N.ptr(b.summary), N.ptr(ws),
+                                        ws.numel(), self._sp()), "rd_fastq_index")
+        N.check(self.lib.rd_fastq_sample(N.ptr(b.line_end), N.ptr(b.summary), EVERY, N.ptr(b.samples), ns, self._sp()), "rd_fastq_sample")
+
     def index(self, text, start, end, final=False, chain=True, prev=None, full_table=False, pad=None):
         """frame text[start:end] (offsets in the batch buffer; start >= PAD unless the batch stands alone) behind the carry of the
         batch indexed before (chain) or of an explicit `prev` = (text, summary). pad: the room in front of `start` when it is not PAD (a
@@ -163,20 +177,17 @@ class FastqIndexer:
             window = (end - start) + ((PAD if pad is None else pad) if prev is not None else 0)
             if window >= 0x7fffffff - 4096:
                 raise ValueError(FQ_ERRORS[3])
+            cap_lines = (window + 2) if full_table else (window // self.line_div + 4096)
             b.text = text
-            b.line_end = torch.empty((window + 2) if full_table else (window // LINE_DIV + 4096), dtype=torch.int32, device=self.device)
+            b.line_end = torch.empty(cap_lines, dtype=torch.int32, device=self.device)
             # what travels to the host: the 64-byte summary and the record-offset samples, in ONE buffer, fetched by a kernel
             # (rd_copy_bytes: an SDMA queue is shared in order with copies that wait for kernels)
-            ns = window // (4 * EVERY) + 3
+            ns = self._n_samples(window, cap_lines)
             meta = torch.empty(64 + 4 * ns, dtype=torch.uint8, device=self.device)
             meta_host = torch.empty(64 + 4 * ns, dtype=torch.uint8, pin_memory=True)
             b.summary, b.samples = meta[:64].view(torch.int64), meta[64:].view(torch.int32)
             b.host, b.samples_host = meta_host[:64].view(torch.int64), meta_host[64:].view(torch.int32)
-            ws = torch.empty(max(int(self.lib.rd_fastq_index_workspace_bytes(end)), 256), dtype=torch.uint8, device=self.device)
-            N.check(self.lib.rd_fastq_index(N.ptr(text), int(start), int(end), N.ptr(prev[0]) if prev is not None else None,
-                                            N.ptr(prev[1]) if prev is not None else None, 1 if final else 0, N.ptr(b.line_end),
-                                            b.line_end.numel(), N.ptr(b.summary), N.ptr(ws), ws.numel(), self._sp()), "rd_fastq_index")
-            N.check(self.lib.rd_fastq_sample(N.ptr(b.line_end), N.ptr(b.summary), EVERY, N.ptr(b.samples), ns, self._sp()), "rd_fastq_sample")
+            self._frame(b, int(start), int(end), (N.ptr(prev[0]), N.ptr(prev[1])) if prev is not None else (None, None), final, window, cap_lines, ns)
             N.copy_bytes(meta_host, meta, meta.numel(), self.stream, workgroups=4)
             b.event = N.new_event()
             b.event.record(self.stream)
@@ -241,16 +252,20 @@ class FastqIndexer:
         left to the caller (the records before the damage are delivered first)."""
         self.wait(b)
         self._read(b)
-        if b.status in (3, 4, 5) and b.chain is not None:
+        if b.status in (3, 4, 5) and b.chain is not None:    # tables or pad too small, or the batch chains to such a one
             self._reframe(b)
         if b.chain is not None:
             self.last_good = b.chain
             self.last_carry = (b.end - b.consumed) if b.status == 0 else 0
+        self._finish_tail(b)
+        return b
+
+    def _finish_tail(self, b):
+        """the hook of finish(): what the format adds once the batch's summary is known"""
         if b.dirty and b.status in (0, 2):       # (a truncated tail does not excuse the records in front of it from rstrip())
             self._strip(b)
         if b.status == 0 and b.bad_record != -1 and b.bad_record < b.n:
             b.status = 1
-        return b
 
     def _strip(self, b):
         """a batch with trailing whitespace on some line: the bytes rstrip() removes are marked, the window is compacted and indexed
@@ -274,6 +289,11 @@ class FastqIndexer:
             setattr(b, k, getattr(nb, k))
         b.dirty = 0
 
+    def _gather_piece(self, b, lo, hi, *out):
+        """the hook of gather(): records [lo, hi) of batch b appended to the chunk (out: max_bytes, the chunk's text and its size, the
+        cursor in and out, where the piece's rec_start / seq_off / seq_len go, the stream)"""
+        N.check(self.lib.rd_fastq_gather(N.ptr(b.text), N.ptr(b.line_end), N.ptr(b.summary), lo, hi, *out), "rd_fastq_gather")
+
     def gather(self, pieces):
         """pieces: [(batch, lo, hi)] -> DeviceChunk of sum(hi - lo) records, in that order"""
         n = sum(hi - lo for _, lo, hi in pieces)
@@ -286,10 +306,9 @@ class FastqIndexer:
             cursor = torch.zeros(len(pieces) + 1, dtype=torch.int64, device=self.device)
             at = 0
             for i, (b, lo, hi) in enumerate(pieces):
-                N.check(self.lib.rd_fastq_gather(N.ptr(b.text), N.ptr(b.line_end), N.ptr(b.summary), lo, hi, b.bytes_bound(lo, hi), N.ptr(text),
-                                                 text.numel(), C.c_void_p(cursor.data_ptr() + 8 * i), C.c_void_p(cursor.data_ptr() + 8 * (i + 1)),
-                                                 C.c_void_p(rs.data_ptr() + 8 * at), C.c_void_p(so.data_ptr() + 8 * at),
-                                                 C.c_void_p(sl.data_ptr() + 4 * at), self._sp()), "rd_fastq_gather")
+                self._gather_piece(b, lo, hi, b.bytes_bound(lo, hi), N.ptr(text), text.numel(), C.c_void_p(cursor.data_ptr() + 8 * i),
+                                   C.c_void_p(cursor.data_ptr() + 8 * (i + 1)), C.c_void_p(rs.data_ptr() + 8 * at), C.c_void_p(so.data_ptr() + 8 * at),
+                                   C.c_void_p(sl.data_ptr() + 4 * at), self._sp())
                 at += hi - lo
             total = torch.empty(1, dtype=torch.int64, pin_memory=True)
             N.copy_bytes(total.view(torch.uint8), cursor[len(pieces):].view(torch.uint8), 8, self.stream, workgroups=1)
@@ -311,82 +330,33 @@ class FastaIndexer(FastqIndexer):
 
     _REFRAMED = FastqIndexer._REFRAMED + ("norm", "rec_tab", "hdr_tab", "norm_end")
 
-    def index(self, text, start, end, final=False, chain=True, prev=None, full_table=False, pad=None):
-        b = _Batch()
-        if prev is None and chain:
-            with self._lock:
-                prev = self.prev
-        full_table = full_table or (chain and self.full_tables)
-        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
-            window = (end - start) + ((PAD if pad is None else pad) if prev is not None else 0)
-            if window >= 0x7fffffff - 4096:
-                raise ValueError(FQ_ERRORS[3])
-            cap_lines = (window + 2) if full_table else (window // LINE_DIV_FA + 4096)
-            cap_rec = cap_lines + 2
-            norm_cap = ((window + cap_lines + 66 + 255) // 256) * 256
-            b.text = text
-            b.line_end = torch.empty(cap_lines, dtype=torch.int32, device=self.device)
-            b.norm = torch.empty(norm_cap, dtype=torch.uint8, device=self.device)
-            b.rec_tab = torch.empty(cap_rec, dtype=torch.int64, device=self.device)
-            b.hdr_tab = torch.empty(cap_rec, dtype=torch.int32, device=self.device)
-            ns = cap_rec // EVERY + 3
-            meta = torch.empty(64 + 4 * ns, dtype=torch.uint8, device=self.device)
-            meta_host = torch.empty(64 + 4 * ns, dtype=torch.uint8, pin_memory=True)
-            b.summary, b.samples = meta[:64].view(torch.int64), meta[64:].view(torch.int32)
-            b.host, b.samples_host = meta_host[:64].view(torch.int64), meta_host[64:].view(torch.int32)
-            ws = torch.empty(max(int(self.lib.rd_fasta_index_workspace_bytes(end, cap_lines)), 256), dtype=torch.uint8, device=self.device)
-            N.check(self.lib.rd_fasta_index(N.ptr(text), int(start), int(end), N.ptr(prev[0]) if prev is not None else None,
-                                            N.ptr(prev[1]) if prev is not None else None, (2 if self.keep_empty_tail else 1) if final else 0,
-                                            N.ptr(b.line_end), cap_lines, N.ptr(b.norm), norm_cap, N.ptr(b.rec_tab), N.ptr(b.hdr_tab), cap_rec, N.ptr(b.summary), N.ptr(ws),
-                                            ws.numel(), self._sp()), "rd_fasta_index")
-            N.check(self.lib.rd_fasta_sample(N.ptr(b.rec_tab), N.ptr(b.summary), EVERY, N.ptr(b.samples), ns, self._sp()), "rd_fasta_sample")
-            N.copy_bytes(meta_host, meta, meta.numel(), self.stream, workgroups=4)
-            b.event = N.new_event()
-            b.event.record(self.stream)
-        b.final, b.orig, b.slot, b.gz_slot, b.n = final, None, None, None, None
-        b.args, b.chain = (start, end, final), (text, b.summary)
-        if chain:
-            with self._lock:
-                self.prev = b.chain
-        self.stats["batches"] += 1
-        return b
+    line_div = LINE_DIV_FA
+
+    def _n_samples(self, window, cap_lines):
+        return (cap_lines + 2) // EVERY + 3
+
+    def _frame(self, b, start, end, prev, final, window, cap_lines, ns):
+        cap_rec = cap_lines + 2
+        norm_cap = ((window + cap_lines + 66 + 255) // 256) * 256
+        b.norm = torch.empty(norm_cap, dtype=torch.uint8, device=self.device)
+        b.rec_tab = torch.empty(cap_rec, dtype=torch.int64, device=self.device)
+        b.hdr_tab = torch.empty(cap_rec, dtype=torch.int32, device=self.device)
+        ws = torch.empty(max(int(self.lib.rd_fasta_index_workspace_bytes(end, cap_lines)), 256), dtype=torch.uint8, device=self.device)
+        N.check(self.lib.rd_fasta_index(N.ptr(b.text), start, end, prev[0], prev[1], (2 if self.keep_empty_tail else 1) if final else 0, N.ptr(b.line_end), cap_lines,
+                                        N.ptr(b.norm), norm_cap, N.ptr(b.rec_tab), N.ptr(b.hdr_tab), cap_rec, N.ptr(b.summary), N.ptr(ws), ws.numel(), self._sp()),
+                "rd_fasta_index")
+        N.check(self.lib.rd_fasta_sample(N.ptr(b.rec_tab), N.ptr(b.summary), EVERY, N.ptr(b.samples), ns, self._sp()), "rd_fasta_sample")
 
     @staticmethod
     def _read(b):
         FastqIndexer._read(b)
         b.norm_end = int(b.host.numpy()[7])
 
-    def finish(self, b):
-        self.wait(b)
-        self._read(b)
-        if b.status in (3, 4, 5) and b.chain is not None:    # (as FastqIndexer.finish: tables or pad too small, or the batch chains to such a one)
-            self._reframe(b)
-        if b.chain is not None:
-            self.last_good = b.chain
-            self.last_carry = (b.end - b.consumed) if b.status == 0 else 0
-        return b
+    def _finish_tail(self, b):
+        pass                  # (no strip pass, no bad-record index: both are part of the re-writing)
 
-    def gather(self, pieces):
-        n = sum(hi - lo for _, lo, hi in pieces)
-        cap = sum(b.bytes_bound(lo, hi) for b, lo, hi in pieces)
-        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
-            text = torch.empty(((cap + 255) // 256) * 256 + 256, dtype=torch.uint8, device=self.device)
-            rs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-            so = torch.empty(n, dtype=torch.int64, device=self.device)
-            sl = torch.empty(n, dtype=torch.int32, device=self.device)
-            cursor = torch.zeros(len(pieces) + 1, dtype=torch.int64, device=self.device)
-            at = 0
-            for i, (b, lo, hi) in enumerate(pieces):
-                N.check(self.lib.rd_fasta_gather(N.ptr(b.norm), N.ptr(b.rec_tab), N.ptr(b.hdr_tab), N.ptr(b.summary), lo, hi, b.bytes_bound(lo, hi),
-                                                 N.ptr(text), text.numel(), C.c_void_p(cursor.data_ptr() + 8 * i), C.c_void_p(cursor.data_ptr() + 8 * (i + 1)),
-                                                 C.c_void_p(rs.data_ptr() + 8 * at), C.c_void_p(so.data_ptr() + 8 * at),
-                                                 C.c_void_p(sl.data_ptr() + 4 * at), self._sp()), "rd_fasta_gather")
-                at += hi - lo
-            total = torch.empty(1, dtype=torch.int64, pin_memory=True)
-            N.copy_bytes(total.view(torch.uint8), cursor[len(pieces):].view(torch.uint8), 8, self.stream, workgroups=1)
-            ready = torch.cuda.Event()
-            ready.record(self.stream)
-        return DeviceChunk(n, text, rs, so, sl, ready, total)
+    def _gather_piece(self, b, lo, hi, *out):
+        N.check(self.lib.rd_fasta_gather(N.ptr(b.norm), N.ptr(b.rec_tab), N.ptr(b.hdr_tab), N.ptr(b.summary), lo, hi, *out), "rd_fasta_gather")
 
 
 class DeviceFeeder:

@@ -5,7 +5,9 @@ detect.py:729-741). Here the records of a chunk that carry one label are compres
 gzip members (BGZF framing), and only the compressed bytes travel to the host, which appends them to the file.
 """
 import ctypes as C
+import os
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -38,6 +40,26 @@ def release_stream(stream, priority=0):
         _stream_pool.setdefault((stream.device.index, priority), []).append(stream)
 
 
+def _grown(owner, key, need, make):
+    """the grow-only buffer owner[key] (a dict's entry, or the attribute `key` of any other owner): kept while it holds `need`
+    elements, else dropped FIRST - so that its block can serve the new one - and made again by make()"""
+    d = owner if isinstance(owner, dict) else owner.__dict__
+    buf = d.get(key)
+    if buf is None or buf.numel() < need:
+        d[key] = None
+        buf = d[key] = make()
+    return buf
+
+
+def _check_tables(who, text, rec_start, entries, n_entries, labels=None):
+    """the checks of a chunk's text, its record table of `n_entries` (spelled `entries` in the message) + 1 entries and, where the
+    method takes them, its labels; `who` names the method in the TypeError"""
+    if rec_start.dtype != torch.int64 or rec_start.numel() < n_entries + 1 or not rec_start.is_contiguous():
+        raise TypeError("%s: rec_start must be a contiguous int64 tensor of %s + 1 entries" % (who, entries))
+    if labels is not None and (labels.dtype not in (torch.int8, torch.uint8) or text.dtype != torch.uint8):
+        raise TypeError("%s: labels must be int8 / uint8 and text uint8" % who)
+
+
 def eof_block():
     """BGZF's 28-byte end-of-file marker (an empty gzip member); appended once when a device-written file is closed"""
     buf = (C.c_uint8 * 28)()
@@ -62,25 +84,17 @@ class DeviceGzip:
         lib = N.lib()
         n = int(labels.numel())
         tb = int(text.numel())
-        if rec_start.dtype != torch.int64 or rec_start.numel() < n + 1 or not rec_start.is_contiguous():
-            raise TypeError("compress_selected: rec_start must be a contiguous int64 tensor of n + 1 entries")
-        if labels.dtype not in (torch.int8, torch.uint8) or text.dtype != torch.uint8:
-            raise TypeError("compress_selected: labels must be int8 / uint8 and text uint8")
+        _check_tables("compress_selected", text, rec_start, "n", n, labels)
         need = int(lib.rd_gz_workspace_bytes(n, tb))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=self.device)
+        ws = _grown(self, "_ws", need, lambda: torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=self.device))
         # out_frac < 1: a smaller output buffer than the worst case (every member stored). FASTQ shrinks 4-6x, so half the bound is
         # plenty; if a chunk does not fit (info[0] > out.numel()) the stream in `out` is incomplete and the caller falls back
         cap = max(int(int(lib.rd_gz_out_bound(tb)) * float(out_frac)) + (1 << 20), 256) if out_frac < 1.0 else max(int(lib.rd_gz_out_bound(tb)), 256)
-        out = self._out.get(slot)
-        if out is None or out.numel() < cap:
-            self._out[slot] = None
-            out = self._out[slot] = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        out = _grown(self._out, slot, cap, lambda: torch.empty(cap, dtype=torch.uint8, device=self.device))
         info = torch.empty(4, dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
             N.check(lib.rd_gz_compress_selected(N.ptr(text), tb, N.ptr(rec_start), N.ptr(labels), n, int(label), N.ptr(out), out.numel(),
-                                                N.ptr(info), N.ptr(self._ws), self._ws.numel(), N.stream_ptr(self.device)),
+                                                N.ptr(info), N.ptr(ws), ws.numel(), N.stream_ptr(self.device)),
                     "rd_gz_compress_selected")
         return out, info
 
@@ -98,22 +112,14 @@ class DeviceSelect:
     def pack_selected(self, text, rec_start, labels, label, slot=0):
         lib = N.lib()
         n, tb = int(labels.numel()), int(text.numel())
-        if rec_start.dtype != torch.int64 or rec_start.numel() < n + 1 or not rec_start.is_contiguous():
-            raise TypeError("pack_selected: rec_start must be a contiguous int64 tensor of n + 1 entries")
-        if labels.dtype not in (torch.int8, torch.uint8) or text.dtype != torch.uint8:
-            raise TypeError("pack_selected: labels must be int8 / uint8 and text uint8")
+        _check_tables("pack_selected", text, rec_start, "n", n, labels)
         need = int(lib.rd_select_workspace_bytes(n))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=self.device)
-        out = self._out.get(slot)
-        if out is None or out.numel() < tb + 16:
-            self._out[slot] = None
-            out = self._out[slot] = torch.empty(tb + 256, dtype=torch.uint8, device=self.device)
+        ws = _grown(self, "_ws", need, lambda: torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=self.device))
+        out = _grown(self._out, slot, tb + 16, lambda: torch.empty(tb + 256, dtype=torch.uint8, device=self.device))
         info = torch.empty(4, dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
             N.check(lib.rd_select_pack(N.ptr(text), tb, N.ptr(rec_start), N.ptr(labels), n, int(label), N.ptr(out), out.numel(), N.ptr(info),
-                                       N.ptr(self._ws), self._ws.numel(), N.stream_ptr(self.device)), "rd_select_pack")
+                                       N.ptr(ws), ws.numel(), N.stream_ptr(self.device)), "rd_select_pack")
         return out, info
 
 
@@ -132,18 +138,14 @@ class DevicePairSplit:
 
     def split(self, text, rec_start, seq_off, seq_len, n_pairs, check_ids=True, slot=0):
         n, tb = int(n_pairs), int(text.numel())
-        if rec_start.dtype != torch.int64 or rec_start.numel() < 2 * n + 1 or not rec_start.is_contiguous():
-            raise TypeError("DevicePairSplit.split: rec_start must be a contiguous int64 tensor of 2 n + 1 entries")
+        _check_tables("DevicePairSplit.split", text, rec_start, "2 n", 2 * n)
         if (seq_off.dtype != torch.int64 or seq_len.dtype != torch.int32 or min(seq_off.numel(), seq_len.numel()) < 2 * n
                 or not seq_off.is_contiguous() or not seq_len.is_contiguous() or text.dtype != torch.uint8):
             raise TypeError("DevicePairSplit.split: seq_off int64[2 n], seq_len int32[2 n] (contiguous) and text uint8")
-        out = self._out.get(slot)
-        if out is None or out[0].numel() < n + 1:
-            self._out[slot] = None
-            cap = max(n + 1, 1024)
-            out = self._out[slot] = (torch.empty(cap, dtype=torch.int64, device=self.device),
-                                     torch.empty((2, cap), dtype=torch.int64, device=self.device), torch.empty((2, cap), dtype=torch.int32, device=self.device))
-        ps, so, sl = out
+        cap = max(n + 1, 1024)
+        ps = _grown(self._out, (slot, "pairs"), n + 1, lambda: torch.empty(cap, dtype=torch.int64, device=self.device))
+        so = _grown(self._out, (slot, "seq_off"), 2 * (n + 1), lambda: torch.empty((2, cap), dtype=torch.int64, device=self.device))
+        sl = _grown(self._out, (slot, "seq_len"), 2 * (n + 1), lambda: torch.empty((2, cap), dtype=torch.int32, device=self.device))
         info = torch.empty(4, dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
             N.check(N.lib().rd_pair_split(N.ptr(text), tb, N.ptr(rec_start), N.ptr(seq_off), N.ptr(seq_len), n, 1 if check_ids else 0, N.ptr(ps),
@@ -154,10 +156,7 @@ class DevicePairSplit:
         n = int(pair_labels.numel())
         if pair_labels.dtype not in (torch.int8, torch.uint8) or not pair_labels.is_contiguous():
             raise TypeError("DevicePairSplit.expand: pair_labels must be a contiguous int8 / uint8 tensor")
-        out = self._lab.get((slot, mate))
-        if out is None or out.numel() < 2 * n:
-            self._lab[(slot, mate)] = None
-            out = self._lab[(slot, mate)] = torch.empty(max(2 * n, 2048), dtype=torch.int8, device=self.device)
+        out = _grown(self._lab, (slot, mate), 2 * n, lambda: torch.empty(max(2 * n, 2048), dtype=torch.int8, device=self.device))
         with torch.cuda.device(self.device):
             N.check(N.lib().rd_pair_expand_labels(N.ptr(pair_labels), n, int(mate), N.ptr(out), N.stream_ptr(self.device)), "rd_pair_expand_labels")
         return out[:2 * n]
@@ -178,40 +177,28 @@ class DeviceReport:
     def __init__(self, device):
         self.device = torch.device(device)
         self._ws = None
-        self._out = {}
+        self._out, self._ls = {}, {}
         self._zeros = None
 
     def zeros(self, n):
-        if self._zeros is None or self._zeros.numel() < n:
-            self._zeros = None
-            self._zeros = torch.zeros(max(n, 1 << 16), dtype=torch.int8, device=self.device)
-        return self._zeros[:n]
+        return _grown(self, "_zeros", n, lambda: torch.zeros(max(n, 1 << 16), dtype=torch.int8, device=self.device))[:n]
 
     def format(self, text, rec_start, logits_a, logits_b, labels, slot=0):
         lib = N.lib()
         n, tb = int(labels.numel()), int(text.numel())
-        if rec_start.dtype != torch.int64 or rec_start.numel() < n + 1 or not rec_start.is_contiguous():
-            raise TypeError("DeviceReport.format: rec_start must be a contiguous int64 tensor of n + 1 entries")
-        if labels.dtype not in (torch.int8, torch.uint8) or text.dtype != torch.uint8:
-            raise TypeError("DeviceReport.format: labels must be int8 / uint8 and text uint8")
+        _check_tables("DeviceReport.format", text, rec_start, "n", n, labels)
         for lg in (logits_a, logits_b):
             if lg is not None and (lg.dtype != torch.float32 or not lg.is_contiguous() or lg.numel() < 2 * n):
                 raise TypeError("DeviceReport.format: logits must be contiguous fp32 [n, 2] tensors")
         need = int(lib.rd_report_workspace_bytes(n))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=self.device)
+        ws = _grown(self, "_ws", need, lambda: torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=self.device))
         cap = int(lib.rd_report_out_bound(n, tb))
-        out, ls = self._out.get(slot, (None, None))
-        if out is None or out.numel() < cap or ls.numel() < n + 1:
-            self._out[slot] = None
-            out = torch.empty(((cap + 255) // 256) * 256 + 256, dtype=torch.uint8, device=self.device)
-            ls = torch.empty(max(n + 1, 1024), dtype=torch.int64, device=self.device)
-            self._out[slot] = (out, ls)
+        out = _grown(self._out, slot, cap, lambda: torch.empty(((cap + 255) // 256) * 256 + 256, dtype=torch.uint8, device=self.device))
+        ls = _grown(self._ls, slot, n + 1, lambda: torch.empty(max(n + 1, 1024), dtype=torch.int64, device=self.device))
         info = torch.empty(4, dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
             N.check(lib.rd_report_format(N.ptr(text), tb, N.ptr(rec_start), n, N.ptr(logits_a), N.ptr(logits_b), N.ptr(labels), N.ptr(out), out.numel(),
-                                         N.ptr(ls), N.ptr(info), N.ptr(self._ws), self._ws.numel(), N.stream_ptr(self.device)), "rd_report_format")
+                                         N.ptr(ls), N.ptr(info), N.ptr(ws), ws.numel(), N.stream_ptr(self.device)), "rd_report_format")
         return out, ls[:n + 1], info
 
 
@@ -263,7 +250,6 @@ class DeviceGunzip:
     object's stream (high priority: it runs in the gaps between the recurrence launches), and finish() sleeps until it is done."""
 
     def __init__(self, device, slots=1, stream=None):
-        import numpy as np
         self.device = torch.device(device)
         if stream is not None:
             self.stream = stream
@@ -316,18 +302,13 @@ class DeviceGunzip:
         lib = N.lib()
         sl = self._slots[slot]
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
-            if sl.comp_dev is None or sl.comp_dev.numel() < nbytes + 16:
-                sl.comp_dev = None
-                sl.comp_dev = torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8, device=self.device)
+            _grown(sl, "comp_dev", nbytes + 16, lambda: torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8, device=self.device))
             if text_out is not None:
                 if text_out.numel() < out_bytes or text_out.dtype != torch.uint8 or not text_out.is_cuda:
                     raise ValueError("DeviceGunzip.submit: text_out must be a device uint8 tensor of at least out_bytes bytes")
                 text_dev = text_out
-            elif sl.text_dev is None or sl.text_dev.numel() < out_bytes:
-                sl.text_dev = None
-                sl.text_dev = torch.empty(int(out_bytes * 1.25) + 4096, dtype=torch.uint8, device=self.device)
-            if text_out is None:
-                text_dev = sl.text_dev
+            else:
+                text_dev = _grown(sl, "text_dev", out_bytes, lambda: torch.empty(int(out_bytes * 1.25) + 4096, dtype=torch.uint8, device=self.device))
             if sl.status is None or sl.status.numel() < n:
                 sl.status = torch.empty(max(n, 1024) * 2, dtype=torch.int32, device=self.device)
                 sl.status_host = torch.empty(max(n, 1024) * 2, dtype=torch.int32, pin_memory=True)
@@ -352,7 +333,6 @@ class DeviceGunzip:
     def finish(self, slot=0):
         """wait for the batch of `slot` (sleeping, not spinning: the host cores belong to readers and writers); ValueError names the
         first member that did not decode"""
-        import time
         sl = self._slots[slot]
         N.wait_event(sl.event)
         st = sl.status_host[: sl.n].numpy()
@@ -416,7 +396,6 @@ class DeviceStreamGunzip:
     TEXT_RATIO = 12             # text bytes a batch may produce per compressed byte
 
     def __init__(self, device, stream):
-        import os
         self.device, self.stream = torch.device(device), stream
         self.carry = self.win = None
         self._ws = None
@@ -426,36 +405,40 @@ class DeviceStreamGunzip:
     def text_cap(self, data_bytes):
         return int(data_bytes) * self.TEXT_RATIO + (1 << 20)
 
-    def submit(self, src, valid_bytes, data_bytes, first_start_bit, at_eof, text_out):
-        """src: pinned uint8 tensor holding valid_bytes bytes of the file from the batch's first byte; the sections cover
-        [0, data_bytes); text_out: device uint8 tensor that receives the text"""
+    def _submit(self, call, ws_bytes, src, valid_bytes, data_bytes, first_start_bit, at_eof, carried, carried_dtype, out):
+        """one batch through `call` (rd_gz_stream_inflate / rd_gz_range_decode, whose workspace `ws_bytes` sizes): the compressed bytes
+        staged in HBM, the call behind the state and `carried` (the window, or the map) of the batch before, the batch's 64-byte state
+        fetched, an event behind it all. Returns (ticket, what the batch leaves to carry)."""
         lib = N.lib()
         cap_syms = self.SECTION * self.CAP_RATIO
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             comp = torch.empty(((valid_bytes + 4096 + 255) // 256) * 256, dtype=torch.uint8, device=self.device)
             N.copy_bytes(comp, src, valid_bytes, self.stream)
             comp[valid_bytes:valid_bytes + 4096].zero_()
-            need = int(lib.rd_gz_stream_workspace_bytes(data_bytes, self.SECTION, cap_syms, text_out.numel()))
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = None
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            need = int(getattr(lib, ws_bytes)(data_bytes, self.SECTION, cap_syms, out.numel()))
+            ws = _grown(self, "_ws", need, lambda: torch.empty(need, dtype=torch.uint8, device=self.device))
             state = torch.zeros(8, dtype=torch.int64, device=self.device)
-            win_out = torch.empty(32768, dtype=torch.uint8, device=self.device)
-            N.check(lib.rd_gz_stream_inflate(N.ptr(comp), comp.numel(), int(data_bytes), int(valid_bytes), self.SECTION, cap_syms,
-                                             int(first_start_bit) & 0xffffffff, N.ptr(self.carry), int(self._delta_bits) if self.carry is not None else 0,
-                                             1 if at_eof else 0, N.ptr(self.win), N.ptr(win_out), N.ptr(text_out), text_out.numel(), N.ptr(state),
-                                             N.ptr(self._ws), self._ws.numel(), C.c_void_p(self.stream.cuda_stream)), "rd_gz_stream_inflate")
+            carried_out = torch.empty(32768, dtype=carried_dtype, device=self.device)
+            N.check(getattr(lib, call)(N.ptr(comp), comp.numel(), int(data_bytes), int(valid_bytes), self.SECTION, cap_syms, int(first_start_bit) & 0xffffffff,
+                                       N.ptr(self.carry), int(self._delta_bits) if self.carry is not None else 0, 1 if at_eof else 0, N.ptr(carried),
+                                       N.ptr(carried_out), N.ptr(out), out.numel(), N.ptr(state), N.ptr(ws), ws.numel(), C.c_void_p(self.stream.cuda_stream)), call)
             host = torch.empty(64, dtype=torch.uint8, pin_memory=True)
             N.copy_bytes(host, state.view(torch.uint8), 64, self.stream, workgroups=1)
             ev = N.new_event()
             ev.record(self.stream)
-        self.carry, self.win, self._delta_bits = state, win_out, int(data_bytes) * 8
-        return {"host": host, "event": ev, "keep": (comp, state, win_out)}
+        self.carry, self._delta_bits = state, int(data_bytes) * 8
+        return {"host": host, "event": ev, "keep": (comp, state, carried_out)}, carried_out
+
+    def submit(self, src, valid_bytes, data_bytes, first_start_bit, at_eof, text_out):
+        """src: pinned uint8 tensor holding valid_bytes bytes of the file from the batch's first byte; the sections cover
+        [0, data_bytes); text_out: device uint8 tensor that receives the text"""
+        ticket, self.win = self._submit("rd_gz_stream_inflate", "rd_gz_stream_workspace_bytes", src, valid_bytes, data_bytes, first_start_bit, at_eof, self.win,
+                                        torch.uint8, text_out)
+        return ticket
 
     @staticmethod
     def finish(ticket):
         """-> dict(total_len, n_text, crc, status, final, end_bit, next_start, bad_section, n_sections)"""
-        import numpy as np
         N.wait_event(ticket["event"])
         h = ticket["host"].numpy()
         q = h.view(np.uint64)
@@ -481,34 +464,15 @@ class DeviceRangeGunzip(DeviceStreamGunzip):
         self._rws = None
 
     def submit(self, src, valid_bytes, data_bytes, first_start_bit, at_eof):
-        lib = N.lib()
-        cap_syms = self.SECTION * self.CAP_RATIO
-        text_cap = self.text_cap(data_bytes)
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
-            comp = torch.empty(((valid_bytes + 4096 + 255) // 256) * 256, dtype=torch.uint8, device=self.device)
-            N.copy_bytes(comp, src, valid_bytes, self.stream)
-            comp[valid_bytes:valid_bytes + 4096].zero_()
-            sym = torch.empty(text_cap, dtype=torch.int16, device=self.device)
-            need = int(lib.rd_gz_range_workspace_bytes(data_bytes, self.SECTION, cap_syms, text_cap))
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = None
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            state = torch.zeros(8, dtype=torch.int64, device=self.device)
-            map_out = torch.empty(32768, dtype=torch.int16, device=self.device)
-            N.check(lib.rd_gz_range_decode(N.ptr(comp), comp.numel(), int(data_bytes), int(valid_bytes), self.SECTION, cap_syms,
-                                           int(first_start_bit) & 0xffffffff, N.ptr(self.carry), int(self._delta_bits) if self.carry is not None else 0,
-                                           1 if at_eof else 0, N.ptr(self.map), N.ptr(map_out), N.ptr(sym), text_cap, N.ptr(state),
-                                           N.ptr(self._ws), self._ws.numel(), C.c_void_p(self.stream.cuda_stream)), "rd_gz_range_decode")
-            host = torch.empty(64, dtype=torch.uint8, pin_memory=True)
-            N.copy_bytes(host, state.view(torch.uint8), 64, self.stream, workgroups=1)
-            ev = N.new_event()
-            ev.record(self.stream)
-        self.carry, self.map, self._delta_bits = state, map_out, int(data_bytes) * 8
-        return {"host": host, "event": ev, "keep": (comp, state, map_out), "sym": sym}
+            sym = torch.empty(self.text_cap(data_bytes), dtype=torch.int16, device=self.device)
+        ticket, self.map = self._submit("rd_gz_range_decode", "rd_gz_range_workspace_bytes", src, valid_bytes, data_bytes, first_start_bit, at_eof, self.map,
+                                        torch.int16, sym)
+        ticket["sym"] = sym
+        return ticket
 
     @staticmethod
     def finish(ticket):
-        import numpy as np
         r = DeviceStreamGunzip.finish(ticket)
         r["first_start"] = int(ticket["host"].numpy().view(np.uint64)[6])       # the bit the batch's text starts at (0xffffffff: none)
         return r
@@ -520,16 +484,13 @@ class DeviceRangeGunzip(DeviceStreamGunzip):
         lib = N.lib()
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             need = int(lib.rd_gz_range_resolve_workspace_bytes(n))
-            if self._rws is None or self._rws.numel() < need:
-                self._rws = None
-                self._rws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=self.device)
-            N.check(lib.rd_gz_range_resolve(N.ptr(sym), int(n), N.ptr(window), int(win_valid), N.ptr(text_out), N.ptr(rstate), N.ptr(self._rws),
-                                            self._rws.numel(), C.c_void_p(self.stream.cuda_stream)), "rd_gz_range_resolve")
+            rws = _grown(self, "_rws", need, lambda: torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=self.device))
+            N.check(lib.rd_gz_range_resolve(N.ptr(sym), int(n), N.ptr(window), int(win_valid), N.ptr(text_out), N.ptr(rstate), N.ptr(rws),
+                                            rws.numel(), C.c_void_p(self.stream.cuda_stream)), "rd_gz_range_resolve")
 
 
 def apply_map(m, window):
     """the window behind a range = its map applied to the window in front of it (numpy: m uint16[32768], window uint8[32768])"""
-    import numpy as np
     m = np.asarray(m).view(np.uint16)
     return np.where(m & 0x8000, window[m & 0x7fff], (m & 0xff).astype(np.uint8)).astype(np.uint8)
 
