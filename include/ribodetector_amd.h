@@ -396,6 +396,35 @@ RD_API int rd_summary_accumulate(const uint8_t *text_a, int64_t bytes_a, const i
                           const uint8_t *text_b, int64_t bytes_b, const int64_t *seq_off_b, const int32_t *seq_len_b, const float *logits_b,
                           const int8_t *labels, int64_t n, int64_t *acc, int64_t *info, void *stream);
 
+/* Reads longer than max_len classified over WINDOWS of max_len bases (CLI extension `--windows`; the reference classifies read[:max_len],
+ * reference detect.py:666-726, and that stays the rule without the flag). A window is one more (seq_off, seq_len) entry over the same
+ * text, so rd_classify takes the window table as it takes a read table and its kernels do not change.
+ * The rule, with L = max_len, S = stride (1..2^31-1), K = max_windows (1..RD_WINDOW_MAX): a read of len bases has W = 1 window when
+ * len <= L, else W = min(K, ceil((len - L) / S) + 1). W == 1: the window is the read's own entry (seq_off, seq_len), unchanged - rd_classify
+ * truncates it as ever, the logits are those of the read. W > 1: window j = 0..W-1 starts at seq_off + (j (len - L)) / (W - 1) (integer
+ * division in int64) and has L bases: the first at the read's start, the last at its end, no short tail window.
+ * rd_window_plan: win_first [dev] int64[n + 1] = the exclusive scan of W (entry n = the total). info [dev] int64[4] = {n, total windows,
+ * 0, fault}: fault != 0 = a seq_len < 0, nothing is to be trusted. workspace [dev, 256-byte aligned] of rd_window_workspace_bytes(n).
+ * rd_window_fill: win_off [dev] int64[total] / win_len [dev] int32[total], the window table, from the same integers (total: info[1] of
+ * the plan, read back by the caller - it sizes the table; entries outside [0, total) are never written). It reads no text.
+ * rd_window_fuse: win_logits [dev, 8-byte aligned] fp32[total][2] (rd_classify over the window table, FINAL: after rd_sync_results under
+ * rd_set_refine_async) -> logits [dev, 8-byte aligned] fp32[n][2] and labels [dev] uint8[n] (or NULL) = logits[1] > logits[0].
+ * RD_WINDOW_MEAN: ((w_0 + w_1) + w_2 + ...) / (float)W per class, a sequential fp32 sum in window order and one correctly rounded division
+ * (W == 1: w_0 bit for bit). RD_WINDOW_MAX_D: the logits of the window with the largest d = w[1] - w[0] (fp32), the lowest window on a tie.
+ * only_multi != 0: rows with W == 1 (logits and labels) are left as they are. Every window's logits carry rd_classify's guarantees (the
+ * float64 pass included); a FUSED margin inside the fp32 noise band has no float64 guarantee. n == 0: no-ops (the plan zeroes info and
+ * win_first[0]). Asynchronous on `stream`. */
+#define RD_WINDOW_MAX 4096
+#define RD_WINDOW_MEAN 0
+#define RD_WINDOW_MAX_D 1
+RD_API size_t rd_window_workspace_bytes(int64_t n);
+RD_API int rd_window_plan(const int32_t *seq_len, int64_t n, int32_t max_len, int64_t stride, int32_t max_windows, int64_t *win_first, int64_t *info,
+                   void *workspace, size_t workspace_bytes, void *stream);
+RD_API int rd_window_fill(const int64_t *seq_off, const int32_t *seq_len, const int64_t *win_first, int64_t n, int32_t max_len, int64_t stride,
+                   int32_t max_windows, int64_t total, int64_t *win_off, int32_t *win_len, void *stream);
+RD_API int rd_window_fuse(const float *win_logits, const int64_t *win_first, int64_t n, int32_t mode, int32_t only_multi, float *logits, uint8_t *labels,
+                   void *stream);
+
 /* ONE DEFLATE stream - a plain .gz, the format sequencers write - inflated on the device (round 5; the CLI's default for such FASTQ, RD_DEVICE_INFLATE=members keeps the host's decoders).
  * Replaces, for such files: gzip.open(path, 'rt') of reference data_loader/seq_encoder.py:21-39. The two-pass scheme of pugz (this
  * build's host reader: csrc/rd_pgzip.h) with one wave per SECTION of `section_bytes` compressed bytes: block starts are searched on the

@@ -29,6 +29,7 @@
 //   rd_report_*                        per-read report lines (id, label, probabilities) of a chunk (rd_report.hpp)
 //   rd_pair_*                          the mates of an interleaved chunk: pair table, mates' sequence tables, mate check (rd_pairs.hpp)
 //   rd_summary_*                       the QC counters of a run, added up chunk by chunk (rd_summary.hpp)
+//   rd_window_*                        reads longer than max_len as several windows: the window table and the fusion of its logits (rd_windows.hpp)
 #include <stdlib.h>
 #include "rd_common.hpp"
 #include "rd_prep.hpp"
@@ -46,6 +47,7 @@
 #include "rd_report.hpp"
 #include "rd_pairs.hpp"
 #include "rd_summary.hpp"
+#include "rd_windows.hpp"
 
 // ================================================================================================
 // C ABI
@@ -1017,6 +1019,87 @@ int rd_summary_accumulate(const uint8_t *text_a, int64_t bytes_a, const int64_t 
                        labels, n, info);
     hipLaunchKernelGGL(rd_summary_acc_kernel, dim3((unsigned)((n + SM_UNITS - 1) / SM_UNITS)), dim3(256), 0, st, text_a, seq_off_a, seq_len_a, logits_a, text_b,
                        seq_off_b, seq_len_b, logits_b, labels, n, acc, info);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+// reads longer than max_len over windows (rd_windows.hpp): the plan counts and scans, the fill writes the window table that rd_classify
+// takes, the fuse turns the windows' logits into the reads'
+namespace {
+struct WindowWs {
+    int nb;
+    int64_t *bsum;
+    int32_t *fault;
+    size_t total;
+};
+WindowWs window_ws(void *workspace, int64_t n) {
+    WindowWs p;
+    Carver c(workspace);
+    p.nb = (int)((n + 1 + GZ_SCAN_ITEMS - 1) / GZ_SCAN_ITEMS);
+    p.bsum = c.take<int64_t>((size_t)p.nb);
+    p.fault = c.take<int32_t>(1);
+    p.total = c.off;
+    return p;
+}
+// the rule's parameters, as every rd_window_* entry point that takes them checks them
+int window_rule_check(const char *fn, int64_t n, int32_t max_len, int64_t stride, int32_t max_windows) {
+    if (n < 0 || n > 0x7fffffffLL) RD_FAIL(RD_E_INVALID, "%s: n=%lld out of range", fn, (long long)n);
+    if (max_len < 1 || max_len > MAX_LEN_LIMIT) RD_FAIL(RD_E_INVALID, "%s: max_len=%d out of range [1,%d]", fn, max_len, MAX_LEN_LIMIT);
+    if (stride < 1 || stride > 0x7fffffffLL) RD_FAIL(RD_E_INVALID, "%s: stride=%lld out of range [1,2^31-1]", fn, (long long)stride);
+    if (max_windows < 1 || max_windows > RD_WINDOW_MAX) RD_FAIL(RD_E_INVALID, "%s: max_windows=%d out of range [1,%d]", fn, max_windows, RD_WINDOW_MAX);
+    return RD_OK;
+}
+}  // namespace
+
+size_t rd_window_workspace_bytes(int64_t n) {
+    if (n < 0 || n > 0x7fffffffLL) return 0;
+    return window_ws(nullptr, n).total;
+}
+
+int rd_window_plan(const int32_t *seq_len, int64_t n, int32_t max_len, int64_t stride, int32_t max_windows, int64_t *win_first, int64_t *info,
+                   void *workspace, size_t workspace_bytes, void *stream) {
+    if (const int rc = window_rule_check("rd_window_plan", n, max_len, stride, max_windows)) return rc;
+    if (!info || !win_first) RD_FAIL(RD_E_INVALID, "rd_window_plan: null info or win_first");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        RD_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int64_t), st));
+        RD_HIP(hipMemsetAsync(win_first, 0, sizeof(int64_t), st));
+        return RD_OK;
+    }
+    if (!seq_len || !workspace) RD_FAIL(RD_E_INVALID, "rd_window_plan: null pointer");
+    if ((uintptr_t)workspace & 255) RD_FAIL(RD_E_INVALID, "rd_window_plan: workspace must be 256-byte aligned");
+    const WindowWs p = window_ws(workspace, n);
+    if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "rd_window_plan: workspace too small: %zu < %zu", workspace_bytes, p.total);
+    RD_HIP(hipMemsetAsync(p.fault, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(rd_window_count_kernel, dim3(p.nb), dim3(256), 0, st, seq_len, n, (int64_t)max_len, stride, (int64_t)max_windows, p.bsum, p.fault);
+    hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, p.bsum, p.nb, info, (int64_t)INT64_MAX);
+    hipLaunchKernelGGL(rd_window_off_kernel, dim3(p.nb), dim3(256), 0, st, seq_len, n, (int64_t)max_len, stride, (int64_t)max_windows, p.bsum, p.fault,
+                       win_first, info);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+int rd_window_fill(const int64_t *seq_off, const int32_t *seq_len, const int64_t *win_first, int64_t n, int32_t max_len, int64_t stride,
+                   int32_t max_windows, int64_t total, int64_t *win_off, int32_t *win_len, void *stream) {
+    if (const int rc = window_rule_check("rd_window_fill", n, max_len, stride, max_windows)) return rc;
+    if (total < n || total > n * (int64_t)max_windows) RD_FAIL(RD_E_INVALID, "rd_window_fill: total=%lld is not a window count of %lld reads", (long long)total, (long long)n);
+    if (n == 0) return RD_OK;
+    if (!seq_off || !seq_len || !win_first || !win_off || !win_len) RD_FAIL(RD_E_INVALID, "rd_window_fill: null pointer");
+    hipLaunchKernelGGL(rd_window_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seq_off, seq_len, win_first, n,
+                       (int64_t)max_len, stride, (int64_t)max_windows, total, win_off, win_len);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+int rd_window_fuse(const float *win_logits, const int64_t *win_first, int64_t n, int32_t mode, int32_t only_multi, float *logits, uint8_t *labels,
+                   void *stream) {
+    if (n < 0 || n > 0x7fffffffLL) RD_FAIL(RD_E_INVALID, "rd_window_fuse: n=%lld out of range", (long long)n);
+    if (mode != RD_WINDOW_MEAN && mode != RD_WINDOW_MAX_D) RD_FAIL(RD_E_INVALID, "rd_window_fuse: unknown mode %d", mode);
+    if (n == 0) return RD_OK;
+    if (!win_logits || !win_first || !logits) RD_FAIL(RD_E_INVALID, "rd_window_fuse: null pointer");
+    if (((uintptr_t)win_logits | (uintptr_t)logits) & 7) RD_FAIL(RD_E_INVALID, "rd_window_fuse: win_logits and logits must be 8-byte aligned");
+    hipLaunchKernelGGL(rd_window_fuse_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float2 *)win_logits, win_first, n,
+                       (int)mode, (int)(only_multi != 0), (float2 *)logits, labels);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }

@@ -23,6 +23,10 @@ records; rd_pair_split (csrc/rd_pairs.hpp) turns a chunk's tables into the two m
 checks the mates' ids, and from there on the run is the paired-end run (under several ranks: always the label gather).
 --summary (an extension): every rank adds the QC counters of the units it classified to one int64 array on its GPU, chunk by chunk
 (rd_summary_accumulate, summary.py); the arrays are summed after the last chunk and rank 0 writes them as JSON once the run has ended well.
+--windows (an extension): a read longer than -l is classified over several windows of -l bases instead of its first -l bases alone. The
+window table of a chunk is planned and written on the copy stream (rd_window_plan / rd_window_fill, csrc/rd_windows.hpp; windows.py has
+the rule), rd_classify runs over it as it runs over a read table, and the post stream fuses the windows' final logits into one pair of
+logits per read (rd_window_fuse); everything behind that - pair fusion, outputs, report, summary - sees reads.
 """
 import argparse
 import functools
@@ -43,6 +47,7 @@ from . import _native as _native_mod
 from . import dist as rdist
 from . import gz as _gzmod
 from . import summary as _summod
+from . import windows as _winmod
 from .data_loader import device_reader as dr
 from .data_loader import fastx_parser as fx
 from .model import model as module_arch
@@ -218,6 +223,8 @@ class Predictor:
         self.mate_check = not getattr(args, 'no_mate_check', False)
         self._pairs = None                       # --interleaved: gz.DevicePairSplit (run_with_chunks)
         self._summary = None                     # --summary: summary.DeviceSummary (run_with_chunks)
+        self._windows = None                     # --windows: {"stride", "max_per_read", "fuse"} (stride None = -l); detect() sets it
+        self._win_classified = [0, 0]            # windows this rank classified, per mate
         self._install_cleanup()
 
     @property
@@ -396,6 +403,36 @@ class Predictor:
                  "first_record": self._chunk_first_record, "keep": (so, sl)}
         return [(text,) + m1, (text,) + m2], pairs
 
+    def _read_work(self, seq_len):
+        """recurrence steps per read, for the shard bounds of the label gather: min(len, -l), times the read's windows under --windows"""
+        ln = np.asarray(seq_len, dtype=np.int64)
+        work = np.minimum(ln, self.len)
+        if self._windows is not None:
+            work = work * _winmod.counts(ln, self.len, self._windows["stride"] or self.len, self._windows["max_per_read"])
+        return work
+
+    def _plan_windows(self, chunks, lo, hi, on_dev):
+        """--windows: the chunk's tables reach the device and the window table of every mate is planned and written on the COPY stream
+        (behind the chunk's `ready` event or its H2D - not behind the recurrences of the chunk before, which fill the main stream); the
+        host waits there, once, for the numbers of windows, which size the tables and the classify calls. The main stream then waits
+        for the copy stream as it does without the flag. Returns (dev_in, pairs, one plan per mate)."""
+        cs, cur = self._copy_stream, torch.cuda.current_stream(self.device)
+        w, pairs = self._windows, None
+        with torch.cuda.stream(cs):
+            if self.interleaved:
+                dev_in, pairs = self._split_pairs(chunks[0], lo, hi, on_dev)
+            elif on_dev:
+                dev_in = [c.dev[:3] for c in chunks]
+                for c in chunks:
+                    cs.wait_event(c.ready)
+            else:
+                dev_in = [self._to_device(c, lo, hi, cs) for c in chunks]
+            plans = [self.model.window_plan(l, self.len, w["stride"], w["max_per_read"]) for _, _, l in dev_in]
+            for e, (p, (_, o, l)) in enumerate(zip(plans, dev_in)):
+                self._win_classified[e] += self.model.window_table(p, o, l)
+        cur.wait_stream(cs)
+        return dev_in, pairs, plans
+
     def _check_pairs(self, chunk, pairs):
         """the verdict of rd_pair_split on this rank's pairs of a chunk, once the event behind it has passed"""
         info = pairs["info"]
@@ -423,16 +460,18 @@ class Predictor:
         bounds = None
         if self.gathers_labels:                     # equal bases (= recurrence steps) per rank, not equal read counts
             if self.interleaved:
-                work = np.minimum(np.asarray(chunks[0].seq_len[:2 * n], dtype=np.int64), self.len).reshape(n, 2).sum(1)
+                work = self._read_work(chunks[0].seq_len[:2 * n]).reshape(n, 2).sum(1)
             else:
-                work = sum(np.minimum(np.asarray(c.seq_len, dtype=np.int64), self.len) for c in chunks)
+                work = sum(self._read_work(c.seq_len) for c in chunks)
             bounds = rdist.shard_bounds(n, self.world, work)
         lo, hi = (0, n) if bounds is None else (bounds[self.rank], bounds[self.rank + 1])
         cs = self._copy_stream
         cur = torch.cuda.current_stream(self.device)
         on_dev = isinstance(chunks[0], dr.DeviceChunk)      # text and index already in HBM (data_loader/device_reader.py): nothing to copy
-        pairs = None
-        if self.interleaved:
+        pairs = plans = None
+        if self._windows is not None:
+            dev_in, pairs, plans = self._plan_windows(chunks, lo, hi, on_dev)
+        elif self.interleaved:
             dev_in, pairs = self._split_pairs(chunks[0], lo, hi, on_dev)
         elif on_dev:
             dev_in = [c.dev[:3] for c in chunks]
@@ -443,7 +482,11 @@ class Predictor:
             cur.wait_stream(cs)
         # (dev_in stays referenced by the ticket: its tensors were allocated on the copy stream and must not return to that
         # stream's pool while other streams read them - and the deferred float64 pass reads the bases until the post-pass has run)
-        outs = [self.model.classify_bytes(a, o, l, self.len, want_labels=not self.is_paired) for a, o, l in dev_in]
+        if plans is None:
+            outs = [self.model.classify_bytes(a, o, l, self.len, want_labels=not self.is_paired) for a, o, l in dev_in]
+        else:                                       # (the window tables: the reads' own entries where nothing is longer than -l)
+            for (a, _, _), p in zip(dev_in, plans):
+                self.model.classify_window_table(a, p)
         main_done = torch.cuda.Event()
         main_done.record(cur)
         # post-pass on its own stream: it overlaps the recurrences of the next chunk (the float64 refine pass has the latency of
@@ -452,11 +495,16 @@ class Predictor:
         with torch.cuda.stream(post):
             post.wait_event(main_done)
             self.model.sync_results()                # the reads inside the noise band, in float64 (current stream = post)
+            if plans is not None:                    # the windows' logits are final: one pair of logits per read
+                outs = [self.model.window_fuse(p, self._windows["fuse"], want_labels=not self.is_paired) for p in plans]
             if self.is_paired and self.args.ensure == 'none' and self.refine_band > 0:
                 # pair label = argmax of the SUMMED logits (reference detect.py:657): also the reads whose PAIR margin is inside the
                 # band - only both mates' logits together say which, so this mode keeps the scan form of the pass (rd_refine)
                 for k, (a, o, l) in enumerate(dev_in):
                     self.model.refine(a, o, l, self.len, outs[k][0], outs[k][1], outs[1 - k][0], thresh=self.refine_band)
+                    if plans is not None:            # the pass read the read-level tables: a read of several windows gets its fused logits back
+                        self.model.window_fuse(plans[k], self._windows["fuse"], logits=outs[k][0], labels=outs[k][1],
+                                               want_labels=outs[k][1] is not None, only_multi=True)
             if self.is_paired:
                 labels = module_arch.pair_fuse(outs[0][0], outs[1][0], self.args.ensure)
             else:
@@ -474,7 +522,7 @@ class Predictor:
                 _, finish = rdist.gather_labels(labels, n, dst=0, bounds=bounds, async_op=True)
             done = _native_mod.new_event()
             done.record(post)
-        return {"n": n, "bounds": bounds, "labels": labels, "host": host, "finish": finish, "done": done, "keep": (dev_in, outs),
+        return {"n": n, "bounds": bounds, "labels": labels, "host": host, "finish": finish, "done": done, "keep": (dev_in, outs, plans),
                 "pieces": pieces, "pairs": pairs, "chunk": chunks[0], "totals": [c.total for c in chunks] if on_dev else (), "summary": sum_info}
 
     def _select_chunk(self, chunks, dev_in, labels, lo, hi, on_dev, pairs=None):
@@ -826,6 +874,13 @@ class Predictor:
                     colors.BOLD, colors.OKCYAN, self.num_unknown, colors.ENDC))
         if self.interleaved:
             fx.check_even_records(self._records_seen)
+        if self._windows is not None:              # every rank classified the windows of its own shard / byte range
+            per_rank = self._all_gather(self._win_classified) if self.multi else [self._win_classified]
+            self._win_total = [sum(int(r[e]) for r in per_rank) for e in range(2 if self.is_paired else 1)]
+            if self.rank == 0:
+                self.logger.info('Classified {}{}{}{} windows ({} mode, at most {} per read)'.format(
+                    colors.BOLD, colors.OKCYAN, " + ".join(str(x) for x in self._win_total), colors.ENDC, self._windows["fuse"],
+                    self._windows["max_per_read"]))
         if self._summary is not None:
             self._write_summary()
 
@@ -844,7 +899,9 @@ class Predictor:
                 units, [self.num_unknown, self.num_nonrrna, self.num_rrna]))
         path = self.args.summary
         doc = _summod.to_json(acc, {"version": __version__, "paired": bool(self.is_paired), "interleaved": self.interleaved, "len": int(self.len),
-                                    "ensure": self.args.ensure, "model": self.state_key, "inputs": list(self.input)})
+                                    "ensure": self.args.ensure, "model": self.state_key, "inputs": list(self.input),
+                                    "windows": None if self._windows is None else dict(
+                                        self._windows, stride=int(self._windows["stride"] or self.len), classified=list(self._win_total))})
         _summod.write_json(path, doc)
         frac = doc["reads"]["rRNA_fraction"]
         self.logger.info('rRNA fraction: {} (summary: {})'.format("n/a" if frac is None else "%.6f" % frac, path))
@@ -972,6 +1029,7 @@ class Predictor:
         self._rep_seq = 0
         # --summary: the run's QC counters, one int64 array per rank that every chunk adds to on the post stream
         self._summary = _summod.DeviceSummary(self.device) if getattr(self.args, 'summary', None) else None
+        self._win_classified = [0, 0]
         if self._gz_files or self._rep_gz:
             self._gz = _gzmod.DeviceGzip(self.device)
 
@@ -1060,6 +1118,7 @@ class Predictor:
                           self.args.ensure)
         check_summary(getattr(self.args, 'summary', None), self.output, self.rrna, self.is_paired, self.args.ensure,
                       getattr(self.args, 'read_report', None))
+        self._windows = check_windows(self.args)
         # reference batch-size heuristic (detect.py:558-568); kept because --chunk_size is expressed in these batches
         denom = (2 * self.len * 6.4) if self.is_paired else (self.len * 6.4)
         self.batch_size = 2 ** math.floor(math.log2(((self.args.memory - 2) * 1024 * 1024) / denom))
@@ -1145,6 +1204,27 @@ def check_summary(path, output, rrna, is_paired, ensure, read_report=None):
             raise RuntimeError("--summary {} is also {}".format(path, what))
 
 
+def check_windows(args):
+    """--windows and its settings, checked before anything touches a device: None without the flag, else {"stride" (None = -l),
+    "max_per_read", "fuse"}. RuntimeError for a setting without --windows, a stride outside 1..2^31-1 or more than 4096 (or fewer than
+    1) windows per read."""
+    stride, most, fuse = (getattr(args, k, None) for k in ('window_stride', 'max_windows', 'window_fuse'))
+    if not getattr(args, 'windows', False):
+        for flag, v in (('--window_stride', stride), ('--max_windows', most), ('--window_fuse', fuse)):
+            if v is not None:
+                raise RuntimeError("{} needs --windows".format(flag))
+        return None
+    if stride is not None and not 1 <= stride <= _winmod.STRIDE_MAX:
+        raise RuntimeError("--window_stride must be in [1, 2^31 - 1]; got {}".format(stride))
+    most = _winmod.DEFAULT_MAX_WINDOWS if most is None else most
+    if not 1 <= most <= _native_mod.WINDOW_MAX:
+        raise RuntimeError("--max_windows must be in [1, {}]; got {}".format(_native_mod.WINDOW_MAX, most))
+    fuse = fuse or "mean"
+    if fuse not in _native_mod.WINDOW_FUSE:
+        raise RuntimeError("--window_fuse must be mean or max; got {!r}".format(fuse))
+    return {"stride": stride, "max_per_read": int(most), "fuse": fuse}
+
+
 def build_parser():
     args = argparse.ArgumentParser(description='rRNA sequence detector', formatter_class=RawTextHelpFormatter)
     args.add_argument('-c', '--config', default=None, type=str, help='Path of config file')
@@ -1192,6 +1272,17 @@ none: give label based on the mean probability of read pair.
                            '-o (and -r) take one path - interleaved output, the selected pairs in input order - or two: mate 1\'s\n'
                            'records and mate 2\'s, as for two input files. The ids of the two records of a pair (the header up to\n'
                            'its first whitespace) must be equal, or equal up to a trailing /1 and /2.')
+    args.add_argument('--windows', action='store_true',
+                      help='(extension) classify a read longer than -l over several windows of -l bases, spread evenly from its start to\n'
+                           'its end, instead of its first -l bases alone; the windows\' logits are fused into one result per read.\n'
+                           'Reads of at most -l bases are classified exactly as without the flag.')
+    args.add_argument('--window_stride', default=None, type=int,
+                      help='(extension) with --windows: a read of len bases gets ceil((len - l) / N) + 1 windows (default: -l, no overlap)')
+    args.add_argument('--max_windows', default=None, type=int,
+                      help='(extension) with --windows: the most windows per read, 1..4096 (default: 32); longer reads spread that many')
+    args.add_argument('--window_fuse', default=None, type=str, choices=['mean', 'max'],
+                      help='(extension) with --windows: mean = the mean of the windows\' logits (default); max = the logits of the window\n'
+                           'with the largest rRNA margin ("rRNA if any stretch of the read is")')
     args.add_argument('--no_mate_check', action='store_true', help='(extension) with --interleaved: do not compare the ids of the mates')
     args.add_argument('-v', '--version', action='version', version='%(prog)s {version}'.format(version=__version__))
     return args
@@ -1201,6 +1292,7 @@ def main(argv=None, log_level=None):
     args = build_parser().parse_args(argv)
     config_file = os.path.join(cd, 'config.json') if args.config is None else args.config
     config = ConfigParser.from_json(config_file)
+    check_windows(args)                          # (before the model is loaded: nothing has touched a device yet)
     seq_pred = Predictor(config, args, log_level=log_level)
     try:
         t0 = time.perf_counter()

@@ -9,7 +9,9 @@ Entries:
   * `forward(x: PackedSequence)`  - API parity with the reference (the one-hot tensor is turned back into bases);
   * `forward(x: Tensor[B,L,4])` when built with pack_seq=false - the reference's forward2 (padded input);
   * `classify_bytes(arena, offsets, lens, max_len)` - the native fast entry: raw ASCII reads resident in HBM,
-    encoder + recurrence + FC + argmax fused on the device.
+    encoder + recurrence + FC + argmax fused on the device;
+  * `classify_windows(arena, offsets, lens, max_len, ...)` - the same for reads of any length: a read longer than max_len is
+    classified over several windows of max_len bases and the windows' logits are fused.
 """
 import contextlib
 import ctypes as C
@@ -21,6 +23,7 @@ import torch
 from torch.nn.utils.rnn import PackedSequence
 
 from .. import _native as N
+from .. import windows as W
 
 log = logging.getLogger("ribodetector_amd")
 
@@ -340,6 +343,93 @@ class SeqModel:
                                     N.ptr(labels if want_labels else None), N.ptr(ws), ws.numel(), N.stream_ptr(self.device)),
                 "rd_classify")
         return logits, (labels if want_labels else None)
+
+    # ---- reads longer than max_len over windows (C ABI rd_window_*, csrc/rd_windows.hpp) ------------------------------
+    WINDOW_SLICE = 1 << 23          # windows per rd_classify call of classify_window_table: bounds the classify workspace (100 MB at 100 bp)
+
+    def window_plan(self, lens, max_len, stride=None, max_windows=32):
+        """First half of classify_windows, on the current stream: the windows of every read counted and scanned (rd_window_plan). Returns
+        the plan: a dict with win_first int64[n + 1] on the device and the pinned verdict `info` ({n, windows, 0, fault}), which
+        window_table reads once `ready` has passed."""
+        if self._handle is None:
+            raise RuntimeError("SeqModel: call .to('cuda') before inference")
+        if lens.dtype != torch.int32 or not lens.is_cuda or not lens.is_contiguous():
+            raise TypeError("classify_windows: lens must be a contiguous torch.int32 CUDA tensor")
+        n = int(lens.numel())
+        stride, max_windows = W.check_params(max_len, stride, max_windows)
+        lib = N.lib()
+        win_first = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        info = torch.empty(4, dtype=torch.int64, device=self.device)
+        ws = torch.empty(max(int(lib.rd_window_workspace_bytes(n)), 256), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(lib.rd_window_plan(N.ptr(lens), n, int(max_len), stride, max_windows, N.ptr(win_first), N.ptr(info), N.ptr(ws), ws.numel(),
+                                       N.stream_ptr(self.device)), "rd_window_plan")
+            host = torch.empty(4, dtype=torch.int64, pin_memory=True).copy_(info, non_blocking=True)
+            ready = N.new_event()
+            ready.record(torch.cuda.current_stream(self.device))
+        return {"n": n, "max_len": int(max_len), "stride": stride, "max_windows": max_windows, "win_first": win_first, "info": host,
+                "ready": ready, "keep": (info, ws)}
+
+    def window_table(self, plan, offsets, lens):
+        """Second half of the plan: waits (the host, sleeping) for the number of windows - the one host wait of the feature - and
+        writes the window table on the current stream (rd_window_fill): plan["win_off"] int64[total], plan["win_len"] int32[total].
+        Returns the number of windows."""
+        N.wait_event(plan["ready"])
+        info = plan["info"]
+        if int(info[3]) or int(info[0]) != plan["n"]:
+            raise RuntimeError("device window plan: a sequence table entry has a negative length")
+        total = int(info[1])
+        if offsets.dtype != torch.int64 or not offsets.is_cuda or not offsets.is_contiguous() or offsets.numel() < plan["n"]:
+            raise TypeError("classify_windows: offsets must be a contiguous torch.int64 CUDA tensor, one entry per read")
+        plan["win_off"] = torch.empty(total, dtype=torch.int64, device=self.device)
+        plan["win_len"] = torch.empty(total, dtype=torch.int32, device=self.device)
+        plan["total"] = total
+        with torch.cuda.device(self.device):
+            N.check(N.lib().rd_window_fill(N.ptr(offsets), N.ptr(lens), N.ptr(plan["win_first"]), plan["n"], plan["max_len"], plan["stride"],
+                                           plan["max_windows"], total, N.ptr(plan["win_off"]), N.ptr(plan["win_len"]), N.stream_ptr(self.device)),
+                    "rd_window_fill")
+        return total
+
+    def classify_window_table(self, arena, plan):
+        """rd_classify over the window table of a plan, WINDOW_SLICE windows per call, on the current stream: plan["win_logits"]
+        fp32[total, 2] (final after sync_results(), like every classify_bytes result)."""
+        total = plan["total"]
+        out = plan["win_logits"] = torch.empty((total, 2), dtype=torch.float32, device=self.device)
+        for a in range(0, total, self.WINDOW_SLICE):
+            b = min(total, a + self.WINDOW_SLICE)
+            self.classify_bytes(arena, plan["win_off"][a:b], plan["win_len"][a:b], plan["max_len"], want_labels=False, logits=out[a:b])
+        return out
+
+    def window_fuse(self, plan, fuse="mean", logits=None, labels=None, want_labels=True, only_multi=False):
+        """The windows' logits of a plan fused into one pair of logits per read (rd_window_fuse) on the current stream, which must see
+        the windows' FINAL logits (sync_results()). only_multi: rows of reads with one window are left as they are."""
+        n = plan["n"]
+        if fuse not in N.WINDOW_FUSE:
+            raise RuntimeError("classify_windows: fuse must be one of %s; got %r" % (", ".join(sorted(N.WINDOW_FUSE)), fuse))
+        if logits is None:
+            logits = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        if want_labels and labels is None:
+            labels = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().rd_window_fuse(N.ptr(plan["win_logits"]), N.ptr(plan["win_first"]), n, N.WINDOW_FUSE[fuse], 1 if only_multi else 0,
+                                           N.ptr(logits), N.ptr(labels if want_labels else None), N.stream_ptr(self.device)), "rd_window_fuse")
+        return logits, (labels if want_labels else None)
+
+    def classify_windows(self, arena, offsets, lens, max_len, stride=None, max_windows=32, fuse="mean", want_labels=True):
+        """classify_bytes for reads of any length: a read longer than max_len is classified as W = min(max_windows, ceil((len - max_len) /
+        stride) + 1) windows of max_len bases spread evenly from its start to its end (stride None = max_len), and the windows' logits
+        are fused: "mean" = their fp32 mean in window order, "max" = the logits of the window with the largest rRNA margin. A read of at
+        most max_len bases is its own window and its logits are classify_bytes' bit for bit (ribodetector_amd/windows.py has the rule
+        in numpy). Returns (logits fp32[n, 2], labels uint8[n] | None, windows classified), FINAL: the call waits once on the host, for
+        the number of windows, and runs the float64 pass of its windows before it fuses."""
+        if fuse not in N.WINDOW_FUSE:
+            raise RuntimeError("classify_windows: fuse must be one of %s; got %r" % (", ".join(sorted(N.WINDOW_FUSE)), fuse))
+        plan = self.window_plan(lens, max_len, stride, max_windows)
+        total = self.window_table(plan, offsets, lens)
+        self.classify_window_table(arena, plan)
+        self.sync_results()
+        logits, labels = self.window_fuse(plan, fuse, want_labels=want_labels)
+        return logits, labels, total
 
     # ---- reference-compatible call --------------------------------------------------------------------
     def forward2(self, x):

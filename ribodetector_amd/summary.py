@@ -76,7 +76,8 @@ class DeviceSummary:
 
 
 def to_json(acc, meta):
-    """the summary document (a dict) of an accumulator; meta: version, paired, interleaved, len, ensure, model, inputs. Pure host code."""
+    """the summary document (a dict) of an accumulator; meta: version, paired, interleaved, len, ensure, model, inputs
+    and, under --windows, windows = {stride, max_per_read, fuse, classified}. Pure host code."""
     s = sections(np.asarray(acc, dtype=np.int64))
     paired = bool(meta["paired"])
     units = [int(x) for x in s["units"]]
@@ -101,6 +102,10 @@ def to_json(acc, meta):
     # from the histogram only while -l lies below that bin
     ln = int(meta["len"])
     doc["truncated_reads"] = int(s["length"][:len(mates), :, ln + 1:].sum()) if 0 <= ln < LEN_BINS - 1 else None
+    # --windows only: the settings, and the windows classified per mate (the reads above were then classified over their whole length;
+    # truncated_reads keeps its meaning, the reads longer than -l)
+    if meta.get("windows") is not None:
+        doc["windows"] = dict(meta["windows"])
     return doc
 
 
