@@ -425,6 +425,32 @@ RD_API int rd_window_fill(const int64_t *seq_off, const int32_t *seq_len, const 
 RD_API int rd_window_fuse(const float *win_logits, const int64_t *win_first, int64_t n, int32_t mode, int32_t only_multi, float *logits, uint8_t *labels,
                    void *stream);
 
+/* WHERE the rRNA is inside reads classified over windows (CLI extension `--regions`, with `--windows`): one text line per REGION of a
+ * chunk, made where the windows' final logits, the reads' lengths and the records' text already are. A unit is a read (text_b == NULL:
+ * single-end) or one mate of a pair; x_a are mate 1's tables, x_b mate 2's (the mates may share one text). Per mate: text_x [dev] /
+ * bytes_x; rec_start_x [dev] int64: record i starts at rec_start_x[i * rec_stride] and ends at the next entry (rec_stride 1: a table of
+ * n + 1 entries per mate; 2: an interleaved chunk's table of 2 n + 1 entries, rec_start_b = rec_start_a + 1); seq_len_x [dev] int32[n];
+ * win_first_x [dev] int64[n + 1] of rd_window_plan; win_logits_x [dev, 8-byte aligned] fp32[win_first_x[n]][2], FINAL (rd_sync_results).
+ * The rule, L = max_len: window j of a read is an rRNA window when l1 > l0 (a tie is not); it covers [start(j), start(j) + L) with
+ * start(j) = (j (len - L)) / (W - 1) of rd_window_fill when W > 1, [0, min(len, L)) when W == 1. A region is a maximal run a..b of rRNA
+ * windows of one read = [start(a), start(b) + L) in 0-based bases of the read (the unsampled bases between two rRNA windows belong to
+ * it; with a stride below L / 2 two regions may overlap); a region of no bases has no line. The line:
+ * `<id>\t<start>\t<end>\t<mate>\t<windows>\t<p_rrna_max>\n`, id as rd_report_format's (of THAT mate's record), start / end decimal, mate
+ * 1 / 2, windows = b - a + 1, p_rrna_max = the largest q = rint(softmax(logits)[1] * 1e4) of the run's windows as rd_report_format
+ * prints it. Order: units in input order, mate 1's lines before mate 2's, ascending start within a read. No header line is written.
+ * out [dev, 16-byte aligned] of out_cap bytes: the text has no bound linear in the text bytes (an id is repeated per region), so the
+ * caller guesses and repeats on fault 1. info [dev] int64[8] = {units, bytes, 0, fault, regions of mate 1, of mate 2, reads of mate 1
+ * with a region, of mate 2}. fault 1: the lines need info[1] > out_cap bytes, nothing is written (info[4..8) are valid). fault 2: a
+ * table entry outside its text, a header that does not start with '@' / '>' or runs past its record, a seq_len < 0, a win_first that is
+ * not increasing by 1..RD_WINDOW_MAX per read inside [0, win_first[n]], several windows on a read of at most L bases, or more windows
+ * than the workspace was sized for: nothing is written, info[0], info[1], info[4..8) = 0. workspace [dev, 256-byte aligned] of
+ * rd_region_workspace_bytes(n, total windows of both mates). n == 0: a no-op that zeroes info. Asynchronous on `stream`. */
+RD_API size_t rd_region_workspace_bytes(int64_t n, int64_t total_windows);
+RD_API int rd_region_format(const uint8_t *text_a, int64_t bytes_a, const int64_t *rec_start_a, const int32_t *seq_len_a, const int64_t *win_first_a,
+                     const float *win_logits_a, const uint8_t *text_b, int64_t bytes_b, const int64_t *rec_start_b, const int32_t *seq_len_b,
+                     const int64_t *win_first_b, const float *win_logits_b, int64_t rec_stride, int64_t n, int32_t max_len, uint8_t *out, size_t out_cap,
+                     int64_t *info, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ONE DEFLATE stream - a plain .gz, the format sequencers write - inflated on the device (round 5; the CLI's default for such FASTQ, RD_DEVICE_INFLATE=members keeps the host's decoders).
  * Replaces, for such files: gzip.open(path, 'rt') of reference data_loader/seq_encoder.py:21-39. The two-pass scheme of pugz (this
  * build's host reader: csrc/rd_pgzip.h) with one wave per SECTION of `section_bytes` compressed bytes: block starts are searched on the

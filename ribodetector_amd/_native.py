@@ -31,6 +31,7 @@ SYMBOLS = [
     "rd_pair_split", "rd_pair_expand_labels",
     "rd_summary_words", "rd_summary_accumulate",
     "rd_window_workspace_bytes", "rd_window_plan", "rd_window_fill", "rd_window_fuse",
+    "rd_region_workspace_bytes", "rd_region_format",
 ]
 WINDOW_MAX = 4096       # include/ribodetector_amd.h RD_WINDOW_MAX: the most windows a read can have
 WINDOW_FUSE = {"mean": 0, "max": 1}     # RD_WINDOW_MEAN / RD_WINDOW_MAX_D
@@ -124,6 +125,9 @@ def lib():
     L.rd_window_plan.argtypes = [vp, i64, i32, i64, i32, vp, vp, vp, sz, vp]
     L.rd_window_fill.argtypes = [vp, vp, vp, i64, i32, i64, i32, i64, vp, vp, vp]
     L.rd_window_fuse.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
+    L.rd_region_workspace_bytes.argtypes = [i64, i64]
+    L.rd_region_workspace_bytes.restype = sz
+    L.rd_region_format.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, i64, i32, vp, sz, vp, vp, sz, vp]
     L.rd_stream_create.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(vp)]
     L.rd_stream_destroy.argtypes = [vp]
     L.rd_copy_bytes.argtypes = [vp, vp, i64, i32, vp]

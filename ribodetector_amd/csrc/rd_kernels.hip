@@ -30,6 +30,7 @@
 //   rd_pair_*                          the mates of an interleaved chunk: pair table, mates' sequence tables, mate check (rd_pairs.hpp)
 //   rd_summary_*                       the QC counters of a run, added up chunk by chunk (rd_summary.hpp)
 //   rd_window_*                        reads longer than max_len as several windows: the window table and the fusion of its logits (rd_windows.hpp)
+//   rd_region_*                        the rRNA stretches of reads classified over windows, as text lines (rd_regions.hpp)
 #include <stdlib.h>
 #include "rd_common.hpp"
 #include "rd_prep.hpp"
@@ -48,6 +49,7 @@
 #include "rd_pairs.hpp"
 #include "rd_summary.hpp"
 #include "rd_windows.hpp"
+#include "rd_regions.hpp"
 
 // ================================================================================================
 // C ABI
@@ -1100,6 +1102,91 @@ int rd_window_fuse(const float *win_logits, const int64_t *win_first, int64_t n,
     if (((uintptr_t)win_logits | (uintptr_t)logits) & 7) RD_FAIL(RD_E_INVALID, "rd_window_fuse: win_logits and logits must be 8-byte aligned");
     hipLaunchKernelGGL(rd_window_fuse_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float2 *)win_logits, win_first, n,
                        (int)mode, (int)(only_multi != 0), (float2 *)logits, labels);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+// the rRNA regions of a chunk's reads (rd_regions.hpp): per-unit tables sized by n (always for two mates), then the line table, which
+// takes what is left of the workspace - rd_region_workspace_bytes leaves room for (total_windows + 2 n) / 2 lines, the most there can be
+namespace {
+struct RegionWs {
+    int nb;
+    int64_t *unit_bytes, *unit_lines, *bsum_bytes, *bsum_lines, *tot_bytes, *tot_lines;
+    int32_t *idlen, *fault;
+    unsigned long long *cnt;
+    size_t fixed;
+    int64_t line_cap;
+    int64_t *line_off;
+    int32_t *line_unit, *line_start, *line_end;
+    uint32_t *line_wq;
+};
+constexpr size_t RG_LINE_SLACK = 8 + 5 * 256;     // entry `lines` of line_off, and the alignment of the five arrays
+RegionWs region_ws(void *workspace, int64_t n, int64_t units, size_t workspace_bytes) {
+    RegionWs p;
+    Carver c(workspace);
+    p.nb = (int)((units + 1 + RG_UNITS - 1) / RG_UNITS);
+    const size_t cap_units = (size_t)(2 * n + 1), cap_nb = (size_t)((2 * n + 1 + RG_UNITS - 1) / RG_UNITS);
+    p.unit_bytes = c.take<int64_t>(cap_units);
+    p.unit_lines = c.take<int64_t>(cap_units);
+    p.idlen = c.take<int32_t>(cap_units);
+    p.bsum_bytes = c.take<int64_t>(cap_nb);
+    p.bsum_lines = c.take<int64_t>(cap_nb);
+    p.tot_bytes = c.take<int64_t>(4);
+    p.tot_lines = c.take<int64_t>(4);
+    p.cnt = c.take<unsigned long long>(4);
+    p.fault = c.take<int32_t>(1);
+    p.fixed = c.off;
+    p.line_cap = workspace_bytes > p.fixed + RG_LINE_SLACK ? (int64_t)((workspace_bytes - p.fixed - RG_LINE_SLACK) / 24) : 0;
+    p.line_off = c.take<int64_t>((size_t)p.line_cap + 1);
+    p.line_unit = c.take<int32_t>((size_t)p.line_cap);
+    p.line_start = c.take<int32_t>((size_t)p.line_cap);
+    p.line_end = c.take<int32_t>((size_t)p.line_cap);
+    p.line_wq = c.take<uint32_t>((size_t)p.line_cap);
+    return p;
+}
+}  // namespace
+
+size_t rd_region_workspace_bytes(int64_t n, int64_t total_windows) {
+    if (n < 0 || n > 0x3fffffffLL || total_windows < 0) return 0;
+    return region_ws(nullptr, n, 2 * n, 0).fixed + RG_LINE_SLACK + 24 * (size_t)((total_windows + 2 * n) / 2 + 1);
+}
+
+int rd_region_format(const uint8_t *text_a, int64_t bytes_a, const int64_t *rec_start_a, const int32_t *seq_len_a, const int64_t *win_first_a,
+                     const float *win_logits_a, const uint8_t *text_b, int64_t bytes_b, const int64_t *rec_start_b, const int32_t *seq_len_b,
+                     const int64_t *win_first_b, const float *win_logits_b, int64_t rec_stride, int64_t n, int32_t max_len, uint8_t *out, size_t out_cap,
+                     int64_t *info, void *workspace, size_t workspace_bytes, void *stream) {
+    if (n < 0 || n > 0x3fffffffLL || bytes_a < 0 || bytes_b < 0) RD_FAIL(RD_E_INVALID, "rd_region_format: bad n or text bytes");
+    if (rec_stride != 1 && rec_stride != 2) RD_FAIL(RD_E_INVALID, "rd_region_format: rec_stride must be 1 or 2; got %lld", (long long)rec_stride);
+    if (max_len < 1 || max_len > MAX_LEN_LIMIT) RD_FAIL(RD_E_INVALID, "rd_region_format: max_len=%d out of range [1,%d]", max_len, MAX_LEN_LIMIT);
+    if (!info) RD_FAIL(RD_E_INVALID, "rd_region_format: null info");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        RD_HIP(hipMemsetAsync(info, 0, 8 * sizeof(int64_t), st));
+        return RD_OK;
+    }
+    const int mates = text_b ? 2 : 1;
+    if (!text_a || !rec_start_a || !seq_len_a || !win_first_a || !win_logits_a || !out || !workspace) RD_FAIL(RD_E_INVALID, "rd_region_format: null pointer");
+    if (mates == 2 && (!rec_start_b || !seq_len_b || !win_first_b || !win_logits_b)) RD_FAIL(RD_E_INVALID, "rd_region_format: null pointer (mate 2)");
+    if (((uintptr_t)workspace & 255) || ((uintptr_t)out & 15)) RD_FAIL(RD_E_INVALID, "rd_region_format: workspace must be 256-byte aligned, out 16-byte aligned");
+    if (((uintptr_t)win_logits_a | (uintptr_t)win_logits_b) & 7) RD_FAIL(RD_E_INVALID, "rd_region_format: win_logits must be 8-byte aligned");
+    const int64_t units = n * mates;
+    const RegionWs p = region_ws(workspace, n, units, workspace_bytes);
+    if (workspace_bytes < p.fixed + RG_LINE_SLACK) RD_FAIL(RD_E_WORKSPACE, "rd_region_format: workspace too small: %zu < %zu", workspace_bytes, p.fixed + RG_LINE_SLACK);
+    const RgMate ma = {text_a, bytes_a, rec_start_a, seq_len_a, win_first_a, (const float2 *)win_logits_a};
+    const RgMate mb = {text_b, bytes_b, rec_start_b, seq_len_b, win_first_b, (const float2 *)win_logits_b};
+    const int64_t cap = (int64_t)(out_cap < (size_t)INT64_MAX ? out_cap : (size_t)INT64_MAX);
+    RD_HIP(hipMemsetAsync(p.cnt, 0, (size_t)((char *)p.fault - (char *)p.cnt) + sizeof(int32_t), st));     // (the counters and the fault word)
+    hipLaunchKernelGGL(rd_region_count_kernel, dim3(p.nb), dim3(256), 0, st, ma, mb, mates, rec_stride, n, (int64_t)max_len, p.unit_bytes, p.unit_lines, p.idlen,
+                       p.bsum_bytes, p.bsum_lines, p.cnt, p.fault);
+    hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, p.bsum_bytes, p.nb, p.tot_bytes, (int64_t)INT64_MAX);
+    hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, p.bsum_lines, p.nb, p.tot_lines, (int64_t)INT64_MAX);
+    hipLaunchKernelGGL(rd_region_off_kernel, dim3(p.nb), dim3(256), 0, st, p.unit_bytes, p.unit_lines, units, p.bsum_bytes, p.bsum_lines, p.tot_bytes, p.tot_lines,
+                       p.cnt, p.fault, cap, p.line_cap, info);
+    hipLaunchKernelGGL(rd_region_lines_kernel, dim3(p.nb), dim3(256), 0, st, ma, mb, mates, n, (int64_t)max_len, p.unit_bytes, p.unit_lines, p.idlen, info, p.line_cap,
+                       p.line_off, p.line_unit, p.line_start, p.line_end, p.line_wq);
+    const int64_t tiles = (p.line_cap + RG_LINES - 1) / RG_LINES;
+    hipLaunchKernelGGL(rd_region_write_kernel, dim3((unsigned)(tiles < 1 ? 1 : tiles > 4096 ? 4096 : tiles)), dim3(256), 0, st, ma, mb, mates, rec_stride,
+                       p.unit_lines, units, p.idlen, p.line_off, p.line_unit, p.line_start, p.line_end, p.line_wq, out, info);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }

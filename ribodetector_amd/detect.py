@@ -27,6 +27,9 @@ checks the mates' ids, and from there on the run is the paired-end run (under se
 window table of a chunk is planned and written on the copy stream (rd_window_plan / rd_window_fill, csrc/rd_windows.hpp; windows.py has
 the rule), rd_classify runs over it as it runs over a read table, and the post stream fuses the windows' final logits into one pair of
 logits per read (rd_window_fuse); everything behind that - pair fusion, outputs, report, summary - sees reads.
+--regions (an extension, with --windows): what the windows said before they were fused - the maximal runs of rRNA windows of every read,
+as intervals in the read's bases, one text line each (regions.py has the rule; rd_region_format, csrc/rd_regions.hpp, formats a chunk's
+lines on the post stream where the windows' final logits are). The lines travel like the per-read report's, as pieces of one more file.
 """
 import argparse
 import functools
@@ -46,6 +49,7 @@ from . import __version__
 from . import _native as _native_mod
 from . import dist as rdist
 from . import gz as _gzmod
+from . import regions as _regmod
 from . import summary as _summod
 from . import windows as _winmod
 from .data_loader import device_reader as dr
@@ -78,6 +82,8 @@ def part_path(path, rank):
 
 
 REPORT = (0, None)      # the --read_report among the (mate, label) output files: mate 1's writer appends it, it holds no label's records
+REGIONS = (0, "regions")        # the --regions file, likewise
+TEXT_FILES = (REPORT, REGIONS)  # files of text made on the device, not of a label's records
 
 
 def _pinned(t):
@@ -225,6 +231,9 @@ class Predictor:
         self._summary = None                     # --summary: summary.DeviceSummary (run_with_chunks)
         self._windows = None                     # --windows: {"stride", "max_per_read", "fuse"} (stride None = -l); detect() sets it
         self._win_classified = [0, 0]            # windows this rank classified, per mate
+        self._regions = False                    # --regions: a piece of region lines per chunk (run_with_chunks)
+        self._reg_counts = [0, 0, 0, 0]          # this rank's regions of mate 1 / 2 and reads of mate 1 / 2 with a region
+        self.regions_repeats = 0                 # chunks whose lines did not fit the reserved bytes and were formatted again
         self._install_cleanup()
 
     @property
@@ -513,6 +522,10 @@ class Predictor:
             pieces = self._select_chunk(chunks, dev_in, labels, lo, hi, on_dev, pairs)
             if self._report is not None:
                 pieces[REPORT] = self._report_chunk(chunks, dev_in, outs, labels, lo, hi, pairs)
+            regions = None
+            if self._regions:
+                regions = self._regions_chunk(chunks, dev_in, plans, lo, hi, pairs)
+                pieces[REGIONS] = [regions["piece"]]
             sum_info = None
             if self._summary is not None:           # --summary: this rank's units of the chunk, counted where they are (rd_summary_accumulate)
                 sum_info = _pinned(self._summary.add(dev_in[0], outs[0][0], dev_in[1] if self.is_paired else None,
@@ -523,7 +536,8 @@ class Predictor:
             done = _native_mod.new_event()
             done.record(post)
         return {"n": n, "bounds": bounds, "labels": labels, "host": host, "finish": finish, "done": done, "keep": (dev_in, outs, plans),
-                "pieces": pieces, "pairs": pairs, "chunk": chunks[0], "totals": [c.total for c in chunks] if on_dev else (), "summary": sum_info}
+                "pieces": pieces, "pairs": pairs, "chunk": chunks[0], "totals": [c.total for c in chunks] if on_dev else (), "summary": sum_info,
+                "regions": regions}
 
     def _select_chunk(self, chunks, dev_in, labels, lo, hi, on_dev, pairs=None):
         """{(mate, label): [Piece]}: the label files whose records of this chunk are selected on the device, on the post stream beside
@@ -580,14 +594,69 @@ class Predictor:
             piece = Piece(out, _pinned(ginfo), False, fault, "report", fallback=piece)
         return [piece]
 
+    def _regions_chunk(self, chunks, dev_in, plans, lo, hi, pairs=None, need=None):
+        """--regions: the piece of the region lines of units [lo, hi) of the chunk, formatted where the records' text, the reads'
+        lengths, the window plans and the windows' final logits already are (rd_region_format, on the post stream after the float64
+        pass). Own ring of buffers. The lines have no bound in the text's bytes, so a hint sizes the buffer (RD_REGIONS_HINT, else
+        regions.default_hint) and _finish_regions formats the chunk again - need = the bytes the first call asked for - when it was too
+        small. A .gz file: the text goes to the host's writer, which deflates it."""
+        if pairs is None:
+            tabs = [self._device_text(chunks[e], dev_in[e][0], lo, hi) for e in range(len(dev_in))]
+            stride = 1
+        else:                                       # one text, one record table: mate 2's records are the odd entries
+            tabs, stride = [(pairs["text"], pairs["rec_start"]), (pairs["text"], pairs["rec_start"][1:])], 2
+        args = []
+        for (text, rs), (_, _, ln), plan in zip(tabs, dev_in, plans):
+            args += [text, rs, ln, plan]
+        if need is None:
+            ring = self._reg_seq % self.GZ_RING
+            self._reg_seq += 1
+            text_bytes = sum(int(t.numel()) for t, _ in tabs[:1 if stride == 2 else 2])
+            cap = _regmod.default_hint(text_bytes, hi - lo, sum(p["total"] for p in plans), len(plans))
+        else:
+            ring, cap = None, int(need)
+        buf = self._reg_out.get(ring)
+        if buf is None or buf.numel() < cap:
+            buf = torch.empty(((cap * 5 // 4 + 255) // 256) * 256, dtype=torch.uint8, device=self.device)
+            if ring is not None:
+                self._reg_out[ring] = buf
+        # (a hint from the environment is taken at its word, also where the ring's buffer has grown beyond it)
+        out, info = self.model.window_regions(*args, rec_stride=stride, out=buf, out_cap=cap if os.environ.get(_regmod.HINT_ENV) and need is None else None)
+        info = _pinned(info)
+        return {"piece": Piece(out, info, True, info, "regions"), "info": info, "again": (chunks, dev_in, plans, lo, hi, pairs)}
+
+    def _finish_regions(self, tk):
+        """the verdict of rd_region_format on this rank's units of a chunk, once the event behind it has passed: the counters are added
+        up; lines that did not fit (fault 1) are formatted once more with the bytes they need, before the piece is handed on"""
+        reg = tk.get("regions")
+        if reg is None:
+            return
+        info = reg["info"]
+        if int(info[3]) == 1:
+            self.regions_repeats += 1
+            post = self._post_stream
+            with torch.cuda.stream(post):
+                reg = self._regions_chunk(*reg["again"], need=int(info[1]))
+                done = _native_mod.new_event()
+                done.record(post)
+            _native_mod.wait_event(done)
+            info = reg["info"]
+            tk["regions"], tk["pieces"][REGIONS] = reg, [reg["piece"]]
+        if int(info[3]):
+            raise RuntimeError("device regions: the chunk's record tables, lengths or window plans do not describe its text (fault %d)" % int(info[3]))
+        for k in range(4):
+            self._reg_counts[k] += int(info[4 + k])
+        tk["regions"] = None                        # (the tables of the chunk are no longer needed)
+
     def collect_chunk(self, tk):
         """Labels of a submitted chunk: int8 numpy on rank 0 (whole chunk, input order), None elsewhere."""
         if self.gathers_labels:
-            if tk["pairs"] is not None or tk["summary"] is not None:     # every rank checks the mates and the counters of its own shard
+            if tk["pairs"] is not None or tk["summary"] is not None or tk["regions"] is not None:     # every rank checks the mates, the counters and the regions of its own shard
                 _native_mod.wait_event(tk["done"])
             if tk["pairs"] is not None:
                 self._check_pairs(tk["chunk"], tk["pairs"])
             self._check_summary(tk)
+            self._finish_regions(tk)
             labels = tk["finish"]()
             if tk["pieces"]:
                 self._gather_pieces(tk)
@@ -599,6 +668,7 @@ class Predictor:
         if tk["pairs"] is not None:
             self._check_pairs(tk["chunk"], tk["pairs"])
         self._check_summary(tk)
+        self._finish_regions(tk)
         return tk["host"].numpy()
 
     @staticmethod
@@ -805,7 +875,7 @@ class Predictor:
         self.ingest = {}                           # per input file: which reader took it, and the device feeder's stage times
         self._copy_stream = _gzmod.acquire_stream(self.device)      # (pooled: the allocator's cache is per stream, gz.acquire_stream)
         self._post_stream = _gzmod.acquire_stream(self.device)
-        self._device_outputs([key for key, _, _ in files if key != REPORT])
+        self._device_outputs([key for key, _, _ in files if key not in TEXT_FILES])
         # writer threads (rank 0; every rank under the sharded parse): one per mate, records of every label file in input order
         errors = []
         writers = [_MateWriter(self, e, [(key, fh) for key, _, fh in files if key[0] == e], errors)
@@ -859,7 +929,7 @@ class Predictor:
         self.thread_cpu_s["main"] = round(time.thread_time() - main_cpu0, 4)
         self._close_arenas()
         if writes:
-            self.writer_threads = sorted({fh.threads for key, _, fh in files if key != REPORT})
+            self.writer_threads = sorted({fh.threads for key, _, fh in files if key not in TEXT_FILES})
             for _, _, fh in files:
                 fh.close()
         if self.sharded_parse:
@@ -881,6 +951,14 @@ class Predictor:
                 self.logger.info('Classified {}{}{}{} windows ({} mode, at most {} per read)'.format(
                     colors.BOLD, colors.OKCYAN, " + ".join(str(x) for x in self._win_total), colors.ENDC, self._windows["fuse"],
                     self._windows["max_per_read"]))
+        if self._regions:                          # likewise: every rank formatted the regions of its own units
+            per_rank = self._all_gather(self._reg_counts) if self.multi else [self._reg_counts]
+            mates = range(2 if self.is_paired else 1)
+            self._reg_total = [[sum(int(r[k + e]) for r in per_rank) for e in mates] for k in (0, 2)]
+            if self.rank == 0:
+                self.logger.info('Wrote {}{}{}{} rRNA regions in {} reads'.format(
+                    colors.BOLD, colors.OKCYAN, " + ".join(str(x) for x in self._reg_total[0]), colors.ENDC,
+                    " + ".join(str(x) for x in self._reg_total[1])))
         if self._summary is not None:
             self._write_summary()
 
@@ -901,7 +979,9 @@ class Predictor:
         doc = _summod.to_json(acc, {"version": __version__, "paired": bool(self.is_paired), "interleaved": self.interleaved, "len": int(self.len),
                                     "ensure": self.args.ensure, "model": self.state_key, "inputs": list(self.input),
                                     "windows": None if self._windows is None else dict(
-                                        self._windows, stride=int(self._windows["stride"] or self.len), classified=list(self._win_total))})
+                                        self._windows, stride=int(self._windows["stride"] or self.len), classified=list(self._win_total),
+                                        **({"regions": list(self._reg_total[0]), "reads_with_regions": list(self._reg_total[1])}
+                                           if self._regions else {}))})
         _summod.write_json(path, doc)
         frac = doc["reads"]["rRNA_fraction"]
         self.logger.info('rRNA fraction: {} (summary: {})'.format("n/a" if frac is None else "%.6f" % frac, path))
@@ -1008,6 +1088,13 @@ class Predictor:
             if self.rank == 0:                 # (the sharded parse: rank 0's part comes first in the joined file)
                 hdr = np.frombuffer(_gzmod.REPORT_HEADER_PE if self.is_paired else _gzmod.REPORT_HEADER_SE, dtype=np.uint8)
                 files[-1][2].write_text(hdr.ctypes.data, hdr.size)
+        reg_path = getattr(self.args, 'regions', None)
+        if reg_path:
+            log('Writing rRNA regions into file: {}{}{}'.format(colors.OKBLUE, reg_path, colors.ENDC))
+            open_(REGIONS[1], [reg_path])
+            if self.rank == 0:
+                hdr = np.frombuffer(_regmod.HEADER, dtype=np.uint8)
+                files[-1][2].write_text(hdr.ctypes.data, hdr.size)
         return files
 
     def _device_outputs(self, out_files):
@@ -1030,6 +1117,9 @@ class Predictor:
         # --summary: the run's QC counters, one int64 array per rank that every chunk adds to on the post stream
         self._summary = _summod.DeviceSummary(self.device) if getattr(self.args, 'summary', None) else None
         self._win_classified = [0, 0]
+        # --regions: the lines of every chunk, formatted on the device; mate 1's writer appends the pieces (and deflates a .gz file)
+        self._regions = bool(getattr(self.args, 'regions', None))
+        self._reg_out, self._reg_seq, self._reg_counts, self.regions_repeats = {}, 0, [0, 0, 0, 0], 0
         if self._gz_files or self._rep_gz:
             self._gz = _gzmod.DeviceGzip(self.device)
 
@@ -1119,6 +1209,8 @@ class Predictor:
         check_summary(getattr(self.args, 'summary', None), self.output, self.rrna, self.is_paired, self.args.ensure,
                       getattr(self.args, 'read_report', None))
         self._windows = check_windows(self.args)
+        check_regions(getattr(self.args, 'regions', None), self._windows is not None, self.output, self.rrna, self.is_paired, self.args.ensure,
+                      getattr(self.args, 'read_report', None), getattr(self.args, 'summary', None))
         # reference batch-size heuristic (detect.py:558-568); kept because --chunk_size is expressed in these batches
         denom = (2 * self.len * 6.4) if self.is_paired else (self.len * 6.4)
         self.batch_size = 2 ** math.floor(math.log2(((self.args.memory - 2) * 1024 * 1024) / denom))
@@ -1225,6 +1317,22 @@ def check_windows(args):
     return {"stride": stride, "max_per_read": int(most), "fuse": fuse}
 
 
+def check_regions(path, windows, output=None, rrna=None, is_paired=False, ensure="none", read_report=None, summary=None):
+    """--regions needs --windows and must not name a file the run writes anyway: an -o / -r file, an '<out>.unclassified.gz' file (-e
+    both, pairs), the --read_report or the --summary. Checked before anything touches a device."""
+    if not path:
+        return
+    if not windows:
+        raise RuntimeError("--regions needs --windows")
+    taken = [(o, "an output sequence file (-o / -r)") for o in list(output or []) + list(rrna or [])]
+    if is_paired and ensure == 'both':
+        taken += [(o + '.unclassified.gz', "the unclassified pairs' output file") for o in output or []]
+    taken += [(o, what) for o, what in ((read_report, "the --read_report file"), (summary, "the --summary file")) if o]
+    for o, what in taken:
+        if os.path.abspath(path) == os.path.abspath(o):
+            raise RuntimeError("--regions {} is also {}".format(path, what))
+
+
 def build_parser():
     args = argparse.ArgumentParser(description='rRNA sequence detector', formatter_class=RawTextHelpFormatter)
     args.add_argument('-c', '--config', default=None, type=str, help='Path of config file')
@@ -1283,6 +1391,13 @@ none: give label based on the mean probability of read pair.
     args.add_argument('--window_fuse', default=None, type=str, choices=['mean', 'max'],
                       help='(extension) with --windows: mean = the mean of the windows\' logits (default); max = the logits of the window\n'
                            'with the largest rRNA margin ("rRNA if any stretch of the read is")')
+    args.add_argument('--regions', default=None, type=str,
+                      help='(extension) with --windows: write where the rRNA is inside the reads to this file, one line per region:\n'
+                           '  #read_id<TAB>start<TAB>end<TAB>mate<TAB>windows<TAB>p_rrna_max\n'
+                           'a region = a maximal run of consecutive windows of one read whose own logits say rRNA, as the interval\n'
+                           '[start, end) in 0-based bases of that read; mate = 1 or 2 (read_id is that mate\'s); windows = the windows\n'
+                           'of the run; p_rrna_max = the largest p_rrna among them. Independent of -e and --window_fuse.\n'
+                           'gzip-compressed when the name ends with gz.')
     args.add_argument('--no_mate_check', action='store_true', help='(extension) with --interleaved: do not compare the ids of the mates')
     args.add_argument('-v', '--version', action='version', version='%(prog)s {version}'.format(version=__version__))
     return args
@@ -1293,6 +1408,7 @@ def main(argv=None, log_level=None):
     config_file = os.path.join(cd, 'config.json') if args.config is None else args.config
     config = ConfigParser.from_json(config_file)
     check_windows(args)                          # (before the model is loaded: nothing has touched a device yet)
+    check_regions(getattr(args, 'regions', None), getattr(args, 'windows', False))
     seq_pred = Predictor(config, args, log_level=log_level)
     try:
         t0 = time.perf_counter()

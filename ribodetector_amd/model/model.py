@@ -431,6 +431,47 @@ class SeqModel:
         logits, labels = self.window_fuse(plan, fuse, want_labels=want_labels)
         return logits, labels, total
 
+    def window_regions(self, arena_a, rec_start_a, lens_a, plan_a, arena_b=None, rec_start_b=None, lens_b=None, plan_b=None, rec_stride=1,
+                       out_cap=None, out=None):
+        """The rRNA regions of the reads of one or two plans as text lines (rd_region_format, csrc/rd_regions.hpp; regions.py has the rule
+        and the line format) on the current stream, which must see the windows' FINAL logits (sync_results()). arena_x: the text that
+        holds mate x's records; rec_start_x int64 on the device: record i starts at rec_start_x[i * rec_stride] and ends at the next entry;
+        lens_x int32[n]; plan_x: a plan with "win_logits" (window_plan / window_table / classify_window_table). arena_b None = single-end.
+        out_cap: the bytes reserved for the lines (None: regions.default_hint), or `out`, a uint8 device buffer to write into. Returns
+        (out, info): info int64[8] on the device = {units, bytes, 0, fault, regions of mate 1, of mate 2, reads of mate 1 with a region,
+        of mate 2}; fault 1 = the lines need info[1] bytes, more than out holds - call again with that much; fault 2 = the tables do not
+        describe the text or the windows. Nothing is written on a fault."""
+        from .. import regions as R
+        n = plan_a["n"]
+        paired = arena_b is not None
+        mates = [(arena_a, rec_start_a, lens_a, plan_a)] + ([(arena_b, rec_start_b, lens_b, plan_b)] if paired else [])
+        for text, rs, ln, plan in mates:
+            if plan["n"] != n or plan["max_len"] != plan_a["max_len"] or "win_logits" not in plan:
+                raise RuntimeError("window_regions: the plans must be classified plans of the same reads")
+            if text.dtype != torch.uint8 or not text.is_cuda or rs.dtype != torch.int64 or not rs.is_cuda or not rs.is_contiguous() \
+                    or rs.numel() < (n - 1) * rec_stride + 2 or ln.dtype != torch.int32 or not ln.is_cuda or not ln.is_contiguous() or ln.numel() < n:
+                raise TypeError("window_regions: text uint8, rec_start int64 (n * rec_stride + 1 entries) and lens int32[n] CUDA tensors")
+        total = sum(p["total"] for _, _, _, p in mates)
+        lib = N.lib()
+        if out is None:
+            if out_cap is None:
+                out_cap = R.default_hint(sum(int(t.numel()) for t, _, _, _ in mates[:1 if rec_stride == 2 else 2]), n, total, len(mates))
+            out = torch.empty(((int(out_cap) + 255) // 256) * 256, dtype=torch.uint8, device=self.device)
+            out_cap = int(out_cap)
+        else:
+            out_cap = int(out.numel()) if out_cap is None else min(int(out_cap), int(out.numel()))
+        info = torch.empty(8, dtype=torch.int64, device=self.device)
+        ws = torch.empty(max(int(lib.rd_region_workspace_bytes(n, total)), 256), dtype=torch.uint8, device=self.device)
+        args = []
+        for text, rs, ln, plan in mates:
+            args += [N.ptr(text), int(text.numel()), N.ptr(rs), N.ptr(ln), N.ptr(plan["win_first"]), N.ptr(plan["win_logits"])]
+        if not paired:
+            args += [None, 0, None, None, None, None]
+        with torch.cuda.device(self.device):
+            N.check(lib.rd_region_format(*args, int(rec_stride), n, plan_a["max_len"], N.ptr(out), out_cap, N.ptr(info), N.ptr(ws), ws.numel(),
+                                         N.stream_ptr(self.device)), "rd_region_format")
+        return out, info              # (ws goes back to the pool of the stream it was taken from: reused behind this call only)
+
     # ---- reference-compatible call --------------------------------------------------------------------
     def forward2(self, x):
         """pack_seq=false entry of the reference (model/model.py:40-50 forward2 + last_pad_out_items :67-72): x is a padded
