@@ -322,6 +322,31 @@ RD_API int rd_fasta_gather(const uint8_t *norm, const int64_t *rec_tab, const in
                     int64_t *seq_off, int32_t *seq_len, void *stream);
 RD_API int rd_fasta_sample(const int64_t *rec_tab, const rd_fq_summary *summary, int64_t every, int32_t *samples, int64_t cap, void *stream);
 
+/* BAM records on the device: the inflated bytes of a BAM file behind its header (BGZF members inflated by rd_gz_inflate_members, or
+ * host-inflated bytes copied there) framed and RE-WRITTEN as FASTQ text - '@' name '\n' SEQ '\n' '+' '\n' QUAL '\n' per record, the rule of
+ * ribodetector_amd/bam.py: 4-bit bases to letters, quality min(q, 93) + 33 ('"' where absent), flag 0x10 reverse-complemented, flag 0x900
+ * (secondary / supplementary) skipped. text / pad / end / prev_text / prev / final / summary as rd_fastq_index: the carry is the raw
+ * bytes behind the last complete record. norm / rec_tab / hdr_tab as rd_fasta_index, over four-line records: hdr_tab[r] = the length of
+ * the header line ('@' included), the bases of record r = [rec_tab[r] + hdr_tab[r] + 1, + (record bytes - hdr_tab[r] - 5) / 2).
+ * norm_cap >= 4 * (end - begin) / 3 + 64 and cap_records >= (end - begin) / 37 + 2 are always enough; smaller ones: RD_FQ_LINES.
+ * summary: n_records = records delivered, n_lines = records walked (the skipped ones included), reserved = bytes of `norm`, dirty =
+ * the segments of RD_BAM_SEGMENT bytes (counted from `begin`) whose speculative framing the in-order pass had to repeat (the tables
+ * are those of a serial walk whatever that number is); status RD_BAM_RECORD: record `bad_record` (counting walked records) is
+ * ill-formed - block_size < 32, lengths that do not fit in it, an empty name or one without its NUL; RD_BAM_TRUNCATED: a final batch
+ * ends inside a record. In both the n_records in front of the damage are in the tables and can be gathered. No length of the data
+ * is followed outside [begin, end). rd_bam_gather / rd_bam_sample: as rd_fasta_gather / rd_fasta_sample. */
+#define RD_BAM_RECORD 6
+#define RD_BAM_TRUNCATED 7
+#define RD_BAM_SEGMENT 32768
+RD_API size_t rd_bam_index_workspace_bytes(int64_t text_end);
+RD_API int rd_bam_index(uint8_t *text, int64_t pad, int64_t end, const uint8_t *prev_text, const rd_fq_summary *prev, int32_t final, uint8_t *norm,
+                 int64_t norm_cap, int64_t *rec_tab, int32_t *hdr_tab, int64_t cap_records, rd_fq_summary *summary, void *workspace,
+                 size_t workspace_bytes, void *stream);
+RD_API int rd_bam_gather(const uint8_t *norm, const int64_t *rec_tab, const int32_t *hdr_tab, const rd_fq_summary *summary, int64_t rec_lo, int64_t rec_hi,
+                  int64_t max_bytes, uint8_t *out_text, int64_t out_cap, const int64_t *cursor_in, int64_t *cursor_out, int64_t *rec_start,
+                  int64_t *seq_off, int32_t *seq_len, void *stream);
+RD_API int rd_bam_sample(const int64_t *rec_tab, const rd_fq_summary *summary, int64_t every, int32_t *samples, int64_t cap, void *stream);
+
 /* The records of a chunk that carry one label as ONE contiguous text in `out` [dev, 16-byte aligned], in input order - what the
  * reference's writer joins on the host (detect.py:485-492: fh.write('\n'.join(selected) + '\n')) - for plain (uncompressed) outputs of
  * chunks whose text lives on the device; arguments as rd_gz_compress_selected. info [dev] int64[4]: info[1] = bytes written,

@@ -1,0 +1,228 @@
+"""Unaligned (or aligned) BAM as an input format: the rule in plain Python - what a record is, which records count, and the FASTQ text
+a record becomes. The device side is csrc/rd_bam_index.hpp behind the C ABI rd_bam_index / rd_bam_gather / rd_bam_sample
+(data_loader/device_reader.BamIndexer); every table it writes equals the serial walk below. Nothing here touches a GPU.
+
+A BAM file is a BGZF file (gzip members that carry their size). All integers little-endian. Inflated and concatenated:
+    magic "BAM\\1", l_text:int32, text[l_text], n_ref:int32, n_ref x (l_name:int32, name[l_name], l_ref:int32)        the header
+    then records up to the end of the data. A record at offset p:
+    p+0 block_size:int32 (bytes of the record BEHIND this field)   p+4 refID:int32   p+8 pos:int32   p+12 l_read_name:uint8 (with the NUL)
+    p+13 mapq:uint8   p+14 bin:uint16   p+16 n_cigar_op:uint16   p+18 flag:uint16   p+20 l_seq:uint32   p+24 next_refID:int32
+    p+28 next_pos:int32   p+32 tlen:int32   p+36 read_name, cigar[4 n_cigar_op], seq[(l_seq + 1) / 2], qual[l_seq], tags to p + 4 + block_size
+    base i = high nibble of seq[i / 2] for even i, else the low one; code c = "=ACMGRSVTWYHKDBN"[c]
+    well-formed: 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq <= block_size, l_read_name >= 1, read_name ends in NUL.
+
+The walk (records): at p == end the data is over. Fewer than 4 bytes left, or p + 4 + block_size > end: the data ends inside a record
+("truncated BAM record at end of file"). block_size < 32, or a record that is not well-formed: "malformed BAM record N", N counting
+every record of the file from 0. Else the next record starts at p + 4 + block_size.
+
+Record -> FASTQ text (fastq_text):  '@' name-without-NUL '\\n' SEQ '\\n' '+' '\\n' QUAL '\\n'  = 2 l_seq + l_read_name + 5 bytes.
+QUAL[i] = min(qual[i], 93) + 33; qualities absent (l_seq > 0 and qual[0] == 0xFF): every QUAL[i] = '"'. flag & 0x10: SEQ reverse-
+complemented (the complement of code c is the 4-bit bit reversal of c: "=TGKCYSBAWRDMHVN"[c]) and QUAL reversed, as samtools fastq
+does. flag & 0x900 (secondary / supplementary): the record is skipped - each read appears once. Tags, CIGAR, mapq, references: ignored.
+"""
+import struct
+import zlib
+
+from . import _native as N
+
+SEGMENT = N.BAM_SEGMENT          # bytes per segment of the device framing (RD_BAM_SEGMENT), counted from the first record of a batch
+MAGIC = b"BAM\1"
+CODES = b"=ACMGRSVTWYHKDBN"
+COMPLEMENT = b"=TGKCYSBAWRDMHVN"
+SKIP_FLAGS = 0x900
+MALFORMED = "malformed BAM record %d"
+TRUNCATED = "truncated BAM record at end of file"
+EOF_MEMBER = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def header_len(data):
+    """the length of the header at the start of `data` (inflated bytes); None while the header is not complete; ValueError: bad magic"""
+    if bytes(data[:4]) != MAGIC[:len(data[:4])]:
+        raise ValueError("not a BAM file (the inflated data does not start with 'BAM\\1')")
+    if len(data) < 8:
+        return None
+    l_text = struct.unpack_from("<i", data, 4)[0]
+    if l_text < 0:
+        raise ValueError("not a BAM file (negative header text length)")
+    p = 8 + l_text
+    if len(data) < p + 4:
+        return None
+    n_ref = struct.unpack_from("<i", data, p)[0]
+    if n_ref < 0:
+        raise ValueError("not a BAM file (negative reference count)")
+    p += 4
+    for _ in range(n_ref):
+        if len(data) < p + 4:
+            return None
+        l_name = struct.unpack_from("<i", data, p)[0]
+        if l_name < 0:
+            raise ValueError("not a BAM file (negative reference name length)")
+        p += 4 + l_name + 4
+    return p if len(data) >= p else None
+
+
+def header_bytes(path):
+    """the header's length in inflated bytes: host zlib over the leading gzip members until the header is complete. ValueError on bad
+    magic or a header the file ends in"""
+    data = bytearray()
+    with open(path, "rb") as fh:
+        d = zlib.decompressobj(31)
+        raw = b""
+        while True:
+            if not raw:
+                raw = fh.read(1 << 16)
+                if not raw:
+                    break
+            try:
+                data += d.decompress(raw)
+            except zlib.error as e:
+                raise ValueError("%s: %s" % (path, e))
+            raw = b""
+            if d.eof:
+                raw, d = d.unused_data, zlib.decompressobj(31)
+            n = header_len(data)
+            if n is not None:
+                return n
+    header_len(data)
+    raise ValueError("truncated BAM header")
+
+
+class Record:
+    """one record of the walk: where it lies in the data (offset, size with the block_size field) and what the text depends on"""
+    __slots__ = ("offset", "size", "name", "flag", "codes", "qual")
+
+    def __init__(self, offset, size, name, flag, codes, qual):
+        self.offset, self.size, self.name, self.flag, self.codes, self.qual = offset, size, name, flag, codes, qual
+
+    @property
+    def skipped(self):
+        return bool(self.flag & SKIP_FLAGS)
+
+    def fastq(self):
+        codes, qual = self.codes, self.qual
+        if len(qual) and qual[0] == 0xFF:
+            q = b'"' * len(qual)
+        else:
+            q = bytes(min(x, 93) + 33 for x in qual)
+        if self.flag & 0x10:
+            s = bytes(COMPLEMENT[c] for c in reversed(codes))
+            q = q[::-1]
+        else:
+            s = bytes(CODES[c] for c in codes)
+        return b"@" + self.name + b"\n" + s + b"\n+\n" + q + b"\n"
+
+
+def records(data, start=None):
+    """the plain serial walk over the inflated bytes of a BAM file (start: where the records begin; None: behind the header, which
+    `data` then starts with). Yields Record objects - the skipped ones too - and raises ValueError at the damage, behind the records in
+    front of it."""
+    data = bytes(data)
+    p = header_len(data) if start is None else int(start)
+    if p is None:
+        raise ValueError("truncated BAM header")
+    end, k = len(data), 0
+    while p < end:
+        if end - p < 4:
+            raise ValueError(TRUNCATED)
+        block = struct.unpack_from("<i", data, p)[0]
+        if block < 32:
+            raise ValueError(MALFORMED % k)
+        if p + 4 + block > end:
+            raise ValueError(TRUNCATED)
+        l_name, n_cigar, flag, l_seq = data[p + 12], struct.unpack_from("<H", data, p + 16)[0], struct.unpack_from("<H", data, p + 18)[0], \
+            struct.unpack_from("<I", data, p + 20)[0]
+        if 32 + l_name + 4 * n_cigar + (l_seq + 1) // 2 + l_seq > block or l_name < 1 or data[p + 36 + l_name - 1] != 0:
+            raise ValueError(MALFORMED % k)
+        s = p + 36 + l_name + 4 * n_cigar
+        packed = data[s:s + (l_seq + 1) // 2]
+        codes = [(packed[i >> 1] & 15) if i & 1 else (packed[i >> 1] >> 4) for i in range(l_seq)]
+        yield Record(p, 4 + block, data[p + 36:p + 36 + l_name - 1], flag, codes, data[s + (l_seq + 1) // 2:s + (l_seq + 1) // 2 + l_seq])
+        p += 4 + block
+        k += 1
+
+
+def fastq_text(data, start=None):
+    """the FASTQ text of the records of `data` that count (module docstring); raises what records() raises"""
+    return b"".join(r.fastq() for r in records(data, start) if not r.skipped)
+
+
+# ---- a writer that follows the specification (tests and tools make their inputs with it) --------------------------------------------
+
+def _reg2bin(beg, end):
+    end -= 1
+    for shift, base in ((14, 4681), (17, 585), (20, 73), (23, 9), (26, 1)):
+        if beg >> shift == end >> shift:
+            return base + (beg >> shift)
+    return 0
+
+
+_CIGAR_OPS = "MIDNSHP=X"
+
+
+def encode_record(read):
+    """one record as bytes, block_size included. read: bytes (taken as they are - a record made by hand) or a dict with
+    name (bytes, no NUL), seq (the letters of CODES, str or bytes), qual (raw Phred bytes, or None: absent), and optionally flag (4),
+    ref_id / pos / next_ref_id / next_pos (-1), mapq (0), tlen (0), cigar ([(length, op letter)]), tags (bytes, already encoded)"""
+    if isinstance(read, (bytes, bytearray)):
+        return bytes(read)
+    name = bytes(read["name"]) + b"\0"
+    seq = read["seq"].encode() if isinstance(read["seq"], str) else bytes(read["seq"])
+    codes = [CODES.index(c) for c in seq]
+    if len(codes) & 1:
+        codes.append(0)
+    packed = bytes((codes[i] << 4) | codes[i + 1] for i in range(0, len(codes), 2))
+    qual = read.get("qual")
+    qual = b"\xff" * len(seq) if qual is None else bytes(qual)
+    if len(qual) != len(seq) or len(name) > 255:
+        raise ValueError("encode_record: qual and seq differ in length, or the name is longer than 254 bytes")
+    cigar = list(read.get("cigar", ()))
+    pos = int(read.get("pos", -1))
+    ref_len = sum(n for n, op in cigar if op in "MDN=X")
+    body = struct.pack("<iiBBHHHIiii", int(read.get("ref_id", -1)), pos, len(name), int(read.get("mapq", 0)),
+                       _reg2bin(pos, pos + max(ref_len, 1)) if pos >= 0 else 4680, len(cigar), int(read.get("flag", 4)), len(seq),
+                       int(read.get("next_ref_id", -1)), int(read.get("next_pos", -1)), int(read.get("tlen", 0)))
+    body += name + b"".join(struct.pack("<I", (n << 4) | _CIGAR_OPS.index(op)) for n, op in cigar) + packed + qual + bytes(read.get("tags", b""))
+    return struct.pack("<i", len(body)) + body
+
+
+def encode_header(refs=(), text=b""):
+    """the header: refs = [(name bytes, length)]"""
+    out = MAGIC + struct.pack("<i", len(text)) + bytes(text) + struct.pack("<i", len(refs))
+    for name, length in refs:
+        out += struct.pack("<i", len(name) + 1) + bytes(name) + b"\0" + struct.pack("<i", int(length))
+    return out
+
+
+def payload(reads, refs=(), text=b""):
+    """the inflated bytes of the file write_bam writes"""
+    return encode_header(refs, text) + b"".join(encode_record(r) for r in reads)
+
+
+def bgzf_member(data, level=6):
+    """one BGZF member (a gzip member with the 'BC' subfield that holds its size - 1) of `data`, at most 0xff00 bytes"""
+    if len(data) > 0xff00:
+        raise ValueError("bgzf_member: at most 0xff00 bytes per member")
+    c = zlib.compressobj(level, zlib.DEFLATED, -15)
+    body = c.compress(bytes(data)) + c.flush()
+    return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(body) + 25) + body +
+            struct.pack("<II", zlib.crc32(bytes(data)) & 0xffffffff, len(data)))
+
+
+def write_bam(path, reads, *, refs=(), text=b"", level=6, member_bytes=0xff00, eof=True):
+    """a BAM file of `reads` (encode_record) behind a header (refs, text): BGZF members of member_bytes inflated bytes each - an integer, or
+    a sequence of sizes used in order, the last one for the rest (0: an empty member) - and BGZF's 28-byte end-of-file member.
+    Returns the inflated bytes."""
+    data = payload(reads, refs, text)
+    sizes = [member_bytes] if isinstance(member_bytes, int) else list(member_bytes)
+    if not sizes or sizes[-1] < 1 or any(s < 0 or s > 0xff00 for s in sizes):
+        raise ValueError("write_bam: member sizes are in [0, 0xff00], the last one >= 1")
+    with open(path, "wb") as fh:
+        p, k = 0, 0
+        while p < len(data):
+            n = sizes[min(k, len(sizes) - 1)]
+            fh.write(bgzf_member(data[p:p + n], level))
+            p += n
+            k += 1
+        if eof:
+            fh.write(EOF_MEMBER)
+    return data

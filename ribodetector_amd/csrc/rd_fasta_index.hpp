@@ -235,12 +235,19 @@ __global__ __launch_bounds__(FQ_THREADS) void rd_fa_emit_kernel(const uint8_t *_
     }
 }
 
+// BAM: the tables of rd_bam_index (rd_bam_index.hpp) - four-line records ('@' name / bases / '+' / quality), and a batch that ends in a
+// damaged record is framed up to it: the records in front can be gathered
+__device__ __forceinline__ bool fa_tables_valid(int status, bool bam) {
+    return status == RD_FQ_OK || (bam && (status == RD_BAM_RECORD || status == RD_BAM_TRUNCATED));
+}
+
+template <bool BAM>
 __global__ __launch_bounds__(FQ_THREADS) void rd_fa_gather_kernel(const uint8_t *__restrict__ norm, const int64_t *__restrict__ rec_tab, const int32_t *__restrict__ hdr_tab,
                                                                  const FqSummary *__restrict__ sum, int64_t lo, int64_t hi, uint8_t *__restrict__ out_text,
                                                                  int64_t out_cap, const int64_t *__restrict__ cursor_in, int64_t *__restrict__ cursor_out,
                                                                  int64_t *__restrict__ rec_start, int64_t *__restrict__ seq_off, int32_t *__restrict__ seq_len) {
     const int64_t d0 = *cursor_in;
-    const bool ok = sum->status == RD_FQ_OK && hi <= sum->n_records && lo <= hi && d0 >= 0;
+    const bool ok = fa_tables_valid(sum->status, BAM) && hi <= sum->n_records && lo <= hi && d0 >= 0;
     const int64_t src0 = ok ? rec_tab[lo] : 0, src1 = ok ? rec_tab[hi] : 0;
     const int64_t nbytes = src1 - src0;
     const int64_t gtid = (int64_t)blockIdx.x * FQ_THREADS + threadIdx.x, stride = (int64_t)gridDim.x * FQ_THREADS;
@@ -266,7 +273,7 @@ __global__ __launch_bounds__(FQ_THREADS) void rd_fa_gather_kernel(const uint8_t 
         const int64_t rs = rec_tab[r], so = rs + hdr_tab[r] + 1;
         rec_start[i] = rs + shift;
         seq_off[i] = so + shift;
-        seq_len[i] = (int32_t)(rec_tab[r + 1] - 1 - so);
+        seq_len[i] = BAM ? (int32_t)((rec_tab[r + 1] - rs - hdr_tab[r] - 5) / 2) : (int32_t)(rec_tab[r + 1] - 1 - so);
     }
     if (gtid == 0) {
         rec_start[hi - lo] = d1;
@@ -275,9 +282,10 @@ __global__ __launch_bounds__(FQ_THREADS) void rd_fa_gather_kernel(const uint8_t 
 }
 
 // samples[k] = offset in `norm` where record k * every starts (-1 beyond the batch's records)
+template <bool BAM>
 __global__ __launch_bounds__(FQ_THREADS) void rd_fa_sample_kernel(const int64_t *__restrict__ rec_tab, const FqSummary *__restrict__ sum, int64_t every,
                                                                  int32_t *__restrict__ samples, int64_t cap) {
-    const int64_t n = sum->status == RD_FQ_OK ? sum->n_records : -1;
+    const int64_t n = fa_tables_valid(sum->status, BAM) ? sum->n_records : -1;
     const int64_t stride = (int64_t)gridDim.x * FQ_THREADS;
     for (int64_t k = (int64_t)blockIdx.x * FQ_THREADS + threadIdx.x; k < cap; k += stride) samples[k] = k * every <= n ? (int32_t)rec_tab[k * every] : -1;
 }

@@ -86,6 +86,8 @@ __device__ __forceinline__ uint32_t fq_block_scan(uint32_t v, uint32_t *sh, uint
     return base + inc - v;
 }
 
+// TEXT: the window holds lines (FASTQ, FASTA); false: binary records (BAM, rd_bam_index.hpp) - no '\n' is appended
+template <bool TEXT>
 __global__ __launch_bounds__(FQ_THREADS) void rd_fq_begin_kernel(uint8_t *__restrict__ text, int64_t pad, int64_t end, const uint8_t *__restrict__ prev_text,
                                                                 const FqSummary *__restrict__ prev, int final, FqSummary *__restrict__ sum) {
     __shared__ int64_t s_begin;
@@ -111,7 +113,7 @@ __global__ __launch_bounds__(FQ_THREADS) void rd_fq_begin_kernel(uint8_t *__rest
     __syncthreads();
     if (threadIdx.x == 0) {
         int64_t e = end;
-        if (final && e > begin && text[e - 1] != '\n') text[e++] = '\n';      // the last line of a file may lack its terminator
+        if (TEXT && final && e > begin && text[e - 1] != '\n') text[e++] = '\n';      // the last line of a file may lack its terminator
         sum->begin = begin;
         sum->end = e;
         sum->n_lines = sum->n_records = 0;
@@ -358,7 +360,7 @@ int fq_index_check(const char *fn, const uint8_t *text, int64_t pad, int64_t end
 // the line table of a batch: where its text begins behind the carry, newlines per tile, their scan, line_end[]
 void fq_line_table(uint8_t *text, int64_t pad, int64_t end, const uint8_t *prev_text, const rd_fq_summary *prev, int32_t final, int32_t *line_end, int64_t cap_lines,
                    FqSummary *sum, const FqWs &w, hipStream_t st) {
-    hipLaunchKernelGGL(rd_fq_begin_kernel, dim3(1), dim3(FQ_THREADS), 0, st, text, pad, end, prev_text, (const FqSummary *)prev, (int)final, sum);
+    hipLaunchKernelGGL(rd_fq_begin_kernel<true>, dim3(1), dim3(FQ_THREADS), 0, st, text, pad, end, prev_text, (const FqSummary *)prev, (int)final, sum);
     hipLaunchKernelGGL(rd_fq_count_kernel, dim3(w.ntiles), dim3(FQ_THREADS), 0, st, text, sum, w.tiles);
     hipLaunchKernelGGL(rd_fq_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, st, w.tiles, w.ntiles, sum, cap_lines);
     hipLaunchKernelGGL(rd_fq_fill_kernel, dim3(w.ntiles), dim3(FQ_THREADS), 0, st, text, sum, w.tiles, line_end);

@@ -45,6 +45,7 @@
 #include "rd_inflate_stream.hpp"
 #include "rd_fastq_index.hpp"
 #include "rd_fasta_index.hpp"
+#include "rd_bam_index.hpp"
 #include "rd_report.hpp"
 #include "rd_pairs.hpp"
 #include "rd_summary.hpp"
@@ -909,12 +910,51 @@ int rd_fasta_index(uint8_t *text, int64_t pad, int64_t end, const uint8_t *prev_
 int rd_fasta_gather(const uint8_t *norm, const int64_t *rec_tab, const int32_t *hdr_tab, const rd_fq_summary *summary, int64_t rec_lo, int64_t rec_hi,
                     int64_t max_bytes, uint8_t *out_text, int64_t out_cap, const int64_t *cursor_in, int64_t *cursor_out, int64_t *rec_start,
                     int64_t *seq_off, int32_t *seq_len, void *stream) {
-    return fq_gather("rd_fasta_gather", rd_fa_gather_kernel, summary, rec_lo, rec_hi, max_bytes, out_text, out_cap, cursor_in, cursor_out, rec_start, seq_off, seq_len,
+    return fq_gather("rd_fasta_gather", rd_fa_gather_kernel<false>, summary, rec_lo, rec_hi, max_bytes, out_text, out_cap, cursor_in, cursor_out, rec_start, seq_off, seq_len,
                      stream, norm, rec_tab, hdr_tab);
 }
 
 int rd_fasta_sample(const int64_t *rec_tab, const rd_fq_summary *summary, int64_t every, int32_t *samples, int64_t cap, void *stream) {
-    return fq_sample("rd_fasta_sample", rd_fa_sample_kernel, rec_tab, summary, every, samples, cap, stream);
+    return fq_sample("rd_fasta_sample", rd_fa_sample_kernel<false>, rec_tab, summary, every, samples, cap, stream);
+}
+
+// ---- BAM records framed and re-written as FASTQ text (rd_bam_index.hpp)
+size_t rd_bam_index_workspace_bytes(int64_t text_end) {
+    if (text_end < 0 || text_end >= 0x7fffffffLL) return 0;
+    return bam_ws(nullptr, text_end).total;
+}
+
+int rd_bam_index(uint8_t *text, int64_t pad, int64_t end, const uint8_t *prev_text, const rd_fq_summary *prev, int32_t final, uint8_t *norm, int64_t norm_cap,
+                 int64_t *rec_tab, int32_t *hdr_tab, int64_t cap_records, rd_fq_summary *summary, void *workspace, size_t workspace_bytes, void *stream) {
+    // (no line table: `text` stands in for it in the checks the three formats share)
+    if (const int rc = fq_index_check("rd_bam_index", text, pad, end, prev_text, prev, (const int32_t *)text, 0, summary, workspace, !norm || !rec_tab || !hdr_tab,
+                                      norm_cap < 0 || cap_records < 1, norm))
+        return rc;
+    const BamWs p = bam_ws(workspace, end);
+    if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "rd_bam_index: workspace too small: %zu < %zu", workspace_bytes, p.total);
+    hipStream_t st = (hipStream_t)stream;
+    FqSummary *sum = (FqSummary *)summary;
+    hipLaunchKernelGGL(rd_fq_begin_kernel<false>, dim3(1), dim3(FQ_THREADS), 0, st, text, pad, end, prev_text, (const FqSummary *)prev, (int)final, sum);
+    hipLaunchKernelGGL(rd_bam_walk_kernel, dim3(p.nseg), dim3(64), 0, st, text, sum, p.seg, p.lists);
+    hipLaunchKernelGGL(rd_bam_stitch_kernel, dim3(1), dim3(64), 0, st, text, sum, p.seg, p.lists, p.nseg, p.seg_rbase, p.seg_nbase, p.seg_cnt, p.sc, (int)final, norm_cap,
+                       cap_records, rec_tab);
+    hipLaunchKernelGGL(rd_bam_table_kernel, dim3(p.nseg), dim3(64), 0, st, text, sum, p.sc, p.lists, p.seg_rbase, p.seg_nbase, p.seg_cnt, rec_tab, hdr_tab, p.src_tab);
+    int64_t grid = (4 * end / 3 + 64) / BAM_EMIT_BYTES + 1;      // (the text of a window is at most 4 / 3 of its bytes)
+    if (grid > 65536) grid = 65536;
+    hipLaunchKernelGGL(rd_bam_emit_kernel, dim3((unsigned)grid), dim3(FQ_THREADS), 0, st, text, sum, rec_tab, p.src_tab, norm, norm_cap);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+int rd_bam_gather(const uint8_t *norm, const int64_t *rec_tab, const int32_t *hdr_tab, const rd_fq_summary *summary, int64_t rec_lo, int64_t rec_hi,
+                  int64_t max_bytes, uint8_t *out_text, int64_t out_cap, const int64_t *cursor_in, int64_t *cursor_out, int64_t *rec_start,
+                  int64_t *seq_off, int32_t *seq_len, void *stream) {
+    return fq_gather("rd_bam_gather", rd_fa_gather_kernel<true>, summary, rec_lo, rec_hi, max_bytes, out_text, out_cap, cursor_in, cursor_out, rec_start, seq_off, seq_len,
+                     stream, norm, rec_tab, hdr_tab);
+}
+
+int rd_bam_sample(const int64_t *rec_tab, const rd_fq_summary *summary, int64_t every, int32_t *samples, int64_t cap, void *stream) {
+    return fq_sample("rd_bam_sample", rd_fa_sample_kernel<true>, rec_tab, summary, every, samples, cap, stream);
 }
 
 // the per-read report of a chunk (rd_report.hpp): one line per record, and the lines' starts as a record table of the report text

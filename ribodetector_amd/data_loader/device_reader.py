@@ -16,6 +16,9 @@ every line rstrip()-ed (a batch with trailing whitespace - CR LF files - is stri
 start with '@', last line may lack its newline, fewer than four blank trailing lines tolerated.
 RD_DEVICE_PARSE=0 keeps the host parser. FASTA: FastaIndexer - the batch is re-written as header / joined upper-case sequence
 (fastx_parser.py:39-55) by rd_fasta_index and indexed there; RD_DEVICE_FASTA=0: the host parser.
+BAM (.bam / .ubam, an extension; the rule is ribodetector_amd/bam.py): a BGZF file like any other up to the batch text; BamIndexer -
+rd_bam_index frames the length-prefixed records of the inflated bytes and re-writes them as FASTQ text, which is what every stage
+behind a chunk sees. The header's inflated bytes are dropped in front of the first batch. There is no host reader for BAM.
 """
 import ctypes as C
 import os
@@ -50,6 +53,8 @@ def device_ingest_kind(path, fmt=None):
     if fx.ingest_env("RD_DEVICE_PARSE", "1") == "0" or not torch.cuda.is_available():
         return None
     fmt = fmt or fx.get_seq_format(path)
+    if fmt == "bam":              # a BGZF file by definition (members that are not: the zlib tail); no host decoders to keep it with
+        return None if fx.ingest_env("RD_DEVICE_INFLATE", "auto") == "0" else "bgzf"
     if not fmt.startswith("fq"):
         # FASTA (round 5: rd_fasta_index re-writes and indexes the batch on the device); RD_DEVICE_FASTA=0 keeps the host parser
         if fx.ingest_env("RD_DEVICE_FASTA", "1") == "0":
@@ -117,7 +122,7 @@ class DeviceChunk:
 
 class _Batch:
     __slots__ = ("text", "line_end", "summary", "host", "event", "slot", "gz_slot", "n", "begin", "end", "consumed", "status", "dirty",
-                 "bad_record", "n_lines", "final", "orig", "samples", "samples_host", "args", "chain", "norm", "rec_tab", "hdr_tab", "norm_end")
+                 "bad_record", "n_lines", "final", "orig", "samples", "samples_host", "args", "chain", "norm", "rec_tab", "hdr_tab", "norm_end", "walked_before")
 
     def bytes_bound(self, lo, hi):
         """an upper bound (tight within 2 * EVERY records) of the text bytes of records [lo, hi)"""
@@ -289,6 +294,11 @@ class FastqIndexer:
             setattr(b, k, getattr(nb, k))
         b.dirty = 0
 
+    def damage(self, b):
+        """a finished batch with status != 0: (the error the stream ends with, the records of the batch in front of the damage)"""
+        good = min(b.n, b.bad_record) if b.status == 1 and b.bad_record >= 0 else (b.n if b.status == 2 else 0)
+        return ValueError(FQ_ERRORS.get(b.status, "FASTQ framing error %d" % b.status)), good
+
     def _gather_piece(self, b, lo, hi, *out):
         """the hook of gather(): records [lo, hi) of batch b appended to the chunk (out: max_bytes, the chunk's text and its size, the
         cursor in and out, where the piece's rec_start / seq_off / seq_len go, the stream)"""
@@ -359,6 +369,61 @@ class FastaIndexer(FastqIndexer):
         N.check(self.lib.rd_fasta_gather(N.ptr(b.norm), N.ptr(b.rec_tab), N.ptr(b.hdr_tab), N.ptr(b.summary), lo, hi, *out), "rd_fasta_gather")
 
 
+class BamIndexer(FastqIndexer):
+    """rd_bam_index / rd_bam_gather behind the interface of FastqIndexer: the inflated bytes of a BAM file (behind its header) are framed
+    - a length-prefixed chain of records, csrc/rd_bam_index.hpp - and RE-WRITTEN on the device into `norm` as FASTQ text (bam.fastq_text)
+    with rec_tab / hdr_tab over it, like FastaIndexer's. The carry of a batch is the raw bytes behind its last complete record. No strip
+    pass: there are no lines in the input. stats: the records walked, and how many of them were skipped (secondary / supplementary)."""
+    _REFRAMED = FastaIndexer._REFRAMED
+
+    line_div = 1 << 30          # (no line table: the few entries index() allocates stay unused)
+    RECORD_DIV = 96             # the record tables of a batch hold window / 96 records (36 + name + 1.5 bytes per base: reads under ~35 bases
+                                # on average overflow them - framed again, full size: window / 37, the smallest well-formed record)
+
+    def __init__(self, device, stream):
+        super().__init__(device, stream)
+        self.walked = 0         # records of the batches finished so far, the skipped ones included: what "malformed BAM record N" counts from
+        self.stats.update({"bam_records": 0, "bam_skipped": 0, "bam_rewalked_segments": 0})
+
+    def _cap_rec(self, window, cap_lines):
+        return window // 37 + 2 if cap_lines >= window + 2 else window // self.RECORD_DIV + 4096
+
+    def _n_samples(self, window, cap_lines):
+        return (self._cap_rec(window, cap_lines) + 2) // EVERY + 3
+
+    def _frame(self, b, start, end, prev, final, window, cap_lines, ns):
+        cap_rec = self._cap_rec(window, cap_lines)
+        norm_cap = ((4 * window // 3 + 64 + 255) // 256) * 256
+        b.norm = torch.empty(norm_cap, dtype=torch.uint8, device=self.device)
+        b.rec_tab = torch.empty(cap_rec, dtype=torch.int64, device=self.device)
+        b.hdr_tab = torch.empty(cap_rec, dtype=torch.int32, device=self.device)
+        ws = torch.empty(max(int(self.lib.rd_bam_index_workspace_bytes(end)), 256), dtype=torch.uint8, device=self.device)
+        N.check(self.lib.rd_bam_index(N.ptr(b.text), start, end, prev[0], prev[1], 1 if final else 0, N.ptr(b.norm), norm_cap, N.ptr(b.rec_tab), N.ptr(b.hdr_tab),
+                                      cap_rec, N.ptr(b.summary), N.ptr(ws), ws.numel(), self._sp()), "rd_bam_index")
+        N.check(self.lib.rd_bam_sample(N.ptr(b.rec_tab), N.ptr(b.summary), EVERY, N.ptr(b.samples), ns, self._sp()), "rd_bam_sample")
+
+    _read = staticmethod(FastaIndexer._read)
+
+    def _finish_tail(self, b):
+        b.walked_before = self.walked
+        if b.status in (0, N.BAM_RECORD, N.BAM_TRUNCATED):
+            self.walked += b.n_lines
+            self.stats["bam_records"] += b.n_lines
+            self.stats["bam_skipped"] += b.n_lines - b.n
+            self.stats["bam_rewalked_segments"] += b.dirty
+
+    def damage(self, b):
+        from .. import bam
+        if b.status == N.BAM_RECORD:
+            return ValueError(bam.MALFORMED % (b.walked_before + b.bad_record)), b.n
+        if b.status == N.BAM_TRUNCATED:
+            return ValueError(bam.TRUNCATED), b.n
+        return super().damage(b)
+
+    def _gather_piece(self, b, lo, hi, *out):
+        N.check(self.lib.rd_bam_gather(N.ptr(b.norm), N.ptr(b.rec_tab), N.ptr(b.hdr_tab), N.ptr(b.summary), lo, hi, *out), "rd_bam_gather")
+
+
 class DeviceFeeder:
     """The producer thread of one input file: file bytes -> batches on the GPU (H2D, members inflated where the file is BGZF, records
     framed), two batches in flight; next_batch() hands them over in order, finished."""
@@ -373,11 +438,13 @@ class DeviceFeeder:
     PLAIN_FIRST = 12 << 20
     SLOTS = 2
 
-    def __init__(self, path, device, compressed, span=None, byte_range=None, fasta=False, keep_empty_tail=False):
+    def __init__(self, path, device, compressed, span=None, byte_range=None, fasta=False, keep_empty_tail=False, bam=False):
         """compressed: the file is BGZF (span = (first file byte, one past the last, text bytes to drop in front, text bytes to
-        deliver) for a rank's share, fastx_parser.BgzfView.file_span); else plain text (byte_range = (start, end), record-aligned)"""
+        deliver) for a rank's share, fastx_parser.BgzfView.file_span); else plain text (byte_range = (start, end), record-aligned).
+        bam: the inflated bytes are a BAM file's - its header is dropped, its records are framed by BamIndexer"""
         self.path, self.device, self.compressed, self.span, self.byte_range = str(path), torch.device(device), compressed, span, byte_range
-        self.fasta, self.keep_empty_tail = bool(fasta), bool(keep_empty_tail)
+        self.fasta, self.keep_empty_tail, self.bam = bool(fasta), bool(keep_empty_tail), bool(bam)
+        self._skip = 0                 # BAM: inflated bytes of the header still to drop in front of the next batch
         self._stop = False
         self.out = queue.Queue(maxsize=self.SLOTS)
         self.slot_free = queue.Queue()
@@ -452,7 +519,7 @@ class DeviceFeeder:
             torch.cuda.set_device(self.device)          # the current device is per thread (and defaults to 0)
             self.stream = gz.acquire_stream(self.device, priority=-1)
             self.dg = gz.DeviceGunzip(self.device, slots=self.SLOTS, stream=self.stream)
-            self.ix = (FastaIndexer if self.fasta else FastqIndexer)(self.device, self.stream)
+            self.ix = (BamIndexer if self.bam else FastaIndexer if self.fasta else FastqIndexer)(self.device, self.stream)
             if self.fasta:
                 self.ix.keep_empty_tail = self.keep_empty_tail
         except BaseException as e:      # noqa: BLE001
@@ -461,6 +528,9 @@ class DeviceFeeder:
             return
         self._ready.set()
         try:
+            if self.bam:                 # (bad magic, a header the file ends in: raised here, in front of the first batch)
+                from .. import bam
+                self._skip = bam.header_bytes(self.path)
             if self.compressed == "stream":
                 self._run_stream()
             elif self.compressed:
@@ -742,7 +812,9 @@ class DeviceFeeder:
         the text shipped to the device in pieces and framed behind the batches in flight"""
         for out in zlib_member_texts(fh, data, lambda: self._stop):
             src = torch.from_numpy(np.frombuffer(out, dtype=np.uint8).copy()).pin_memory()
-            b = self._submit_text(src, len(out), None)
+            skip = min(self._skip, len(out))
+            self._skip -= skip
+            b = self._submit_text(src, len(out), None, start_skip=skip)
             b.orig = src                                  # (keeps the pinned bytes alive until the batch is consumed)
             if not self._put(b):
                 return
@@ -765,7 +837,9 @@ class DeviceFeeder:
                 t3 = time.perf_counter()
                 text = self.ix.alloc_text(ev.out_bytes)
                 dg.submit(bufs[ev.slot], ev.nbytes, ev.n, ev.out_bytes, slot=ev.slot, text_out=text[PAD:PAD + ev.out_bytes])
-                b = self.ix.index(text, PAD + ev.drop, PAD + ev.drop + ev.take)
+                skip = min(self._skip, ev.take)      # (BAM: the header's bytes, in front of the first batches)
+                self._skip -= skip
+                b = self.ix.index(text, PAD + ev.drop + skip, PAD + ev.drop + ev.take)
                 b.slot, b.gz_slot = ev.slot, ev.slot
                 tm["submit"] += time.perf_counter() - t3
                 tm["batches"] += 1
@@ -782,7 +856,8 @@ def get_seq_chunks_device(seq_file, chunk_size=1048576, byte_range=None, first_c
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     torch.cuda.set_device(device)
     kind = device_ingest_kind(seq_file)
-    compressed = "stream" if kind == "stream" else fx.get_seq_format(seq_file).endswith("gz")
+    fmt = fx.get_seq_format(seq_file)
+    compressed = "stream" if kind == "stream" else (fmt.endswith("gz") or fmt == "bam")
     span = None
     keep_tail = False            # a share that ends before the file does (FASTA: its last record counts even without a sequence)
     from . import gz_shard
@@ -799,8 +874,7 @@ def get_seq_chunks_device(seq_file, chunk_size=1048576, byte_range=None, first_c
     if resident is not None:
         feeder = gz_shard.ResidentFeeder(resident)
     else:
-        feeder = DeviceFeeder(seq_file, device, compressed, span=span, byte_range=byte_range, fasta=fx.get_seq_format(seq_file).startswith("fa"),
-                              keep_empty_tail=keep_tail)
+        feeder = DeviceFeeder(seq_file, device, compressed, span=span, byte_range=byte_range, fasta=fmt.startswith("fa"), keep_empty_tail=keep_tail, bam=fmt == "bam")
     skip_left = resident.skip if resident is not None else 0      # (mate files: the records in front of the ranks' common cut went to the rank before)
     want = chunk_size if not first_chunk else max(1, min(int(first_chunk), chunk_size))
     sched = list(schedule) if schedule else None
@@ -839,8 +913,7 @@ def get_seq_chunks_device(seq_file, chunk_size=1048576, byte_range=None, first_c
                     break
                 good = b.n
                 if b.status:             # a malformed record: the chunks in front of it are delivered, then the error
-                    err, eof, framing = ValueError(FQ_ERRORS.get(b.status, "FASTQ framing error %d" % b.status)), True, True
-                    good = min(b.n, b.bad_record) if b.status == 1 and b.bad_record >= 0 else (b.n if b.status == 2 else 0)
+                    (err, good), eof, framing = feeder.ix.damage(b), True, True
                 drop = min(skip_left, good)
                 skip_left -= drop
                 if good > drop:

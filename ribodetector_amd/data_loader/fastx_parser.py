@@ -23,10 +23,11 @@ from .member_batches import TRUNCATED, Tail, error_bytes, member_batches, zlib_m
 
 FA_EXTS = [".fasta", ".fa", ".fna", ".fas"]
 FQ_EXTS = [".fq", ".fastq"]
+BAM_EXTS = [".bam", ".ubam"]      # (an extension of this build: records framed and turned into FASTQ text on the device, ribodetector_amd/bam.py)
 
 
 def get_seq_format(seq_file):
-    """'fa' | 'fq' (+ 'gz') from the file name (reference seq_encoder.py:21-39)."""
+    """'fa' | 'fq' (+ 'gz') from the file name (reference seq_encoder.py:21-39); 'bam' for .bam / .ubam."""
     encoding = guess_type(str(seq_file))[1]
     if encoding is None:
         encoding = ""
@@ -36,6 +37,8 @@ def get_seq_format(seq_file):
         raise ValueError('Unknown file encoding: "{}"'.format(encoding))
     name = Path(seq_file).stem if encoding == "gz" else Path(seq_file).name
     ext = Path(name).suffix
+    if ext in BAM_EXTS and not encoding:
+        return "bam"
     if ext not in FA_EXTS + FQ_EXTS:
         raise ValueError('Unknown extension {}. Only fastq and fasta sequence formats are supported.\n'
                          'And the file must end with one of ".fasta", ".fa", ".fna", ".fas", ".fq", ".fastq"\n'
@@ -492,6 +495,8 @@ class NativeReader:
         self._torch = torch
         self._pin = torch.cuda.is_available()
         fmt = get_seq_format(path)                  # raises ValueError like the reference for unknown extensions
+        if fmt == "bam":
+            raise ValueError("BAM input is read by the device reader only (data_loader/device_reader.py): the host reader has no BAM support")
         self.h = C.c_void_p()
         self._feeder = None
         f = 1 if fmt.startswith("fa") else 0

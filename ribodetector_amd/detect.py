@@ -30,6 +30,9 @@ logits per read (rd_window_fuse); everything behind that - pair fusion, outputs,
 --regions (an extension, with --windows): what the windows said before they were fused - the maximal runs of rRNA windows of every read,
 as intervals in the read's bases, one text line each (regions.py has the rule; rd_region_format, csrc/rd_regions.hpp, formats a chunk's
 lines on the post stream where the windows' final logits are). The lines travel like the per-read report's, as pieces of one more file.
+BAM input (an extension): -i x.bam / x.ubam, in all three layouts of the inputs (one file, two files, --interleaved). The file's BGZF
+members are inflated on the GPU and rd_bam_index (csrc/rd_bam_index.hpp; bam.py has the rule) frames the records and re-writes them as
+FASTQ text, so the chunks are FASTQ chunks and the outputs FASTQ files. One rank, device ingest only (check_bam).
 """
 import argparse
 import functools
@@ -942,6 +945,11 @@ class Predictor:
             if self.is_paired and self.args.ensure == 'both':
                 self.logger.info('Discarded {}{}{}{} unclassified sequences'.format(
                     colors.BOLD, colors.OKCYAN, self.num_unknown, colors.ENDC))
+        for path in self.input:                    # (BAM input is one rank's: check_bam)
+            if fx.get_seq_format(path) == "bam":
+                ix = (self.ingest.get(os.path.basename(str(path))) or {}).get("indexer") or {}
+                self.logger.info('BAM input: {} records, {} secondary/supplementary skipped ({})'.format(
+                    ix.get("bam_records", 0), ix.get("bam_skipped", 0), path))
         if self.interleaved:
             fx.check_even_records(self._records_seen)
         if self._windows is not None:              # every rank classified the windows of its own shard / byte range
@@ -1266,6 +1274,39 @@ def check_file_counts(inputs, output, rrna, interleaved=False):
     return n_in == 2
 
 
+def check_bam(inputs, output, rrna):
+    """BAM input (.bam / .ubam, ribodetector_amd/bam.py): the rules that hold before anything touches a device; returns whether the
+    inputs are BAM. The records become FASTQ text on the device, so the outputs are FASTQ files; there is no host reader for BAM,
+    so the switches and layouts that need one are refused."""
+    def fmt(path):
+        try:
+            return fx.get_seq_format(path)
+        except ValueError:
+            return None                          # (the run reports unknown extensions, as ever)
+    for o in list(output or []) + list(rrna or []):
+        if fmt(o) == "bam":
+            raise RuntimeError("BAM output is not supported: {} (-o / -r take FASTQ names, plain or .gz; checked before anything touches a "
+                               "device)".format(o))
+    kinds = [fmt(p) for p in inputs or []]
+    if "bam" not in kinds:
+        return False
+    if any(k != "bam" for k in kinds):
+        raise RuntimeError("BAM input cannot be mixed with FASTQ / FASTA input files: {} (checked before anything touches a "
+                           "device)".format(", ".join(str(p) for p in inputs)))
+    for o in list(output or []) + list(rrna or []):
+        if fmt(o) not in ("fq", "fqgz"):
+            raise RuntimeError("BAM input is written as FASTQ: {} must end with .fq or .fastq, plain or .gz (checked before anything "
+                               "touches a device)".format(o))
+    for name in ("RD_DEVICE_PARSE", "RD_DEVICE_INFLATE"):
+        if fx.ingest_env(name, "1") == "0":
+            raise RuntimeError("BAM input is framed and inflated on the device only: it cannot run with {}=0 or RD_INGEST=host (checked "
+                               "before anything touches a device)".format(name))
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("BAM input runs on one rank: the multi-rank layouts use the host reader, which has no BAM support (checked "
+                           "before anything touches a device)")
+    return True
+
+
 def check_read_report(path, output, rrna, is_paired, ensure):
     """--read_report must not name a file the run writes anyway: an -o / -r file or an '<out>.unclassified.gz' file (-e both, pairs:
     one per -o path, also when the pairs come from one interleaved file)"""
@@ -1341,7 +1382,8 @@ def build_parser():
     args.add_argument('-l', '--len', type=int, required=True,
                       help='Sequencing read length. Note: the accuracy reduces for reads shorter than 40.')
     args.add_argument('-i', '--input', default=None, type=str, nargs='*', required=True,
-                      help='Path of input sequence files (fasta and fastq), the second file will be considered as second end if two files given.')
+                      help='Path of input sequence files (fasta and fastq), the second file will be considered as second end if two files given.\n'
+                           '(extension) .bam / .ubam files are read too; their records are written as FASTQ.')
     args.add_argument('-o', '--output', default=None, type=str, nargs='*', required=True,
                       help='Path of the output sequence files after rRNAs removal (same number of files as input). \n(Note: 2 times slower to write gz files)')
     args.add_argument('-r', '--rrna', default=None, type=str, nargs='*',
@@ -1409,6 +1451,7 @@ def main(argv=None, log_level=None):
     config = ConfigParser.from_json(config_file)
     check_windows(args)                          # (before the model is loaded: nothing has touched a device yet)
     check_regions(getattr(args, 'regions', None), getattr(args, 'windows', False))
+    check_bam(args.input, args.output, args.rrna)
     seq_pred = Predictor(config, args, log_level=log_level)
     try:
         t0 = time.perf_counter()

@@ -1,0 +1,227 @@
+#!/usr/bin/env python
+"""BAM input against the same reads as BGZF FASTQ, in one process: per measurement one untimed warm-up call of each leg, then `--calls`
+timed calls of each, ALTERNATING the legs (model load excluded: Predictor.timing["detect_s"]). Prints one JSON line per measurement.
+    python tools/bam_bench.py [--reads 4194304] [--long_reads 262144] [--calls 3] [--keep DIR] [--only short|long|kernel] [--trace OUT]
+  short   `--reads` single-end reads of 100 bp: x.bam -> .gz against x.fq.gz (BGZF, the same reads, the same bgzip-style members) -> .gz.
+          The FASTQ leg is the yardstick - the existing path: the BAM leg's median is to be read against that leg's run-to-run spread.
+  long    `--long_reads` reads of 10 kb with --windows, the same two legs
+  kernel  rd_bam_index ALONE on a batch of each shape resident in HBM (the inflated bytes, as the feeder hands them over), 20 calls timed
+          with device events: us per call, the bytes it moves, the fraction of an HBM-bound pass at 8 TB/s that is, and the segments the
+          in-order pass had to walk again. The split over the walk / stitch / table / emit kernels is not visible to events around one
+          call of the C ABI: run this measurement under  rocprofv3 --kernel-trace --output-format csv -d OUT -- python tools/bam_bench.py
+          --only kernel  and print the split with --trace OUT.
+Every fourth record of the BAM files is stored on the reverse strand (flag 0x10, bases reverse-complemented, qualities reversed), so
+that the text the two legs see is the same. The inputs are written by processes that never touch the GPU."""
+import argparse
+import csv
+import glob
+import json
+import os
+import shutil
+import statistics
+import struct
+import sys
+import tempfile
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, ROOT)
+
+SHAPES = {"short": 100, "long": 10000}
+NAME = 11                      # 'r' + 9 digits + NUL
+
+
+def trace_times(root):
+    """({kernel: [us per launch]} of the rd_bam_* kernels and the begin kernel, us of all kernels) in a rocprofv3 --kernel-trace directory"""
+    out, total = {}, 0.0
+    for path in glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True):
+        with open(path) as fh:
+            for r in csv.DictReader(fh):
+                us = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
+                total += us
+                for key in ("rd_bam_", "rd_fq_begin_"):
+                    if key in r["Kernel_Name"]:
+                        out.setdefault(key + r["Kernel_Name"].split(key)[1].split("(")[0].split("<")[0], []).append(us)
+    return out, total
+
+
+def _rows(n, first, length, seed):
+    """(FASTQ text, BAM records) of n reads of `length` (even) bases as two uint8 matrices, one row per read"""
+    import numpy as np
+    from ribodetector_amd import bam, synth
+    arena, _, _ = synth.reads_numpy(n, length, seed=seed)
+    seq = arena.reshape(n, length)
+    rng = np.random.default_rng(seed)
+    phred = np.array([37, 25, 11, 2], np.uint8)[rng.choice(4, size=(n, length), p=[0.90, 0.06, 0.03, 0.01])]      # NovaSeq-like bins
+    idx = first + np.arange(n, dtype=np.int64)
+    name = np.empty((n, NAME), np.uint8)
+    name[:, 0] = ord("r")
+    for k in range(9):
+        name[:, 9 - k] = 48 + (idx // 10 ** k) % 10
+    name[:, 10] = 0
+    fq = np.empty((n, 2 * length + NAME + 5), np.uint8)
+    fq[:, 0] = ord("@")
+    fq[:, 1:NAME] = name[:, :10]
+    fq[:, NAME] = 10
+    fq[:, NAME + 1:NAME + 1 + length] = seq
+    fq[:, NAME + 1 + length:NAME + 4 + length] = np.frombuffer(b"\n+\n", np.uint8)
+    fq[:, NAME + 4 + length:NAME + 4 + 2 * length] = phred + 33
+    fq[:, -1] = 10
+    code = np.zeros(256, np.uint8)
+    for c, ch in enumerate(bam.CODES):
+        code[ch] = c
+    comp = np.zeros(16, np.uint8)
+    for c in range(16):
+        comp[c] = bam.CODES.index(bam.COMPLEMENT[c])
+    codes, qual = code[seq], phred.copy()
+    rev = (idx % 4) == 3
+    codes[rev] = comp[codes[rev]][:, ::-1]
+    qual[rev] = qual[rev][:, ::-1]
+    block = 32 + NAME + length // 2 + length
+    rec = np.empty((n, 4 + block), np.uint8)
+    fixed = struct.pack("<iiiBBHHHIiii", block, -1, -1, NAME, 0, 4680, 0, 4, length, -1, -1, 0)
+    rec[:, :36] = np.frombuffer(fixed, np.uint8)
+    rec[rev, 18] = 4 | 0x10
+    rec[:, 36:36 + NAME] = name
+    rec[:, 36 + NAME:36 + NAME + length // 2] = (codes[:, 0::2] << 4) | codes[:, 1::2]
+    rec[:, 36 + NAME + length // 2:] = qual
+    return fq, rec
+
+
+def _make(job):
+    d, shape, reads = job
+    from ribodetector_amd import bam, synth
+    length = SHAPES[shape]
+    fq_gz, bam_path = os.path.join(d, "%s_%d.fq.gz" % (shape, reads)), os.path.join(d, "%s_%d.bam" % (shape, reads))
+    if os.path.exists(fq_gz) and os.path.exists(bam_path):
+        return
+    step = max(1, (64 << 20) // (2 * length))
+    with open(fq_gz + ".raw", "wb") as f1, open(bam_path + ".raw", "wb") as f2:
+        f2.write(bam.encode_header(text=b"@HD\tVN:1.6\tSO:unsorted\n"))
+        for first in range(0, reads, step):
+            fq, rec = _rows(min(step, reads - first), first, length, seed=1000 + first // step)
+            f1.write(fq.tobytes())
+            f2.write(rec.tobytes())
+    for raw, dst in ((fq_gz + ".raw", fq_gz), (bam_path + ".raw", bam_path)):
+        synth.bgzip_file(raw, dst, level=6, threads=8)
+        os.remove(raw)
+
+
+def make_inputs(d, jobs):
+    import multiprocessing as mp
+    with mp.get_context("spawn").Pool(len(jobs)) as pool:
+        pool.map(_make, [(d,) + j for j in jobs])
+
+
+def timed_legs(argv, calls, units):
+    from ribodetector_amd import detect
+    last = {}
+    for k in argv:
+        detect.main(argv[k], log_level="WARNING")
+    secs = {k: [] for k in argv}
+    for _ in range(calls):
+        for k in argv:
+            last[k] = detect.main(argv[k], log_level="WARNING")
+            secs[k].append(last[k].timing["detect_s"])
+    return {k: sorted(units / s for s in v) for k, v in secs.items()}, last
+
+
+def _mlh(v):
+    return {"median": round(statistics.median(v)), "lowest": round(v[0]), "highest": round(v[-1])}
+
+
+def bench_cli(d, shape, reads, calls):
+    extra = ["--windows", "--chunk_size", "1"] if shape == "long" else []       # (chunks of 32,768 reads: 0.65 GB of text at 10 kb)
+    src = {"bam": os.path.join(d, "%s_%d.bam" % (shape, reads)), "fastq_bgzf": os.path.join(d, "%s_%d.fq.gz" % (shape, reads))}
+    argv = {k: ["-l", "100", "-i", src[k], "-o", os.path.join(d, "o_%s.fq.gz" % k)] + extra for k in src}
+    rate, last = timed_legs(argv, calls, reads)
+    med = {k: statistics.median(v) for k, v in rate.items()}
+    ix = last["bam"].ingest[os.path.basename(src["bam"])]["indexer"]
+    same = all(getattr(last["bam"], a) == getattr(last["fastq_bgzf"], a) for a in ("num_read", "num_rrna", "num_nonrrna"))
+    print(json.dumps({"measurement": shape, "reads": reads, "read_len": SHAPES[shape], "calls": calls,
+                      "flow": "single-end -> .gz" + (", --windows --chunk_size 1" if extra else ""), "input_bytes": {k: os.path.getsize(v) for k, v in src.items()},
+                      "reads_per_s": {k: _mlh(v) for k, v in rate.items()}, "ratio_of_medians": round(med["bam"] / med["fastq_bgzf"], 4),
+                      "bam_median_inside_fastq_spread": bool(rate["fastq_bgzf"][0] <= med["bam"] <= rate["fastq_bgzf"][-1]),
+                      "same_counts": bool(same), "rrna": last["bam"].num_rrna, "bam_records": ix["bam_records"], "bam_skipped": ix["bam_skipped"],
+                      "segments_walked_again": ix["bam_rewalked_segments"], "batches": ix["batches"]}), flush=True)
+
+
+def bench_kernel(calls, batch_bytes=128 << 20):
+    import numpy as np
+    import torch
+    from ribodetector_amd import _native as N
+    lib, dev = N.lib(), torch.device("cuda:0")
+    st = N.stream_ptr(dev)
+    for shape, length in SHAPES.items():
+        size = 36 + NAME + length // 2 + length
+        n = batch_bytes // size
+        step = max(1, (64 << 20) // (2 * length))
+        raw = b"".join(_rows(min(step, n - f), f, length, seed=7 + f // step)[1].tobytes() for f in range(0, n, step))
+        pad, end = 64, 64 + len(raw)
+        text = torch.zeros(((end + 64 + 127) // 64) * 64, dtype=torch.uint8, device=dev)
+        text[pad:end] = torch.from_numpy(np.frombuffer(raw, np.uint8).copy()).to(dev)
+        window = end - pad
+        cap_rec, norm_cap = window // 37 + 2, ((4 * window // 3 + 64 + 255) // 256) * 256
+        norm = torch.empty(norm_cap, dtype=torch.uint8, device=dev)
+        rec_tab, hdr_tab = torch.empty(cap_rec, dtype=torch.int64, device=dev), torch.empty(cap_rec, dtype=torch.int32, device=dev)
+        summary = torch.zeros(8, dtype=torch.int64, device=dev)
+        ws = torch.empty(int(lib.rd_bam_index_workspace_bytes(end)), dtype=torch.uint8, device=dev)
+
+        def index():
+            N.check(lib.rd_bam_index(N.ptr(text), pad, end, None, None, 1, N.ptr(norm), norm_cap, N.ptr(rec_tab), N.ptr(hdr_tab), cap_rec, N.ptr(summary),
+                                     N.ptr(ws), ws.numel(), st), "rd_bam_index")
+        for _ in range(3):
+            index()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(calls + 1)]
+        ev[0].record()
+        for k in range(calls):
+            index()
+            ev[k + 1].record()
+        torch.cuda.synchronize()
+        s = summary.cpu().numpy()
+        status, rewalked, norm_bytes = int(s[6]) & 0xffffffff, (int(s[6]) >> 32) & 0xffffffff, int(s[7])
+        assert status == 0 and int(s[3]) == n and norm_bytes == n * (2 * length + NAME + 5), (status, int(s[3]), n, norm_bytes)
+        us = sorted(ev[k].elapsed_time(ev[k + 1]) * 1e3 for k in range(calls))
+        med = statistics.median(us)
+        # the window is read by the walk (staged once) and again by the emit pass (names, bases, qualities: all but the fixed fields and
+        # tags); `norm` is written once; per record 16 bytes of tables and 8 of the segment lists are written and read
+        moved = 2 * window + norm_bytes + 2 * 24 * n
+        print(json.dumps({"measurement": "kernel", "shape": shape, "read_len": length, "records": n, "window_bytes": window, "norm_bytes": norm_bytes,
+                          "segments": window // N.BAM_SEGMENT + 1, "segments_walked_again": rewalked, "calls": calls,
+                          "us_per_call": {"median": round(med, 1), "lowest": round(us[0], 1), "highest": round(us[-1], 1)}, "bytes_moved": moved,
+                          "GB_per_s": round(moved / med / 1e3, 1), "fraction_of_hbm_bound_pass_at_8TBps": round(moved / 8e12 / (med * 1e-6), 4),
+                          "records_per_s": round(n / (med * 1e-6)), "kernel_split": "not measured here (see --trace)"}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reads", type=int, default=1 << 22, help="reads of the short leg")
+    ap.add_argument("--long_reads", type=int, default=1 << 18, help="reads of the long leg")
+    ap.add_argument("--calls", type=int, default=3)
+    ap.add_argument("--keep", default=None)
+    ap.add_argument("--only", default=None, choices=["short", "long", "kernel"])
+    ap.add_argument("--trace", default=None)
+    a = ap.parse_args()
+    if a.trace:
+        t, total = trace_times(a.trace)
+        print(json.dumps({"all_kernels_us": round(total, 1), "kernel_us": {k: {"launches": len(v), "sum": round(sum(v), 1), "median": round(statistics.median(v), 1),
+                                                                               "largest": round(max(v), 1)} for k, v in sorted(t.items())}}))
+        return
+    which = [a.only] if a.only else ["short", "long", "kernel"]
+    jobs = [(s, n) for s, n in (("short", a.reads), ("long", a.long_reads)) if s in which]
+    d = a.keep or tempfile.mkdtemp(prefix="rdbam", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+    os.makedirs(d, exist_ok=True)
+    try:
+        if jobs:
+            make_inputs(d, jobs)                 # (before anything initialises the GPU)
+        import ribodetector_amd  # noqa: F401
+        for s, n in jobs:
+            bench_cli(d, s, n, a.calls)
+        if "kernel" in which:
+            bench_kernel(20)
+    finally:
+        if not a.keep:
+            shutil.rmtree(d, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()
