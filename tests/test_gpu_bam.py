@@ -416,3 +416,21 @@ def test_cli_windows_and_regions_on_long_records(tmp_path):
     b, f, _ = _files(tmp_path, "long", _bam_reads(a, o, rng=rng))
     p, files = _pair_of_runs(tmp_path, "win", [b], [f], 1, extra=["--windows", "--regions", "PATH:regions.bed"])
     assert p.num_read == 300 and files["regions.bed"] is not None and len(files["regions.bed"]) > 0
+
+
+# ---- the reader over what tests/test_gpu_bam_index.py tests below it (windows of tests/bam_windows.py) -------------------------------------
+@pytest.mark.parametrize("named", [False, True])
+def test_h_records_without_bases_overflow_the_first_tables(tmp_path, named):
+    """20,000 records of 37 (38) bytes: more than the window / 96 + 4096 entries of the batch's first tables - rd_bam_index refuses the
+    batch (RD_FQ_LINES), BamIndexer frames it again with full-size tables"""
+    import bam_windows as W
+    ix = _same(tmp_path, "h%d" % named, W.tiny(20000, named))
+    assert ix["reframed"] >= 1 and ix["bam_records"] == 20000
+
+
+def test_i_two_decoys_in_different_rounds_of_one_batch(tmp_path):
+    """about 140 segments in one batch: the stitch takes three rounds of 64 segments, a decoy in the first and one in the second"""
+    import bam_windows as W
+    c = W.Chain(29).decoy(40 * S, False).decoy(100 * S, True).to(140 * S - 999)
+    ix = _same(tmp_path, "i", c.recs)
+    assert ix["bam_rewalked_segments"] >= 2 and ix["batches"] == 2        # (the batch of the data and the empty one that ends every stream)
