@@ -347,6 +347,24 @@ RD_API int rd_bam_gather(const uint8_t *norm, const int64_t *rec_tab, const int3
                   int64_t *seq_off, int32_t *seq_len, void *stream);
 RD_API int rd_bam_sample(const int64_t *rec_tab, const rd_fq_summary *summary, int64_t every, int32_t *samples, int64_t cap, void *stream);
 
+/* The delivered records of a framed BAM batch as they stand in the input - block_size, fixed fields, name, CIGAR, packed bases,
+ * qualities and every tag, nothing decoded - next to their FASTQ text (the rule: ribodetector_amd/bam.py select). The skipped records
+ * lie between them, so the raw view is a table and a gather. rd_bam_index_src [host, no launch]: the address of the table of source
+ * offsets (int32 per delivered record, offsets in `text`) that the rd_bam_index call with this workspace and this `end` filled; valid
+ * as long as the caller keeps the workspace; NULL for a bad argument. rd_bam_raw_tab: raw_tab [dev] int64[cap_records] (cap_records
+ * as given to rd_bam_index) = the exclusive scan of 4 + block_size over the delivered records, raw_tab[n_records] = their total;
+ * samples [dev] int32[cap_samples]: samples[k] = raw_tab[min(k * every, n_records)] (closed by the total; -1 everywhere for a batch
+ * that is not framed). A batch whose status is not RD_FQ_OK / RD_BAM_RECORD / RD_BAM_TRUNCATED: nothing is read or written but the
+ * samples. rd_bam_raw_gather: the contract of rd_bam_gather - records [rec_lo, rec_hi) appended to out [dev, 16-byte aligned] at
+ * *cursor_in; *cursor_out = the position behind them, or -1 (and nothing written) when they do not fit out_cap, the cursor was -1
+ * already or the batch is not framed; raw_start[0 .. rec_hi - rec_lo] = their offsets in `out`. No byte of `out` in front of *cursor_in
+ * or behind *cursor_out is written: two pieces of one chunk are two launches. max_bytes: an upper bound of the piece (sizes the grid). */
+RD_API int32_t *rd_bam_index_src(void *workspace, int64_t text_end);
+RD_API int rd_bam_raw_tab(const uint8_t *text, const int32_t *src_tab, const rd_fq_summary *summary, int64_t *raw_tab, int64_t cap_records, int64_t every,
+                   int32_t *samples, int64_t cap_samples, void *stream);
+RD_API int rd_bam_raw_gather(const uint8_t *text, const int32_t *src_tab, const int64_t *raw_tab, const rd_fq_summary *summary, int64_t rec_lo, int64_t rec_hi,
+                      int64_t max_bytes, uint8_t *out, int64_t out_cap, const int64_t *cursor_in, int64_t *cursor_out, int64_t *raw_start, void *stream);
+
 /* The records of a chunk that carry one label as ONE contiguous text in `out` [dev, 16-byte aligned], in input order - what the
  * reference's writer joins on the host (detect.py:485-492: fh.write('\n'.join(selected) + '\n')) - for plain (uncompressed) outputs of
  * chunks whose text lives on the device; arguments as rd_gz_compress_selected. info [dev] int64[4]: info[1] = bytes written,

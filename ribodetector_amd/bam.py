@@ -19,6 +19,9 @@ Record -> FASTQ text (fastq_text):  '@' name-without-NUL '\\n' SEQ '\\n' '+' '\\
 QUAL[i] = min(qual[i], 93) + 33; qualities absent (l_seq > 0 and qual[0] == 0xFF): every QUAL[i] = '"'. flag & 0x10: SEQ reverse-
 complemented (the complement of code c is the 4-bit bit reversal of c: "=TGKCYSBAWRDMHVN"[c]) and QUAL reversed, as samtools fastq
 does. flag & 0x900 (secondary / supplementary): the record is skipped - each read appears once. Tags, CIGAR, mapq, references: ignored.
+
+BAM output (detect.py --bam_output; device side csrc/rd_bam_raw.hpp): an output file is header(path of its input) followed by
+select(data, keep) - the kept records as they stand in the input, every tag included, in input order - in BGZF members.
 """
 import struct
 import zlib
@@ -85,6 +88,34 @@ def header_bytes(path):
                 return n
     header_len(data)
     raise ValueError("truncated BAM header")
+
+
+def header(path):
+    """the header's inflated bytes (magic, text, references) - what every BAM output of a run starts with, byte for byte: host zlib over
+    the leading gzip members, like header_bytes. ValueError on bad magic or a header the file ends in"""
+    n = header_bytes(path)
+    data = bytearray()
+    with open(path, "rb") as fh:
+        d = zlib.decompressobj(31)
+        while len(data) < n:
+            raw = fh.read(1 << 16)
+            if not raw:
+                raise ValueError("truncated BAM header")
+            while raw and len(data) < n:
+                data += d.decompress(raw)
+                raw = b""
+                if d.eof:
+                    raw, d = d.unused_data, zlib.decompressobj(31)
+    return bytes(data[:n])
+
+
+def select(data, keep, start=None):
+    """BAM output (--bam_output): the records of `data` (records(data, start)) that are not skipped and whose index among the delivered
+    records is in `keep`, as they stand in the input - block_size, fixed fields, name, CIGAR, packed bases, qualities, every tag -
+    joined in input order. Nothing is decoded; a record on the reverse strand stays as it is stored."""
+    data, keep = bytes(data), set(int(k) for k in keep)
+    delivered = (r for r in records(data, start) if not r.skipped)
+    return b"".join(data[r.offset:r.offset + r.size] for k, r in enumerate(delivered) if k in keep)
 
 
 class Record:

@@ -238,6 +238,7 @@ struct rd_writer {
     std::vector<void *> comp;       // gz only: one libdeflate compressor per worker slot (empty: zlib)
     bool bgzf = false;              // members written by rd_writer_write_members (BGZF blocks made on the GPU)
     bool eof_marker = true;         // ... then the file ends with BGZF's empty block (rd_writer_set_eof_marker)
+    bool bam = false;               // a BAM output (.bam / .ubam): gzip mode whose every member is a BGZF block, the end-of-file block always
 };
 
 // libdeflate (a system library of this image, libdeflate0 1.10) compresses level 5 ~2.5x faster than zlib at the same
@@ -344,10 +345,41 @@ bool gz_member(const uint8_t *src, size_t len, std::vector<uint8_t> &out, void *
     return true;
 }
 
-// compress w->pending[0, upto) as members of GZ_BLOCK bytes and write them in order: the workers take blocks from a shared
-// counter (no barrier between batches), the calling thread writes each member as soon as it and its predecessors are done
+// One BGZF member (SAM specification 4.1: a gzip member whose 'B','C' subfield holds its size - 1 in 16 bits) of at most BGZF_BLOCK
+// bytes: what a BAM output is made of. Level 5 like gz_member; a block that deflate does not shrink is one stored block, so that the
+// member always fits the 16 bits (18 + 5 + 0xff00 + 8 bytes).
+constexpr size_t BGZF_BLOCK = 0xff00, BGZF_HDR = 18;
+bool bgzf_member(const uint8_t *src, size_t len, std::vector<uint8_t> &out, void *comp) {
+    if (len > BGZF_BLOCK) return false;
+    std::vector<uint8_t> big;
+    if (!gz_member(src, len, big, comp)) return false;
+    const size_t body = big.size() - GZ_HDR - 8;
+    if (body <= len + 5) {
+        out.resize(BGZF_HDR + body + 8);
+        memcpy(out.data() + BGZF_HDR, big.data() + GZ_HDR, body + 8);       // (the deflate stream, CRC-32 and ISIZE)
+    } else {
+        out.resize(BGZF_HDR + 5 + len + 8);
+        uint8_t *p = out.data() + BGZF_HDR;
+        const uint16_t l16 = (uint16_t)len, n16 = (uint16_t)~l16;
+        p[0] = 1;                                                            // BFINAL, stored
+        memcpy(p + 1, &l16, 2);
+        memcpy(p + 3, &n16, 2);
+        if (len) memcpy(p + 5, src, len);
+        memcpy(p + 5 + len, big.data() + big.size() - 8, 8);
+    }
+    static const uint8_t hdr[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+    memcpy(out.data(), hdr, 16);
+    const uint16_t sz = (uint16_t)(out.size() - 1);
+    memcpy(out.data() + 16, &sz, 2);
+    return true;
+}
+
+// compress w->pending[0, upto) as members of GZ_BLOCK bytes (a BAM output: BGZF members of BGZF_BLOCK bytes) and write them in order:
+// the workers take blocks from a shared counter (no barrier between batches), the calling thread writes each member as soon as it
+// and its predecessors are done
 int gz_flush(rd_writer *w, size_t upto) {
-    const size_t nblk = (upto + GZ_BLOCK - 1) / GZ_BLOCK;
+    const size_t blk = w->bam ? BGZF_BLOCK : GZ_BLOCK;
+    const size_t nblk = (upto + blk - 1) / blk;
     std::vector<std::vector<uint8_t>> outs(nblk);
     std::vector<signed char> state(nblk, 0);   // 0 = pending, 1 = compressed, -1 = failed (guarded by m)
     std::mutex m;
@@ -365,8 +397,8 @@ int gz_flush(rd_writer *w, size_t upto) {
                     if (next >= nblk) return;
                     b = next++;
                 }
-                const size_t off = b * GZ_BLOCK, len = std::min(GZ_BLOCK, upto - off);
-                const bool ok = gz_member(w->pending.data() + off, len, outs[b], comp);
+                const size_t off = b * blk, len = std::min(blk, upto - off);
+                const bool ok = (w->bam ? bgzf_member : gz_member)(w->pending.data() + off, len, outs[b], comp);
                 {
                     std::lock_guard<std::mutex> lk(m);
                     state[b] = ok ? 1 : -1;
@@ -1009,7 +1041,8 @@ int rd_writer_open(const char *path, rd_writer **out) {
     if (!path || !out) RDH_FAIL("rd_writer_open: null argument");
     rd_writer *w = new rd_writer();
     std::string p(path);
-    w->gz = ends_with(p, "gz");            // reference detect.py:738: read_file.endswith('gz')
+    w->bam = ends_with(p, ".bam") || ends_with(p, ".ubam");      // BGZF is the container of BAM: what is written is the caller's (header, records)
+    w->gz = w->bam || ends_with(p, "gz");  // reference detect.py:738: read_file.endswith('gz')
     w->threads = usable_threads();
     w->fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
     w->off = 0;
@@ -1065,7 +1098,7 @@ int rd_writer_write_selected(rd_writer *w, const uint8_t *buf, const int64_t *re
         i = j;
     }
     if (w->gz) {
-        const size_t full = (w->pending.size() / GZ_BLOCK) * GZ_BLOCK;
+        const size_t blk = w->bam ? BGZF_BLOCK : GZ_BLOCK, full = (w->pending.size() / blk) * blk;
         if (full >= GZ_BLOCK * (size_t)w->threads && gz_flush(w, full) != 0) RDH_FAIL("gzip compression/write failed");
         return 0;
     }
@@ -1092,7 +1125,7 @@ int rd_writer_write_text(rd_writer *w, const uint8_t *text, int64_t len) {
     if (!w || len < 0 || (!text && len)) RDH_FAIL("rd_writer_write_text: bad argument");
     if (w->gz) {
         w->pending.insert(w->pending.end(), text, text + len);
-        const size_t full = (w->pending.size() / GZ_BLOCK) * GZ_BLOCK;
+        const size_t blk = w->bam ? BGZF_BLOCK : GZ_BLOCK, full = (w->pending.size() / blk) * blk;
         if (full >= GZ_BLOCK * (size_t)w->threads && gz_flush(w, full) != 0) RDH_FAIL("gzip compression/write failed");
         return 0;
     }
@@ -1114,8 +1147,8 @@ int rd_writer_close(rd_writer *w) {
     int rc = 0;
     if (w->gz) {
         if (!w->pending.empty()) rc = gz_flush(w, w->pending.size());
-        if (w->bgzf && !w->eof_marker) {
-        } else if (w->bgzf) {            // device-written members are BGZF blocks: the file ends with BGZF's end-of-file marker (an empty member)
+        if ((w->bgzf || w->bam) && !w->eof_marker) {
+        } else if (w->bgzf || w->bam) {  // device-written members are BGZF blocks: the file ends with BGZF's end-of-file marker (an empty member)
             static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
             if (rc == 0 && pwrite_all(w->fd, eof, sizeof(eof), w->off)) w->off += (int64_t)sizeof(eof);
             else rc = -1;

@@ -46,6 +46,7 @@
 #include "rd_fastq_index.hpp"
 #include "rd_fasta_index.hpp"
 #include "rd_bam_index.hpp"
+#include "rd_bam_raw.hpp"
 #include "rd_report.hpp"
 #include "rd_pairs.hpp"
 #include "rd_summary.hpp"
@@ -955,6 +956,46 @@ int rd_bam_gather(const uint8_t *norm, const int64_t *rec_tab, const int32_t *hd
 
 int rd_bam_sample(const int64_t *rec_tab, const rd_fq_summary *summary, int64_t every, int32_t *samples, int64_t cap, void *stream) {
     return fq_sample("rd_bam_sample", rd_fa_sample_kernel<true>, rec_tab, summary, every, samples, cap, stream);
+}
+
+// ---- the delivered BAM records as they stand in the input (rd_bam_raw.hpp): the source offsets rd_bam_index left in its workspace
+int32_t *rd_bam_index_src(void *workspace, int64_t text_end) {
+    if (!workspace || text_end < 0 || text_end >= 0x7fffffffLL) return nullptr;
+    return bam_ws(workspace, text_end).src_tab;
+}
+
+int rd_bam_raw_tab(const uint8_t *text, const int32_t *src_tab, const rd_fq_summary *summary, int64_t *raw_tab, int64_t cap_records, int64_t every, int32_t *samples,
+                   int64_t cap_samples, void *stream) {
+    if (!text || !src_tab || !summary || !raw_tab || (cap_samples > 0 && !samples)) RD_FAIL(RD_E_INVALID, "rd_bam_raw_tab: null pointer");
+    if (cap_records < 1 || cap_records > 0x7fffffffLL || every < 1 || cap_samples < 0) RD_FAIL(RD_E_INVALID, "rd_bam_raw_tab: bad cap_records / every / cap_samples");
+    hipStream_t st = (hipStream_t)stream;
+    const FqSummary *sum = (const FqSummary *)summary;
+    const unsigned nb = (unsigned)((cap_records + GZ_SCAN_ITEMS - 1) / GZ_SCAN_ITEMS);
+    hipLaunchKernelGGL(rd_bam_raw_local_kernel, dim3(nb), dim3(256), 0, st, text, src_tab, sum, raw_tab, cap_records);
+    hipLaunchKernelGGL(rd_bam_raw_base_kernel, dim3(1), dim3(256), 0, st, sum, raw_tab);
+    hipLaunchKernelGGL(rd_bam_raw_add_kernel, dim3(nb), dim3(256), 0, st, sum, raw_tab);
+    if (cap_samples > 0) {
+        int64_t grid = cap_samples / FQ_THREADS + 1;
+        if (grid > 1024) grid = 1024;
+        hipLaunchKernelGGL(rd_bam_raw_sample_kernel, dim3((unsigned)grid), dim3(FQ_THREADS), 0, st, (const int64_t *)raw_tab, sum, every, samples, cap_samples);
+    }
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+int rd_bam_raw_gather(const uint8_t *text, const int32_t *src_tab, const int64_t *raw_tab, const rd_fq_summary *summary, int64_t rec_lo, int64_t rec_hi,
+                      int64_t max_bytes, uint8_t *out, int64_t out_cap, const int64_t *cursor_in, int64_t *cursor_out, int64_t *raw_start, void *stream) {
+    if (!text || !src_tab || !raw_tab || !summary || !out || !cursor_in || !cursor_out || !raw_start) RD_FAIL(RD_E_INVALID, "rd_bam_raw_gather: null pointer");
+    if (rec_lo < 0 || rec_hi < rec_lo || max_bytes < 0 || out_cap < 0 || cursor_in == cursor_out) RD_FAIL(RD_E_INVALID, "rd_bam_raw_gather: bad range");
+    if ((uintptr_t)out & 15) RD_FAIL(RD_E_INVALID, "rd_bam_raw_gather: out must be 16-byte aligned");
+    int64_t grid = max_bytes / (BAM_RAW_BYTES * 4) + 1;         // four 16-byte granules per thread
+    const int64_t grid_r = (rec_hi - rec_lo) / FQ_THREADS + 1;
+    if (grid < grid_r) grid = grid_r;
+    if (grid > 8192) grid = 8192;
+    hipLaunchKernelGGL(rd_bam_raw_gather_kernel, dim3((unsigned)grid), dim3(FQ_THREADS), 0, (hipStream_t)stream, text, src_tab, raw_tab, (const FqSummary *)summary, rec_lo,
+                       rec_hi, out, out_cap, cursor_in, cursor_out, raw_start);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
 }
 
 // the per-read report of a chunk (rd_report.hpp): one line per record, and the lines' starts as a record table of the report text

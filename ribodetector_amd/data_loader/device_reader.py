@@ -87,6 +87,8 @@ class DeviceChunk:
     release = None
     shm = None
     verbatim = True
+    raw = None                   # keep_raw (BAM): (raw record bytes, raw_start int64[n + 1]) device tensors - the records as they stand in the input
+    raw_total = None             # ... and pinned int64[1]: the raw bytes (-1: assembly failed), valid after `ready`
 
     def __init__(self, n, text, rec_start, seq_off, seq_len, ready, total):
         self.n, self.dev, self.ready, self.total = n, (text, seq_off, seq_len, rec_start), ready, total
@@ -122,7 +124,8 @@ class DeviceChunk:
 
 class _Batch:
     __slots__ = ("text", "line_end", "summary", "host", "event", "slot", "gz_slot", "n", "begin", "end", "consumed", "status", "dirty",
-                 "bad_record", "n_lines", "final", "orig", "samples", "samples_host", "args", "chain", "norm", "rec_tab", "hdr_tab", "norm_end", "walked_before")
+                 "bad_record", "n_lines", "final", "orig", "samples", "samples_host", "args", "chain", "norm", "rec_tab", "hdr_tab", "norm_end", "walked_before",
+                 "ws", "src", "raw_tab", "raw_samples", "raw_samples_host")
 
     def bytes_bound(self, lo, hi):
         """an upper bound (tight within 2 * EVERY records) of the text bytes of records [lo, hi)"""
@@ -130,6 +133,11 @@ class _Batch:
         k1 = -(-hi // EVERY)
         top = int(s[k1]) if k1 * EVERY <= self.n and k1 < len(s) else (self.consumed if getattr(self, "norm", None) is None else self.norm_end)
         return top - int(s[lo // EVERY])
+
+    def raw_bound(self, lo, hi):
+        """keep_raw: the same bound for the raw bytes of records [lo, hi) (the raw samples are closed by the batch's total)"""
+        s = self.raw_samples_host
+        return int(s[min(-(-hi // EVERY), len(s) - 1)]) - int(s[lo // EVERY])
 
 
 class FastqIndexer:
@@ -146,6 +154,8 @@ class FastqIndexer:
         self.full_tables = False       # a batch overflowed its line table: the batches queued from now on get full-size tables
         self._lock = threading.Lock()  # (producer and consumer both touch `prev` after a repair)
         self.stats = {"batches": 0, "stripped": 0, "reframed": 0, "regrown": 0, "index_wait_s": 0.0}
+
+    keep_raw = False                   # BamIndexer: the batches keep what the raw view of their records needs
 
     def _sp(self):
         return C.c_void_p(self.stream.cuda_stream)
@@ -188,10 +198,13 @@ class FastqIndexer:
             # what travels to the host: the 64-byte summary and the record-offset samples, in ONE buffer, fetched by a kernel
             # (rd_copy_bytes: an SDMA queue is shared in order with copies that wait for kernels)
             ns = self._n_samples(window, cap_lines)
-            meta = torch.empty(64 + 4 * ns, dtype=torch.uint8, device=self.device)
-            meta_host = torch.empty(64 + 4 * ns, dtype=torch.uint8, pin_memory=True)
-            b.summary, b.samples = meta[:64].view(torch.int64), meta[64:].view(torch.int32)
-            b.host, b.samples_host = meta_host[:64].view(torch.int64), meta_host[64:].view(torch.int32)
+            nx = ns if self.keep_raw else 0          # (keep_raw: as many samples of the raw record offsets behind them)
+            meta = torch.empty(64 + 4 * (ns + nx), dtype=torch.uint8, device=self.device)
+            meta_host = torch.empty(64 + 4 * (ns + nx), dtype=torch.uint8, pin_memory=True)
+            b.summary, b.samples = meta[:64].view(torch.int64), meta[64:64 + 4 * ns].view(torch.int32)
+            b.host, b.samples_host = meta_host[:64].view(torch.int64), meta_host[64:64 + 4 * ns].view(torch.int32)
+            b.ws = b.src = b.raw_tab = None
+            b.raw_samples, b.raw_samples_host = (meta[64 + 4 * ns:].view(torch.int32), meta_host[64 + 4 * ns:].view(torch.int32)) if nx else (None, None)
             self._frame(b, int(start), int(end), (N.ptr(prev[0]), N.ptr(prev[1])) if prev is not None else (None, None), final, window, cap_lines, ns)
             N.copy_bytes(meta_host, meta, meta.numel(), self.stream, workgroups=4)
             b.event = N.new_event()
@@ -251,6 +264,7 @@ class FastqIndexer:
         b.begin, b.end, b.n_lines, b.n, b.consumed, b.bad_record, sd = (int(x) for x in h[:7])
         b.status, b.dirty = sd & 0xffffffff, (sd >> 32) & 0xffffffff
         b.samples_host = b.samples_host.numpy() if torch.is_tensor(b.samples_host) else b.samples_host
+        b.raw_samples_host = b.raw_samples_host.numpy() if torch.is_tensor(b.raw_samples_host) else b.raw_samples_host
 
     def finish(self, b):
         """wait (sleeping) for the batch's summary; strips a dirty batch. Returns the batch with n / status filled in - a status != 0 is
@@ -322,9 +336,13 @@ class FastqIndexer:
                 at += hi - lo
             total = torch.empty(1, dtype=torch.int64, pin_memory=True)
             N.copy_bytes(total.view(torch.uint8), cursor[len(pieces):].view(torch.uint8), 8, self.stream, workgroups=1)
+            raw = self._gather_raw(pieces, n) if self.keep_raw else None
             ready = torch.cuda.Event()
             ready.record(self.stream)
-        return DeviceChunk(n, text, rs, so, sl, ready, total)
+        chunk = DeviceChunk(n, text, rs, so, sl, ready, total)
+        if raw is not None:
+            chunk.raw, chunk.raw_total = raw[:2], raw[2]
+        return chunk
 
 
 LINE_DIV_FA = 8               # FASTA: the line table of a batch holds window / 8 lines (shorter lines on average - reads under 14 bases: framed again, full size)
@@ -374,14 +392,18 @@ class BamIndexer(FastqIndexer):
     - a length-prefixed chain of records, csrc/rd_bam_index.hpp - and RE-WRITTEN on the device into `norm` as FASTQ text (bam.fastq_text)
     with rec_tab / hdr_tab over it, like FastaIndexer's. The carry of a batch is the raw bytes behind its last complete record. No strip
     pass: there are no lines in the input. stats: the records walked, and how many of them were skipped (secondary / supplementary)."""
-    _REFRAMED = FastaIndexer._REFRAMED
+    _REFRAMED = FastaIndexer._REFRAMED + ("ws", "src", "raw_tab", "raw_samples", "raw_samples_host")
 
     line_div = 1 << 30          # (no line table: the few entries index() allocates stay unused)
     RECORD_DIV = 96             # the record tables of a batch hold window / 96 records (36 + name + 1.5 bytes per base: reads under ~35 bases
                                 # on average overflow them - framed again, full size: window / 37, the smallest well-formed record)
 
-    def __init__(self, device, stream):
+    def __init__(self, device, stream, keep_raw=False):
         super().__init__(device, stream)
+        # keep_raw (BAM output): a batch keeps its index workspace (the source offsets of its records) and a table of raw record offsets
+        # (rd_bam_raw_tab), and gather() adds the records as they stand in the input to the chunk (DeviceChunk.raw) - with a cursor
+        # chain of its own, next to the FASTQ text, which is what it is without the flag
+        self.keep_raw = bool(keep_raw)
         self.walked = 0         # records of the batches finished so far, the skipped ones included: what "malformed BAM record N" counts from
         self.stats.update({"bam_records": 0, "bam_skipped": 0, "bam_rewalked_segments": 0})
 
@@ -401,6 +423,11 @@ class BamIndexer(FastqIndexer):
         N.check(self.lib.rd_bam_index(N.ptr(b.text), start, end, prev[0], prev[1], 1 if final else 0, N.ptr(b.norm), norm_cap, N.ptr(b.rec_tab), N.ptr(b.hdr_tab),
                                       cap_rec, N.ptr(b.summary), N.ptr(ws), ws.numel(), self._sp()), "rd_bam_index")
         N.check(self.lib.rd_bam_sample(N.ptr(b.rec_tab), N.ptr(b.summary), EVERY, N.ptr(b.samples), ns, self._sp()), "rd_bam_sample")
+        if self.keep_raw:
+            b.ws, b.src = ws, C.c_void_p(self.lib.rd_bam_index_src(N.ptr(ws), end))
+            b.raw_tab = torch.empty(cap_rec, dtype=torch.int64, device=self.device)
+            N.check(self.lib.rd_bam_raw_tab(N.ptr(b.text), b.src, N.ptr(b.summary), N.ptr(b.raw_tab), cap_rec, EVERY, N.ptr(b.raw_samples), ns, self._sp()),
+                    "rd_bam_raw_tab")
 
     _read = staticmethod(FastaIndexer._read)
 
@@ -423,6 +450,25 @@ class BamIndexer(FastqIndexer):
     def _gather_piece(self, b, lo, hi, *out):
         N.check(self.lib.rd_bam_gather(N.ptr(b.norm), N.ptr(b.rec_tab), N.ptr(b.hdr_tab), N.ptr(b.summary), lo, hi, *out), "rd_bam_gather")
 
+    def _gather_raw(self, pieces, n):
+        """keep_raw: the records of the pieces as they stand in the input, behind one another (rd_bam_raw_gather; the current stream is the
+        indexer's). Returns (raw bytes, raw_start int64[n + 1], pinned int64[1]: the bytes, -1 when a piece did not fit)"""
+        cap = sum(b.raw_bound(lo, hi) for b, lo, hi in pieces)
+        raw = torch.empty(((cap + 255) // 256) * 256 + 256, dtype=torch.uint8, device=self.device)
+        rs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        cursor = torch.zeros(len(pieces) + 1, dtype=torch.int64, device=self.device)
+        at = 0
+        for i, (b, lo, hi) in enumerate(pieces):
+            N.check(self.lib.rd_bam_raw_gather(N.ptr(b.text), b.src, N.ptr(b.raw_tab), N.ptr(b.summary), lo, hi, b.raw_bound(lo, hi), N.ptr(raw), raw.numel(),
+                                               C.c_void_p(cursor.data_ptr() + 8 * i), C.c_void_p(cursor.data_ptr() + 8 * (i + 1)),
+                                               C.c_void_p(rs.data_ptr() + 8 * at), self._sp()), "rd_bam_raw_gather")
+            at += hi - lo
+        if not pieces:
+            rs.zero_()
+        total = torch.empty(1, dtype=torch.int64, pin_memory=True)
+        N.copy_bytes(total.view(torch.uint8), cursor[len(pieces):].view(torch.uint8), 8, self.stream, workgroups=1)
+        return raw, rs, total
+
 
 class DeviceFeeder:
     """The producer thread of one input file: file bytes -> batches on the GPU (H2D, members inflated where the file is BGZF, records
@@ -438,12 +484,13 @@ class DeviceFeeder:
     PLAIN_FIRST = 12 << 20
     SLOTS = 2
 
-    def __init__(self, path, device, compressed, span=None, byte_range=None, fasta=False, keep_empty_tail=False, bam=False):
+    def __init__(self, path, device, compressed, span=None, byte_range=None, fasta=False, keep_empty_tail=False, bam=False, keep_raw=False):
         """compressed: the file is BGZF (span = (first file byte, one past the last, text bytes to drop in front, text bytes to
         deliver) for a rank's share, fastx_parser.BgzfView.file_span); else plain text (byte_range = (start, end), record-aligned).
-        bam: the inflated bytes are a BAM file's - its header is dropped, its records are framed by BamIndexer"""
+        bam: the inflated bytes are a BAM file's - its header is dropped, its records are framed by BamIndexer (keep_raw: which also keeps
+        the records as they stand in the input, for BAM outputs)"""
         self.path, self.device, self.compressed, self.span, self.byte_range = str(path), torch.device(device), compressed, span, byte_range
-        self.fasta, self.keep_empty_tail, self.bam = bool(fasta), bool(keep_empty_tail), bool(bam)
+        self.fasta, self.keep_empty_tail, self.bam, self.keep_raw = bool(fasta), bool(keep_empty_tail), bool(bam), bool(keep_raw)
         self._skip = 0                 # BAM: inflated bytes of the header still to drop in front of the next batch
         self._stop = False
         self.out = queue.Queue(maxsize=self.SLOTS)
@@ -519,7 +566,10 @@ class DeviceFeeder:
             torch.cuda.set_device(self.device)          # the current device is per thread (and defaults to 0)
             self.stream = gz.acquire_stream(self.device, priority=-1)
             self.dg = gz.DeviceGunzip(self.device, slots=self.SLOTS, stream=self.stream)
-            self.ix = (BamIndexer if self.bam else FastaIndexer if self.fasta else FastqIndexer)(self.device, self.stream)
+            if self.bam:
+                self.ix = BamIndexer(self.device, self.stream, keep_raw=self.keep_raw)
+            else:
+                self.ix = (FastaIndexer if self.fasta else FastqIndexer)(self.device, self.stream)
             if self.fasta:
                 self.ix.keep_empty_tail = self.keep_empty_tail
         except BaseException as e:      # noqa: BLE001
@@ -848,15 +898,18 @@ class DeviceFeeder:
                     break
 
 
-def get_seq_chunks_device(seq_file, chunk_size=1048576, byte_range=None, first_chunk=None, schedule=None, device=None, stats=None):
+def get_seq_chunks_device(seq_file, chunk_size=1048576, byte_range=None, first_chunk=None, schedule=None, device=None, stats=None, keep_raw=False):
     """fastx_parser.get_seq_chunks for FASTQ whose text stays on the device: DeviceChunk objects of exactly the scheduled number of
     records (fewer only at the end of the stream). byte_range: (start, end) of a plain file or a fastx_parser.BgzfRange. A damaged
-    stream delivers the chunks before the damage, then raises ValueError like the host reader."""
+    stream delivers the chunks before the damage, then raises ValueError like the host reader. keep_raw (BAM input only): every chunk
+    also carries its records as they stand in the input, chunk.raw = (bytes, raw_start) - what a BAM output is selected from."""
     from . import fastx_parser as fx
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     torch.cuda.set_device(device)
-    kind = device_ingest_kind(seq_file)
     fmt = fx.get_seq_format(seq_file)
+    if keep_raw and fmt != "bam":
+        raise ValueError("keep_raw: %s is not a BAM file" % seq_file)
+    kind = device_ingest_kind(seq_file)
     compressed = "stream" if kind == "stream" else (fmt.endswith("gz") or fmt == "bam")
     span = None
     keep_tail = False            # a share that ends before the file does (FASTA: its last record counts even without a sequence)
@@ -874,7 +927,8 @@ def get_seq_chunks_device(seq_file, chunk_size=1048576, byte_range=None, first_c
     if resident is not None:
         feeder = gz_shard.ResidentFeeder(resident)
     else:
-        feeder = DeviceFeeder(seq_file, device, compressed, span=span, byte_range=byte_range, fasta=fmt.startswith("fa"), keep_empty_tail=keep_tail, bam=fmt == "bam")
+        feeder = DeviceFeeder(seq_file, device, compressed, span=span, byte_range=byte_range, fasta=fmt.startswith("fa"), keep_empty_tail=keep_tail, bam=fmt == "bam",
+                              keep_raw=keep_raw)
     skip_left = resident.skip if resident is not None else 0      # (mate files: the records in front of the ranks' common cut went to the rank before)
     want = chunk_size if not first_chunk else max(1, min(int(first_chunk), chunk_size))
     sched = list(schedule) if schedule else None

@@ -33,6 +33,9 @@ lines on the post stream where the windows' final logits are). The lines travel 
 BAM input (an extension): -i x.bam / x.ubam, in all three layouts of the inputs (one file, two files, --interleaved). The file's BGZF
 members are inflated on the GPU and rd_bam_index (csrc/rd_bam_index.hpp; bam.py has the rule) frames the records and re-writes them as
 FASTQ text, so the chunks are FASTQ chunks and the outputs FASTQ files. One rank, device ingest only (check_bam).
+--bam_output (an extension, BAM input): the chunks also carry their records as they stand in the input (DeviceChunk.raw: rd_bam_raw_tab /
+rd_bam_raw_gather, csrc/rd_bam_raw.hpp), and the output kernels select from THAT view (_select_chunk): every output is a BAM file - the
+header of its input, the selected records byte for byte, BGZF members. Classification, report, summary and regions see the FASTQ view.
 """
 import argparse
 import functools
@@ -50,6 +53,7 @@ import torch.distributed as dist
 
 from . import __version__
 from . import _native as _native_mod
+from . import bam as _bammod
 from . import dist as rdist
 from . import gz as _gzmod
 from . import regions as _regmod
@@ -230,6 +234,7 @@ class Predictor:
         self._report = None                      # --read_report: gz.DeviceReport (run_with_chunks)
         self.interleaved = bool(getattr(args, 'interleaved', False))     # paired-end reads from ONE interleaved FASTQ file
         self.mate_check = not getattr(args, 'no_mate_check', False)
+        self.bam_output = bool(getattr(args, 'bam_output', False))       # BAM outputs: the selected records as they stand in the input
         self._pairs = None                       # --interleaved: gz.DevicePairSplit (run_with_chunks)
         self._summary = None                     # --summary: summary.DeviceSummary (run_with_chunks)
         self._windows = None                     # --windows: {"stride", "max_per_read", "fuse"} (stride None = -l); detect() sets it
@@ -539,7 +544,7 @@ class Predictor:
             done = _native_mod.new_event()
             done.record(post)
         return {"n": n, "bounds": bounds, "labels": labels, "host": host, "finish": finish, "done": done, "keep": (dev_in, outs, plans),
-                "pieces": pieces, "pairs": pairs, "chunk": chunks[0], "totals": [c.total for c in chunks] if on_dev else (), "summary": sum_info,
+                "pieces": pieces, "pairs": pairs, "chunk": chunks[0], "totals": [t for c in chunks for t in (c.total, c.raw_total) if t is not None] if on_dev else (), "summary": sum_info,
                 "regions": regions}
 
     def _select_chunk(self, chunks, dev_in, labels, lo, hi, on_dev, pairs=None):
@@ -563,7 +568,15 @@ class Predictor:
         views = {}                                  # mate -> (text, record table, labels) that select the records of its files
         for e, lab in files:
             if e not in views:
-                if pairs is None:
+                if self.bam_output:                 # the records as they stand in the input (DeviceChunk.raw), selected like the text's
+                    raw, raw_start = chunks[e if pairs is None else 0].raw
+                    if pairs is None:
+                        views[e] = (raw, raw_start, labels.view(torch.int8))
+                    elif len(self.output) == 1:     # pair k = raw records 2 k and 2 k + 1
+                        views[e] = (raw, raw_start[0:2 * (hi - lo) + 1:2].contiguous(), labels.view(torch.int8))
+                    else:
+                        views[e] = (raw, raw_start, self._pairs.expand(labels.view(torch.int8), e, slot=pairs["ring"]))
+                elif pairs is None:
                     views[e] = self._device_text(chunks[e], dev_in[e][0], lo, hi) + (labels.view(torch.int8),)
                 elif len(self.output) == 1:         # interleaved output: the pairs are the records
                     views[e] = (pairs["text"], pairs["pair_start"], labels.view(torch.int8))
@@ -724,7 +737,7 @@ class Predictor:
                 if arena is None and self._device_parse(path):
                     st = self.ingest.setdefault(os.path.basename(str(path)), {"path": "device"})
                     stream = dr.get_seq_chunks_device(path, chunk_size=chunk_reads, byte_range=byte_range, first_chunk=first, schedule=schedule,
-                                                      device=self.device, stats=st)
+                                                      device=self.device, stats=st, keep_raw=self.bam_output)
                 # one plain input file: its parser thread was the slowest stage of the pipeline - two readers over byte segments,
                 # small first chunks (mate files keep one reader each and exact chunk sizes: their chunks must pair up)
                 # (not an interleaved file: its chunks must hold whole pairs)
@@ -1070,7 +1083,7 @@ class Predictor:
     def _open_outputs(self):
         """Open this rank's output set - under the sharded parse its part of every file: the label files, the '.unclassified.gz'
         files (-e both, pairs) and the --read_report with its header. Returns [((mate, label), final path, handle)] in opening order."""
-        files = []
+        files, headers = [], {}
         log = self.logger.info if self.rank == 0 else (lambda *a, **k: None)
 
         def open_(label, paths):               # one file per mate: keys (mate, label); the report's is REPORT
@@ -1080,13 +1093,18 @@ class Predictor:
                 files.append(((e, label), path, fx.open_for_write(self._part_files[-1] if self.sharded_parse else path)))
                 if self.sharded_parse:         # parts are joined later: the joined file gets ONE BGZF end-of-file block, at its end
                     files[-1][2].set_eof_marker(False)
+                if self.bam_output and label in (0, 1, -1):      # a BAM output starts with the header of its mate's input, byte for byte
+                    src = self.input[e if len(self.input) == 2 else 0]
+                    if src not in headers:
+                        headers[src] = np.frombuffer(_bammod.header(src), dtype=np.uint8)
+                    files[-1][2].write_text(headers[src].ctypes.data, headers[src].size)
         if self.rrna is not None:
             log('Writing output rRNA sequences into file: {}{}{}'.format(colors.OKBLUE, ", ".join(self.rrna), colors.ENDC))
             open_(1, self.rrna)
         log('Writing output non-rRNA sequences into file: {}{}{}'.format(colors.OKBLUE, ", ".join(self.output), colors.ENDC))
         open_(0, self.output)
         if self.is_paired and self.args.ensure == 'both':
-            unclf = [path + '.unclassified.gz' for path in self.output]
+            unclf = [unclassified_path(path, self.bam_output) for path in self.output]
             open_(-1, unclf)
             log('Writing unclassified sequences into file: {}{}{}'.format(colors.OKYELLOW, ", ".join(unclf), colors.ENDC))
         rep_path = getattr(self.args, 'read_report', None)
@@ -1186,7 +1204,8 @@ class Predictor:
         (detect.py:738: read_file.endswith('gz')); the '<out>.unclassified.gz' files of --ensure both (detect.py:390-400) always are.
         The same list on every rank (it depends on the arguments only): the files whose records are deflated on the device."""
         # (one file per mate - or, for the pairs of an interleaved input, ONE file per label: its key is mate 0's)
-        files = [(e, lab) for lab, names in ((1, rrna), (0, output)) if names is not None for e, name in enumerate(names) if name.endswith('gz')]
+        files = [(e, lab) for lab, names in ((1, rrna), (0, output)) if names is not None for e, name in enumerate(names)
+                 if name.endswith('gz') or name.endswith(('.bam', '.ubam'))]      # (BAM names: --bam_output only - BGZF members, like a .gz)
         if is_paired and ensure == 'both':
             files += [(e, -1) for e in range(len(output))]
         return files
@@ -1213,12 +1232,12 @@ class Predictor:
             self.logger.error('{}{}{}'.format(colors.FAIL, _COUNT_ERRORS.get(str(e), str(e)), colors.ENDC))
             raise
         check_read_report(self.args.read_report if hasattr(self.args, 'read_report') else None, self.output, self.rrna, self.is_paired,
-                          self.args.ensure)
+                          self.args.ensure, self.bam_output)
         check_summary(getattr(self.args, 'summary', None), self.output, self.rrna, self.is_paired, self.args.ensure,
-                      getattr(self.args, 'read_report', None))
+                      getattr(self.args, 'read_report', None), self.bam_output)
         self._windows = check_windows(self.args)
         check_regions(getattr(self.args, 'regions', None), self._windows is not None, self.output, self.rrna, self.is_paired, self.args.ensure,
-                      getattr(self.args, 'read_report', None), getattr(self.args, 'summary', None))
+                      getattr(self.args, 'read_report', None), getattr(self.args, 'summary', None), self.bam_output)
         # reference batch-size heuristic (detect.py:558-568); kept because --chunk_size is expressed in these batches
         denom = (2 * self.len * 6.4) if self.is_paired else (self.len * 6.4)
         self.batch_size = 2 ** math.floor(math.log2(((self.args.memory - 2) * 1024 * 1024) / denom))
@@ -1274,27 +1293,43 @@ def check_file_counts(inputs, output, rrna, interleaved=False):
     return n_in == 2
 
 
-def check_bam(inputs, output, rrna):
+def unclassified_path(out, bam_output=False):
+    """the file of the unclassified pairs (-e both) that goes with the -o file `out`: '<out>.unclassified.gz', or under --bam_output
+    '<out>.unclassified.bam' - the one place that knows the name (the collision checks of --read_report / --summary / --regions use it)"""
+    return out + ('.unclassified.bam' if bam_output else '.unclassified.gz')
+
+
+def check_bam(inputs, output, rrna, bam_output=False):
     """BAM input (.bam / .ubam, ribodetector_amd/bam.py): the rules that hold before anything touches a device; returns whether the
     inputs are BAM. The records become FASTQ text on the device, so the outputs are FASTQ files; there is no host reader for BAM,
-    so the switches and layouts that need one are refused."""
+    so the switches and layouts that need one are refused. bam_output (--bam_output): every input is BAM and every -o / -r name ends
+    with .bam / .ubam - the selected records are written as they stand in the input (all outputs are BAM or none is)."""
     def fmt(path):
         try:
             return fx.get_seq_format(path)
         except ValueError:
             return None                          # (the run reports unknown extensions, as ever)
-    for o in list(output or []) + list(rrna or []):
-        if fmt(o) == "bam":
+    outs = list(output or []) + list(rrna or [])
+    kinds = [fmt(p) for p in inputs or []]
+    if bam_output:
+        if not kinds or any(k != "bam" for k in kinds):
+            raise RuntimeError("--bam_output writes the records of BAM input as they stand: every -i file must end with .bam or .ubam, got {} "
+                               "(checked before anything touches a device)".format(", ".join(str(p) for p in inputs or [])))
+        for o in outs:
+            if fmt(o) != "bam":
+                raise RuntimeError("--bam_output: {} must end with .bam or .ubam - all outputs are BAM or none is (checked before anything "
+                                   "touches a device)".format(o))
+    for o in outs:
+        if fmt(o) == "bam" and not bam_output:
             raise RuntimeError("BAM output is not supported: {} (-o / -r take FASTQ names, plain or .gz; checked before anything touches a "
                                "device)".format(o))
-    kinds = [fmt(p) for p in inputs or []]
     if "bam" not in kinds:
         return False
     if any(k != "bam" for k in kinds):
         raise RuntimeError("BAM input cannot be mixed with FASTQ / FASTA input files: {} (checked before anything touches a "
                            "device)".format(", ".join(str(p) for p in inputs)))
-    for o in list(output or []) + list(rrna or []):
-        if fmt(o) not in ("fq", "fqgz"):
+    for o in outs:
+        if not bam_output and fmt(o) not in ("fq", "fqgz"):
             raise RuntimeError("BAM input is written as FASTQ: {} must end with .fq or .fastq, plain or .gz (checked before anything "
                                "touches a device)".format(o))
     for name in ("RD_DEVICE_PARSE", "RD_DEVICE_INFLATE"):
@@ -1307,7 +1342,7 @@ def check_bam(inputs, output, rrna):
     return True
 
 
-def check_read_report(path, output, rrna, is_paired, ensure):
+def check_read_report(path, output, rrna, is_paired, ensure, bam_output=False):
     """--read_report must not name a file the run writes anyway: an -o / -r file or an '<out>.unclassified.gz' file (-e both, pairs:
     one per -o path, also when the pairs come from one interleaved file)"""
     if not path:
@@ -1318,18 +1353,18 @@ def check_read_report(path, output, rrna, is_paired, ensure):
             raise RuntimeError("--read_report {} is also an output sequence file (-o / -r)".format(path))
     if is_paired and ensure == 'both':
         for o in output or []:
-            if same(path, o + '.unclassified.gz'):
+            if same(path, unclassified_path(o, bam_output)):
                 raise RuntimeError("--read_report {} is the unclassified pairs' output file".format(path))
 
 
-def check_summary(path, output, rrna, is_paired, ensure, read_report=None):
+def check_summary(path, output, rrna, is_paired, ensure, read_report=None, bam_output=False):
     """--summary must not name a file the run writes anyway: an -o / -r file, an '<out>.unclassified.gz' file (-e both, pairs) or the
     --read_report"""
     if not path:
         return
     taken = [(o, "an output sequence file (-o / -r)") for o in list(output or []) + list(rrna or [])]
     if is_paired and ensure == 'both':
-        taken += [(o + '.unclassified.gz', "the unclassified pairs' output file") for o in output or []]
+        taken += [(unclassified_path(o, bam_output), "the unclassified pairs' output file") for o in output or []]
     if read_report:
         taken.append((read_report, "the --read_report file"))
     for o, what in taken:
@@ -1358,7 +1393,7 @@ def check_windows(args):
     return {"stride": stride, "max_per_read": int(most), "fuse": fuse}
 
 
-def check_regions(path, windows, output=None, rrna=None, is_paired=False, ensure="none", read_report=None, summary=None):
+def check_regions(path, windows, output=None, rrna=None, is_paired=False, ensure="none", read_report=None, summary=None, bam_output=False):
     """--regions needs --windows and must not name a file the run writes anyway: an -o / -r file, an '<out>.unclassified.gz' file (-e
     both, pairs), the --read_report or the --summary. Checked before anything touches a device."""
     if not path:
@@ -1367,7 +1402,7 @@ def check_regions(path, windows, output=None, rrna=None, is_paired=False, ensure
         raise RuntimeError("--regions needs --windows")
     taken = [(o, "an output sequence file (-o / -r)") for o in list(output or []) + list(rrna or [])]
     if is_paired and ensure == 'both':
-        taken += [(o + '.unclassified.gz', "the unclassified pairs' output file") for o in output or []]
+        taken += [(unclassified_path(o, bam_output), "the unclassified pairs' output file") for o in output or []]
     taken += [(o, what) for o, what in ((read_report, "the --read_report file"), (summary, "the --summary file")) if o]
     for o, what in taken:
         if os.path.abspath(path) == os.path.abspath(o):
@@ -1440,6 +1475,10 @@ none: give label based on the mean probability of read pair.
                            '[start, end) in 0-based bases of that read; mate = 1 or 2 (read_id is that mate\'s); windows = the windows\n'
                            'of the run; p_rrna_max = the largest p_rrna among them. Independent of -e and --window_fuse.\n'
                            'gzip-compressed when the name ends with gz.')
+    args.add_argument('--bam_output', action='store_true',
+                      help='(extension) BAM input only: -o / -r take .bam / .ubam names, and every output file is a BAM file - the header of\n'
+                           'its input and the selected records, byte for byte as they stand in the input (every tag kept), in input\n'
+                           'order. Secondary / supplementary records are in no output. No @PG line is added.')
     args.add_argument('--no_mate_check', action='store_true', help='(extension) with --interleaved: do not compare the ids of the mates')
     args.add_argument('-v', '--version', action='version', version='%(prog)s {version}'.format(version=__version__))
     return args
@@ -1451,7 +1490,7 @@ def main(argv=None, log_level=None):
     config = ConfigParser.from_json(config_file)
     check_windows(args)                          # (before the model is loaded: nothing has touched a device yet)
     check_regions(getattr(args, 'regions', None), getattr(args, 'windows', False))
-    check_bam(args.input, args.output, args.rrna)
+    check_bam(args.input, args.output, args.rrna, getattr(args, 'bam_output', False))
     seq_pred = Predictor(config, args, log_level=log_level)
     try:
         t0 = time.perf_counter()

@@ -10,6 +10,9 @@ timed calls of each, ALTERNATING the legs (model load excluded: Predictor.timing
           in-order pass had to walk again. The split over the walk / stitch / table / emit kernels is not visible to events around one
           call of the C ABI: run this measurement under  rocprofv3 --kernel-trace --output-format csv -d OUT -- python tools/bam_bench.py
           --only kernel  and print the split with --trace OUT.
+  --bam_output   the same three measurements for BAM OUTPUT (detect.py --bam_output, csrc/rd_bam_raw.hpp): short / long time x.bam -> .bam
+          --bam_output against x.bam -> .fq.gz - the same input file, the existing path is the yardstick; kernel times rd_bam_raw_tab +
+          rd_bam_raw_gather (every record of the batch, one piece) behind one rd_bam_index call on the resident batch.
 Every fourth record of the BAM files is stored on the reverse strand (flag 0x10, bases reverse-complemented, qualities reversed), so
 that the text the two legs see is the same. The inputs are written by processes that never touch the GPU."""
 import argparse
@@ -38,7 +41,7 @@ def trace_times(root):
             for r in csv.DictReader(fh):
                 us = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
                 total += us
-                for key in ("rd_bam_", "rd_fq_begin_"):
+                for key in ("rd_bam_", "rd_fq_begin_", "rd_gz_", "rd_select_"):
                     if key in r["Kernel_Name"]:
                         out.setdefault(key + r["Kernel_Name"].split(key)[1].split("(")[0].split("<")[0], []).append(us)
     return out, total
@@ -88,11 +91,11 @@ def _rows(n, first, length, seed):
 
 
 def _make(job):
-    d, shape, reads = job
+    d, shape, reads, bam_only = job
     from ribodetector_amd import bam, synth
     length = SHAPES[shape]
     fq_gz, bam_path = os.path.join(d, "%s_%d.fq.gz" % (shape, reads)), os.path.join(d, "%s_%d.bam" % (shape, reads))
-    if os.path.exists(fq_gz) and os.path.exists(bam_path):
+    if (bam_only or os.path.exists(fq_gz)) and os.path.exists(bam_path):
         return
     step = max(1, (64 << 20) // (2 * length))
     with open(fq_gz + ".raw", "wb") as f1, open(bam_path + ".raw", "wb") as f2:
@@ -102,7 +105,8 @@ def _make(job):
             f1.write(fq.tobytes())
             f2.write(rec.tobytes())
     for raw, dst in ((fq_gz + ".raw", fq_gz), (bam_path + ".raw", bam_path)):
-        synth.bgzip_file(raw, dst, level=6, threads=8)
+        if not (bam_only and dst == fq_gz):      # (the BAM output measurements read the BAM file only)
+            synth.bgzip_file(raw, dst, level=6, threads=8)
         os.remove(raw)
 
 
@@ -145,7 +149,26 @@ def bench_cli(d, shape, reads, calls):
                       "segments_walked_again": ix["bam_rewalked_segments"], "batches": ix["batches"]}), flush=True)
 
 
-def bench_kernel(calls, batch_bytes=128 << 20):
+def bench_cli_bam_output(d, shape, reads, calls):
+    """x.bam -> .fq.gz (the yardstick) against x.bam -> .bam --bam_output: one input file, the legs alternating"""
+    extra = ["--windows", "--chunk_size", "1"] if shape == "long" else []
+    src = os.path.join(d, "%s_%d.bam" % (shape, reads))
+    argv = {"bam_to_fqgz": ["-l", "100", "-i", src, "-o", os.path.join(d, "o_yard.fq.gz")] + extra,
+            "bam_to_bam": ["-l", "100", "-i", src, "-o", os.path.join(d, "o_out.bam"), "--bam_output"] + extra}
+    rate, last = timed_legs(argv, calls, reads)
+    med = {k: statistics.median(v) for k, v in rate.items()}
+    yard = rate["bam_to_fqgz"]
+    same = all(getattr(last["bam_to_bam"], a) == getattr(last["bam_to_fqgz"], a) for a in ("num_read", "num_rrna", "num_nonrrna"))
+    outside = 0.0 if yard[0] <= med["bam_to_bam"] <= yard[-1] else (med["bam_to_bam"] / yard[0] - 1 if med["bam_to_bam"] < yard[0] else med["bam_to_bam"] / yard[-1] - 1)
+    print(json.dumps({"measurement": shape + "_bam_output", "reads": reads, "read_len": SHAPES[shape], "calls": calls,
+                      "flow": "single-end x.bam -> .fq.gz | .bam --bam_output" + (", --windows --chunk_size 1" if extra else ""), "input_bytes": os.path.getsize(src),
+                      "output_bytes": {"bam_to_fqgz": os.path.getsize(argv["bam_to_fqgz"][5]), "bam_to_bam": os.path.getsize(argv["bam_to_bam"][5])},
+                      "reads_per_s": {k: _mlh(v) for k, v in rate.items()}, "ratio_of_medians": round(med["bam_to_bam"] / med["bam_to_fqgz"], 4),
+                      "bam_output_median_inside_fastq_output_spread": bool(outside == 0.0), "outside_the_spread_by": round(outside, 4),
+                      "same_counts": bool(same), "non_rrna": last["bam_to_bam"].num_nonrrna}), flush=True)
+
+
+def bench_kernel(calls, batch_bytes=128 << 20, raw_view=False):
     import numpy as np
     import torch
     from ribodetector_amd import _native as N
@@ -169,6 +192,20 @@ def bench_kernel(calls, batch_bytes=128 << 20):
         def index():
             N.check(lib.rd_bam_index(N.ptr(text), pad, end, None, None, 1, N.ptr(norm), norm_cap, N.ptr(rec_tab), N.ptr(hdr_tab), cap_rec, N.ptr(summary),
                                      N.ptr(ws), ws.numel(), st), "rd_bam_index")
+        if raw_view:                             # the raw view behind ONE framing of the batch: the table, then every record gathered as one piece
+            index()
+            src = N.C.c_void_p(lib.rd_bam_index_src(N.ptr(ws), end))
+            raw_tab = torch.empty(cap_rec, dtype=torch.int64, device=dev)
+            ns = cap_rec // 4096 + 3
+            samples = torch.empty(ns, dtype=torch.int32, device=dev)
+            out = torch.empty(((window + 255) // 256) * 256 + 256, dtype=torch.uint8, device=dev)
+            raw_start = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            cursor = torch.zeros(2, dtype=torch.int64, device=dev)
+
+            def index():      # noqa: F811
+                N.check(lib.rd_bam_raw_tab(N.ptr(text), src, N.ptr(summary), N.ptr(raw_tab), cap_rec, 4096, N.ptr(samples), ns, st), "rd_bam_raw_tab")
+                N.check(lib.rd_bam_raw_gather(N.ptr(text), src, N.ptr(raw_tab), N.ptr(summary), 0, n, window, N.ptr(out), out.numel(), N.ptr(cursor),
+                                              N.C.c_void_p(cursor.data_ptr() + 8), N.ptr(raw_start), st), "rd_bam_raw_gather")
         for _ in range(3):
             index()
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(calls + 1)]
@@ -182,6 +219,16 @@ def bench_kernel(calls, batch_bytes=128 << 20):
         assert status == 0 and int(s[3]) == n and norm_bytes == n * (2 * length + NAME + 5), (status, int(s[3]), n, norm_bytes)
         us = sorted(ev[k].elapsed_time(ev[k + 1]) * 1e3 for k in range(calls))
         med = statistics.median(us)
+        if raw_view:
+            assert int(cursor.cpu()[1]) == window and bytes(out[:window].cpu().numpy()) == raw and int(samples.cpu()[-1]) == window
+            # every byte of the window is read once and written once; per record: 4 bytes of src_tab and a 32-byte sector for block_size
+            # read, 8 bytes of raw_tab written, read and written again (the add pass), read by the gather, and 8 of raw_start written
+            moved = 2 * window + (4 + 32 + 4 * 8 + 8) * n
+            print(json.dumps({"measurement": "kernel_raw", "what": "rd_bam_raw_tab + rd_bam_raw_gather", "shape": shape, "read_len": length, "records": n,
+                              "raw_bytes": window, "calls": calls, "us_per_call": {"median": round(med, 1), "lowest": round(us[0], 1), "highest": round(us[-1], 1)},
+                              "bytes_moved": moved, "TB_per_s": round(moved / med / 1e6, 3),
+                              "fraction_of_hbm_bound_pass_at_8TBps": round(moved / 8e12 / (med * 1e-6), 4)}), flush=True)
+            continue
         # the window is read by the walk (staged once) and again by the emit pass (names, bases, qualities: all but the fixed fields and
         # tags); `norm` is written once; per record 16 bytes of tables and 8 of the segment lists are written and read
         moved = 2 * window + norm_bytes + 2 * 24 * n
@@ -200,6 +247,7 @@ def main():
     ap.add_argument("--keep", default=None)
     ap.add_argument("--only", default=None, choices=["short", "long", "kernel"])
     ap.add_argument("--trace", default=None)
+    ap.add_argument("--bam_output", action="store_true", help="the measurements of BAM output instead")
     a = ap.parse_args()
     if a.trace:
         t, total = trace_times(a.trace)
@@ -207,17 +255,17 @@ def main():
                                                                                "largest": round(max(v), 1)} for k, v in sorted(t.items())}}))
         return
     which = [a.only] if a.only else ["short", "long", "kernel"]
-    jobs = [(s, n) for s, n in (("short", a.reads), ("long", a.long_reads)) if s in which]
+    jobs = [(s, n, a.bam_output) for s, n in (("short", a.reads), ("long", a.long_reads)) if s in which]
     d = a.keep or tempfile.mkdtemp(prefix="rdbam", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
     os.makedirs(d, exist_ok=True)
     try:
         if jobs:
             make_inputs(d, jobs)                 # (before anything initialises the GPU)
         import ribodetector_amd  # noqa: F401
-        for s, n in jobs:
-            bench_cli(d, s, n, a.calls)
+        for s, n, _ in jobs:
+            (bench_cli_bam_output if a.bam_output else bench_cli)(d, s, n, a.calls)
         if "kernel" in which:
-            bench_kernel(20)
+            bench_kernel(20, raw_view=a.bam_output)
     finally:
         if not a.keep:
             shutil.rmtree(d, ignore_errors=True)
