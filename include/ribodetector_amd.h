@@ -439,6 +439,34 @@ RD_API int rd_summary_accumulate(const uint8_t *text_a, int64_t bytes_a, const i
                           const uint8_t *text_b, int64_t bytes_b, const int64_t *seq_off_b, const int32_t *seq_len_b, const float *logits_b,
                           const int8_t *labels, int64_t n, int64_t *acc, int64_t *info, void *stream);
 
+/* The optional fields (tags) of raw BAM records, and counters per read group (the CLI's --read_groups, an extension). The rule is
+ * ribodetector_amd/bam.py (find_tag, group_row). raw [dev] uint8[raw_bytes] / raw_start [dev] int64[n_rec + 1]: a raw view as
+ * rd_bam_raw_gather writes it - record k is raw[raw_start[k] .. raw_start[k + 1]), its block_size field first.
+ * rd_bam_tag_find: for every record the first tag `tag` [host, 2 bytes]: val_off [dev] int64[n_rec] = where its value starts in raw
+ * (-1: the record has no such tag; -2: its tags are malformed in front of or at the tag, or the record does not lie inside the view),
+ * val_len [dev] int32[n_rec] = the value's bytes (Z / H: without the NUL; B: subtype and count included), val_type [dev] uint8[n_rec] =
+ * the type byte; both 0 where val_off < 0. Every length in a record is data: it is checked against the record's end before a byte it
+ * points to is read, and no byte outside [raw_start[k], raw_start[k + 1]) is read for record k.
+ * rd_bam_group_rows: rows [dev] int32[n_rec] from the three tables of a search for "RG" and the dictionary of the G declared ids
+ * (0 <= G <= RD_GROUPS_MAX), SORTED as unsigned bytes with a prefix in front of what it is a prefix of: dict_bytes [dev] the ids behind
+ * one another (no id holds a NUL byte), dict_off [dev] int32[G + 1] where each starts. Row j: a Z value equal to id j; G: no tag; G + 1: a Z value that is no
+ * declared id; G + 2: malformed tags or a tag that is not of type Z.
+ * rd_bam_group_accumulate: acc [dev] int64[(G + 3) * 6 + 1], zeroed by the caller at run start, += the n units of a chunk. Unit u is
+ * record first_a + stride_a * u of mate 1's view (and first_b + stride_b * u of mate 2's; raw_b == NULL: single-end; the two mates may
+ * share one view). With g = rows_a[...] and class c = labels[u] + 1: acc[(g * 3 + c) * 2] += 1, acc[(g * 3 + c) * 2 + 1] += l_seq of
+ * mate 1 (+ l_seq of mate 2), read from the raw records; acc[(G + 3) * 6] += 1 for a pair whose rows_b differs from g. info [dev]
+ * int64[4]: info[0] != 0 = NOTHING was added - a label outside -1..1 (bit 0) or a row outside 0..G + 2 (bit 1); else info[1] = n. A
+ * check pass decides that before the accumulate pass reads a record. n == 0: a no-op (info, when given, is zeroed). Integer sums: exact,
+ * independent of the chunking. All three are asynchronous on `stream`. */
+#define RD_GROUPS_MAX 65536
+RD_API int rd_bam_tag_find(const uint8_t *raw, int64_t raw_bytes, const int64_t *raw_start, int64_t n_rec, const uint8_t *tag, int64_t *val_off,
+                           int32_t *val_len, uint8_t *val_type, void *stream);
+RD_API int rd_bam_group_rows(const uint8_t *raw, const int64_t *val_off, const int32_t *val_len, const uint8_t *val_type, int64_t n_rec,
+                             const uint8_t *dict_bytes, const int32_t *dict_off, int32_t G, int32_t *rows, void *stream);
+RD_API int rd_bam_group_accumulate(const uint8_t *raw_a, const int64_t *raw_start_a, const int32_t *rows_a, int64_t first_a, int64_t stride_a,
+                                   const uint8_t *raw_b, const int64_t *raw_start_b, const int32_t *rows_b, int64_t first_b, int64_t stride_b,
+                                   const int8_t *labels, int64_t n, int32_t G, int64_t *acc, int64_t *info, void *stream);
+
 /* Reads longer than max_len classified over WINDOWS of max_len bases (CLI extension `--windows`; the reference classifies read[:max_len],
  * reference detect.py:666-726, and that stays the rule without the flag). A window is one more (seq_off, seq_len) entry over the same
  * text, so rd_classify takes the window table as it takes a read table and its kernels do not change.

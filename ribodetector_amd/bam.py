@@ -22,6 +22,13 @@ does. flag & 0x900 (secondary / supplementary): the record is skipped - each rea
 
 BAM output (detect.py --bam_output; device side csrc/rd_bam_raw.hpp): an output file is header(path of its input) followed by
 select(data, keep) - the kept records as they stand in the input, every tag included, in input order - in BGZF members.
+
+Optional fields (find_tag; device side csrc/rd_bam_tags.hpp, C ABI rd_bam_tag_find): the tags of a record lie between the qualities and
+the record's end E = p + 4 + block_size, each one as tag[2] type[1] value. Type A c C: 1 byte; s S: 2; i I f: 4; Z H: bytes up to and
+with a NUL; B: subtype[1] (one of cCsSiIf) count:uint32 and count elements. Every length is data: a tag whose value does not end at or in
+front of E, an unknown type, fewer than 3 bytes left in front of E: the tags are malformed. Read groups (detect.py --read_groups): the
+header text declares them ('@RG' lines, read_groups), a record names its group with RG:Z:<id>, and group_row says which row of the
+per-group counters a record is counted in.
 """
 import struct
 import zlib
@@ -257,3 +264,114 @@ def write_bam(path, reads, *, refs=(), text=b"", level=6, member_bytes=0xff00, e
         if eof:
             fh.write(EOF_MEMBER)
     return data
+
+
+# ---- optional fields (tags) and read groups: the rule the device side (csrc/rd_bam_tags.hpp) is compared against ----------------------
+
+TAG_NONE, TAG_MALFORMED = -1, -2
+_TAG_FIXED = {ord("A"): 1, ord("c"): 1, ord("C"): 1, ord("s"): 2, ord("S"): 2, ord("i"): 4, ord("I"): 4, ord("f"): 4}
+_TAG_B_SIZE = {ord("c"): 1, ord("C"): 1, ord("s"): 2, ord("S"): 2, ord("i"): 4, ord("I"): 4, ord("f"): 4}
+
+
+def find_tag(data, rec_off, tag):
+    """(val_off, val_len, val_type) of the first optional field `tag` (2 bytes) of the record at data[rec_off:] (its block_size field):
+    val_off = where the value starts in `data`, val_len = its bytes (Z / H: without the NUL; B: with subtype and count), val_type = the
+    type byte. (-1, 0, 0): the record has no such tag; (-2, 0, 0): its tags are malformed in front of or at the tag (module docstring) -
+    a malformed tag BEHIND the first occurrence is not seen. No byte at or behind the record's end p + 4 + block_size is looked at."""
+    data, tag, r = bytes(data), bytes(tag), int(rec_off)
+    bad = (TAG_MALFORMED, 0, 0)
+    if len(tag) != 2:
+        raise ValueError("find_tag: a tag has 2 bytes")
+    if r < 0 or r + 36 > len(data):
+        return bad
+    block = struct.unpack_from("<i", data, r)[0]
+    E = r + 4 + block
+    if block < 32 or E > len(data):
+        return bad
+    l_name, n_cigar, l_seq = data[r + 12], struct.unpack_from("<H", data, r + 16)[0], struct.unpack_from("<i", data, r + 20)[0]
+    if l_seq < 0:
+        return bad
+    p = r + 36 + l_name + 4 * n_cigar + (l_seq + 1) // 2 + l_seq
+    if p > E:
+        return bad
+    while p < E:
+        if E - p < 3:
+            return bad
+        name, t, v = data[p:p + 2], data[p + 2], p + 3
+        if t in _TAG_FIXED:
+            n = _TAG_FIXED[t]
+            if v + n > E:
+                return bad
+            nxt = v + n
+        elif t in (ord("Z"), ord("H")):
+            q = data.find(b"\0", v, E)
+            if q < 0:
+                return bad
+            n, nxt = q - v, q + 1
+        elif t == ord("B"):
+            if v + 5 > E or data[v] not in _TAG_B_SIZE:
+                return bad
+            n = 5 + struct.unpack_from("<I", data, v + 1)[0] * _TAG_B_SIZE[data[v]]
+            if v + n > E:
+                return bad
+            nxt = v + n
+        else:
+            return bad
+        if name == tag:
+            return (v, n, t)
+        p = nxt
+    return (TAG_NONE, 0, 0)
+
+
+def read_groups(header_bytes):
+    """[(id bytes, {field: value})] of the '@RG' lines of a header (the bytes header() returns), in header order; field = the two
+    letters in front of the colon (str), value = the rest (str, latin-1). ValueError: an @RG line without ID, with an empty ID, or an
+    ID that an earlier line declared - the message names the line or the ID."""
+    data = bytes(header_bytes)
+    if data[:4] != MAGIC or len(data) < 8:
+        raise ValueError("read_groups: not a BAM header")
+    l_text = struct.unpack_from("<i", data, 4)[0]
+    if l_text < 0 or 8 + l_text > len(data):
+        raise ValueError("read_groups: the header text does not lie inside the header")
+    out, seen = [], set()
+    for k, line in enumerate(data[8:8 + l_text].split(b"\0")[0].split(b"\n")):
+        line = line.rstrip(b"\r")
+        if line[:3] != b"@RG" or (len(line) > 3 and line[3:4] != b"\t"):
+            continue
+        fields, rid = {}, None
+        for f in line.split(b"\t")[1:]:
+            if len(f) >= 3 and f[2:3] == b":":
+                if f[:2] == b"ID" and rid is None:
+                    rid = f[3:]
+                fields.setdefault(f[:2].decode("latin-1"), f[3:].decode("latin-1"))
+        if rid is None:
+            raise ValueError("@RG line without ID (header line %d): %s" % (k + 1, line.decode("latin-1")))
+        if not rid:
+            raise ValueError("@RG line with an empty ID (header line %d)" % (k + 1))
+        if rid in seen:
+            raise ValueError("duplicate @RG ID '%s' (header line %d)" % (rid.decode("latin-1"), k + 1))
+        seen.add(rid)
+        out.append((rid, fields))
+    return out
+
+
+def sorted_ids(ids):
+    """(the ids sorted bytewise as unsigned bytes - a prefix in front of what it is a prefix of -, order): sorted[j] = ids[order[j]].
+    The device's dictionary (rd_bam_group_rows) is the sorted list; order maps its rows back to header order."""
+    order = sorted(range(len(ids)), key=lambda j: bytes(ids[j]))
+    return [bytes(ids[j]) for j in order], order
+
+
+def group_row(data, val_off, val_len, val_type, ids):
+    """the row a record is counted in, from find_tag(data, rec_off, b"RG") and the G = len(ids) declared ids: j for a Z value equal to
+    ids[j]; G: no RG tag; G + 1: a Z value that no @RG line declares; G + 2: malformed tags, or an RG that is not of type Z."""
+    G = len(ids)
+    if val_off == TAG_NONE:
+        return G
+    if val_off < 0 or val_type != ord("Z"):
+        return G + 2
+    value = bytes(data[val_off:val_off + val_len])
+    for j, rid in enumerate(ids):
+        if bytes(rid) == value:
+            return j
+    return G + 1

@@ -29,6 +29,7 @@
 //   rd_report_*                        per-read report lines (id, label, probabilities) of a chunk (rd_report.hpp)
 //   rd_pair_*                          the mates of an interleaved chunk: pair table, mates' sequence tables, mate check (rd_pairs.hpp)
 //   rd_summary_*                       the QC counters of a run, added up chunk by chunk (rd_summary.hpp)
+//   rd_bam_tag_find, rd_bam_group_*    the optional fields of raw BAM records, and the counters per read group (rd_bam_tags.hpp)
 //   rd_window_*                        reads longer than max_len as several windows: the window table and the fusion of its logits (rd_windows.hpp)
 //   rd_region_*                        the rRNA stretches of reads classified over windows, as text lines (rd_regions.hpp)
 #include <stdlib.h>
@@ -50,6 +51,7 @@
 #include "rd_report.hpp"
 #include "rd_pairs.hpp"
 #include "rd_summary.hpp"
+#include "rd_bam_tags.hpp"
 #include "rd_windows.hpp"
 #include "rd_regions.hpp"
 
@@ -1102,6 +1104,74 @@ int rd_summary_accumulate(const uint8_t *text_a, int64_t bytes_a, const int64_t 
                        labels, n, info);
     hipLaunchKernelGGL(rd_summary_acc_kernel, dim3((unsigned)((n + SM_UNITS - 1) / SM_UNITS)), dim3(256), 0, st, text_a, seq_off_a, seq_len_a, logits_a, text_b,
                        seq_off_b, seq_len_b, logits_b, labels, n, acc, info);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+// the optional fields of the raw BAM records of a chunk (rd_bam_tags.hpp): where a tag's value lies, which declared read group it names,
+// and the units and bases per (group, class)
+namespace {
+// lanes per record of rd_bam_tag_find: 4 for short records, 16 when a record's mean size says that long Z / B values are the rule
+// (DESIGN.md §3.23 has the measurement, also of 1 and 64 lanes, which lost on both shapes); RD_TAG_LANES = 4 / 16 overrides it, so that
+// tools/groups_bench.py can time each mapping on each shape
+int tag_lanes(int64_t raw_bytes, int64_t n_rec) {
+    if (const char *e = getenv("RD_TAG_LANES")) {
+        const int v = atoi(e);
+        if (v == 4 || v == 16) return v;
+    }
+    return raw_bytes / n_rec >= 1024 ? 16 : 4;
+}
+}  // namespace
+
+int rd_bam_tag_find(const uint8_t *raw, int64_t raw_bytes, const int64_t *raw_start, int64_t n_rec, const uint8_t *tag, int64_t *val_off, int32_t *val_len,
+                    uint8_t *val_type, void *stream) {
+    if (n_rec < 0 || n_rec > 0x7fffffffLL / 64 || raw_bytes < 0) RD_FAIL(RD_E_INVALID, "rd_bam_tag_find: bad n_rec or raw_bytes");
+    if (!tag) RD_FAIL(RD_E_INVALID, "rd_bam_tag_find: null pointer");
+    if (n_rec == 0) return RD_OK;
+    if ((!raw && raw_bytes > 0) || !raw_start || !val_off || !val_len || !val_type) RD_FAIL(RD_E_INVALID, "rd_bam_tag_find: null pointer");
+    const uint32_t want = (uint32_t)tag[0] | ((uint32_t)tag[1] << 8);
+    hipStream_t st = (hipStream_t)stream;
+    if (tag_lanes(raw_bytes, n_rec) == 16) tag_find_launch<16>(raw, raw_bytes, raw_start, n_rec, want, val_off, val_len, val_type, st);
+    else tag_find_launch<4>(raw, raw_bytes, raw_start, n_rec, want, val_off, val_len, val_type, st);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+int rd_bam_group_rows(const uint8_t *raw, const int64_t *val_off, const int32_t *val_len, const uint8_t *val_type, int64_t n_rec, const uint8_t *dict_bytes,
+                      const int32_t *dict_off, int32_t G, int32_t *rows, void *stream) {
+    if (n_rec < 0 || n_rec > 0x7fffffffLL || G < 0 || G > RD_GROUPS_MAX) RD_FAIL(RD_E_INVALID, "rd_bam_group_rows: bad n_rec or G");
+    if (n_rec == 0) return RD_OK;
+    if (!raw || !val_off || !val_len || !val_type || !rows || !dict_off || (G > 0 && !dict_bytes)) RD_FAIL(RD_E_INVALID, "rd_bam_group_rows: null pointer");
+    const int64_t wgs = (n_rec + GR_THREADS - 1) / GR_THREADS;
+    if (G <= GR_ROWS_LDS)                                 // the dictionary in LDS, staged once per workgroup: fewer, longer-lived workgroups
+        hipLaunchKernelGGL(rd_bam_group_rows_lds_kernel, dim3((unsigned)(wgs < 1024 ? wgs : 1024)), dim3(GR_THREADS), 0, (hipStream_t)stream, raw, val_off, val_len,
+                           val_type, n_rec, dict_bytes, dict_off, G, rows);
+    else
+        hipLaunchKernelGGL(rd_bam_group_rows_kernel, dim3((unsigned)wgs), dim3(GR_THREADS), 0, (hipStream_t)stream, raw, val_off, val_len, val_type, n_rec, dict_bytes,
+                           dict_off, G, rows);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+int rd_bam_group_accumulate(const uint8_t *raw_a, const int64_t *raw_start_a, const int32_t *rows_a, int64_t first_a, int64_t stride_a, const uint8_t *raw_b,
+                            const int64_t *raw_start_b, const int32_t *rows_b, int64_t first_b, int64_t stride_b, const int8_t *labels, int64_t n, int32_t G,
+                            int64_t *acc, int64_t *info, void *stream) {
+    if (n < 0 || n > 0x7fffffffLL || G < 0 || G > RD_GROUPS_MAX) RD_FAIL(RD_E_INVALID, "rd_bam_group_accumulate: bad n or G");
+    if (first_a < 0 || stride_a < 1 || (raw_b && (first_b < 0 || stride_b < 1))) RD_FAIL(RD_E_INVALID, "rd_bam_group_accumulate: bad first / stride");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        if (info) RD_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int64_t), st));
+        return RD_OK;
+    }
+    if (!acc || !info || !labels || !raw_a || !raw_start_a || !rows_a) RD_FAIL(RD_E_INVALID, "rd_bam_group_accumulate: null pointer");
+    if (raw_b && (!raw_start_b || !rows_b)) RD_FAIL(RD_E_INVALID, "rd_bam_group_accumulate: mate 2 needs its record table and rows");
+    if (!raw_b) rows_b = nullptr;                         // (single-end: the check pass skips mate 2 by this pointer)
+    RD_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int64_t), st));
+    hipLaunchKernelGGL(rd_bam_group_check_kernel, dim3((unsigned)((n + GR_THREADS - 1) / GR_THREADS)), dim3(GR_THREADS), 0, st, rows_a, first_a, stride_a, rows_b, first_b,
+                       stride_b, labels, n, G, info);
+    const int64_t tiles = (n + GR_THREADS - 1) / GR_THREADS;
+    hipLaunchKernelGGL(rd_bam_group_acc_kernel, dim3((unsigned)(tiles < GR_MAX_WGS ? tiles : GR_MAX_WGS)), dim3(GR_THREADS), 0, st, raw_a, raw_start_a, rows_a, first_a,
+                       stride_a, raw_b, raw_start_b, rows_b, first_b, stride_b, labels, n, G, acc, info);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }

@@ -36,6 +36,8 @@ FASTQ text, so the chunks are FASTQ chunks and the outputs FASTQ files. One rank
 --bam_output (an extension, BAM input): the chunks also carry their records as they stand in the input (DeviceChunk.raw: rd_bam_raw_tab /
 rd_bam_raw_gather, csrc/rd_bam_raw.hpp), and the output kernels select from THAT view (_select_chunk): every output is a BAM file - the
 header of its input, the selected records byte for byte, BGZF members. Classification, report, summary and regions see the FASTQ view.
+--read_groups (an extension, BAM input, with --summary): the chunks carry the same raw view, and every chunk's units are counted per
+read group on the post stream (groups.py: rd_bam_tag_find / rd_bam_group_rows / rd_bam_group_accumulate); the summary gains "read_groups".
 """
 import argparse
 import functools
@@ -55,6 +57,7 @@ from . import __version__
 from . import _native as _native_mod
 from . import bam as _bammod
 from . import dist as rdist
+from . import groups as _grpmod
 from . import gz as _gzmod
 from . import regions as _regmod
 from . import summary as _summod
@@ -235,6 +238,8 @@ class Predictor:
         self.interleaved = bool(getattr(args, 'interleaved', False))     # paired-end reads from ONE interleaved FASTQ file
         self.mate_check = not getattr(args, 'no_mate_check', False)
         self.bam_output = bool(getattr(args, 'bam_output', False))       # BAM outputs: the selected records as they stand in the input
+        self.read_groups = bool(getattr(args, 'read_groups', False))     # --summary gains the counters per BAM read group
+        self._groups = None                      # ... groups.DeviceGroups (run_with_chunks)
         self._pairs = None                       # --interleaved: gz.DevicePairSplit (run_with_chunks)
         self._summary = None                     # --summary: summary.DeviceSummary (run_with_chunks)
         self._windows = None                     # --windows: {"stride", "max_per_read", "fuse"} (stride None = -l); detect() sets it
@@ -538,6 +543,10 @@ class Predictor:
             if self._summary is not None:           # --summary: this rank's units of the chunk, counted where they are (rd_summary_accumulate)
                 sum_info = _pinned(self._summary.add(dev_in[0], outs[0][0], dev_in[1] if self.is_paired else None,
                                                      outs[1][0] if self.is_paired else None, labels.view(torch.int8)))
+            grp_info, keep_raw = None, None
+            if self._groups is not None:            # --read_groups: the same units per read group, over the chunks' raw records
+                grp_info = _pinned(self._groups.add(chunks, labels.view(torch.int8), self.interleaved))
+                keep_raw = [c.raw for c in chunks]
             finish = None
             if self.gathers_labels:                 # label gather (1 B per read) queued behind the kernels, collected later
                 _, finish = rdist.gather_labels(labels, n, dst=0, bounds=bounds, async_op=True)
@@ -545,7 +554,7 @@ class Predictor:
             done.record(post)
         return {"n": n, "bounds": bounds, "labels": labels, "host": host, "finish": finish, "done": done, "keep": (dev_in, outs, plans),
                 "pieces": pieces, "pairs": pairs, "chunk": chunks[0], "totals": [t for c in chunks for t in (c.total, c.raw_total) if t is not None] if on_dev else (), "summary": sum_info,
-                "regions": regions}
+                "regions": regions, "groups": grp_info, "keep_raw": keep_raw}
 
     def _select_chunk(self, chunks, dev_in, labels, lo, hi, on_dev, pairs=None):
         """{(mate, label): [Piece]}: the label files whose records of this chunk are selected on the device, on the post stream beside
@@ -667,7 +676,7 @@ class Predictor:
     def collect_chunk(self, tk):
         """Labels of a submitted chunk: int8 numpy on rank 0 (whole chunk, input order), None elsewhere."""
         if self.gathers_labels:
-            if tk["pairs"] is not None or tk["summary"] is not None or tk["regions"] is not None:     # every rank checks the mates, the counters and the regions of its own shard
+            if tk["pairs"] is not None or tk["summary"] is not None or tk["regions"] is not None or tk.get("groups") is not None:     # every rank checks the mates, the counters and the regions of its own shard
                 _native_mod.wait_event(tk["done"])
             if tk["pairs"] is not None:
                 self._check_pairs(tk["chunk"], tk["pairs"])
@@ -693,6 +702,9 @@ class Predictor:
         if tk["summary"] is not None and int(tk["summary"][0]):
             raise RuntimeError("device summary: the chunk's sequence tables or labels are not what the counters can take (fault %d); "
                                "nothing of the chunk was counted" % int(tk["summary"][0]))
+        if tk.get("groups") is not None and int(tk["groups"][0]):
+            raise RuntimeError("device read groups: the chunk's labels or group rows are not what the counters can take (fault %d); "
+                               "nothing of the chunk was counted" % int(tk["groups"][0]))
 
     def _gather_pieces(self, tk):
         """label gather: the pieces every rank made of its shard travel to rank 0, which appends them in rank order = input order
@@ -737,7 +749,7 @@ class Predictor:
                 if arena is None and self._device_parse(path):
                     st = self.ingest.setdefault(os.path.basename(str(path)), {"path": "device"})
                     stream = dr.get_seq_chunks_device(path, chunk_size=chunk_reads, byte_range=byte_range, first_chunk=first, schedule=schedule,
-                                                      device=self.device, stats=st, keep_raw=self.bam_output)
+                                                      device=self.device, stats=st, keep_raw=self.bam_output or self.read_groups)
                 # one plain input file: its parser thread was the slowest stage of the pipeline - two readers over byte segments,
                 # small first chunks (mate files keep one reader each and exact chunk sizes: their chunks must pair up)
                 # (not an interleaved file: its chunks must hold whole pairs)
@@ -1003,9 +1015,19 @@ class Predictor:
                                         self._windows, stride=int(self._windows["stride"] or self.len), classified=list(self._win_total),
                                         **({"regions": list(self._reg_total[0]), "reads_with_regions": list(self._reg_total[1])}
                                            if self._regions else {}))})
+        if self._groups is not None:               # (BAM input: one rank)
+            gacc, grp = self._groups.result(), self._groups
+            got = _grpmod.units_per_class(gacc, grp.G)
+            if got != units:
+                raise RuntimeError("--read_groups: the rows of the read groups hold {} unclassified / non-rRNA / rRNA units, the run {}".format(got, units))
+            rg = doc["read_groups"] = _grpmod.to_json(gacc, grp.groups, bool(self.is_paired), input=self.input[0])
         _summod.write_json(path, doc)
         frac = doc["reads"]["rRNA_fraction"]
         self.logger.info('rRNA fraction: {} (summary: {})'.format("n/a" if frac is None else "%.6f" % frac, path))
+        if self._groups is not None:
+            self.logger.info('Read groups: {} declared, {} with reads; {} reads without RG, {} undeclared, {} with malformed tags'.format(
+                len(rg["groups"]), sum(1 for g in rg["groups"] if g["units"]["total"]), rg["none"]["units"]["total"],
+                rg["undeclared"]["units"]["total"], rg["malformed_tags"]["units"]["total"]))
 
     def _mark(self, event, t=None):
         """the first events of the run on its timeline, seconds since it started (timing first_chunks_timeline: tools/first_chunk_probe.py)"""
@@ -1142,6 +1164,8 @@ class Predictor:
         self._rep_seq = 0
         # --summary: the run's QC counters, one int64 array per rank that every chunk adds to on the post stream
         self._summary = _summod.DeviceSummary(self.device) if getattr(self.args, 'summary', None) else None
+        # --read_groups: the same units per read group of mate 1's BAM, one more int64 array that every chunk adds to
+        self._groups = _grpmod.DeviceGroups(self.device, _bammod.header(self.input[0])) if self.read_groups else None
         self._win_classified = [0, 0]
         # --regions: the lines of every chunk, formatted on the device; mate 1's writer appends the pieces (and deflates a .gz file)
         self._regions = bool(getattr(self.args, 'regions', None))
@@ -1235,6 +1259,7 @@ class Predictor:
                           self.args.ensure, self.bam_output)
         check_summary(getattr(self.args, 'summary', None), self.output, self.rrna, self.is_paired, self.args.ensure,
                       getattr(self.args, 'read_report', None), self.bam_output)
+        check_read_groups(self.read_groups, getattr(self.args, 'summary', None), self.input)
         self._windows = check_windows(self.args)
         check_regions(getattr(self.args, 'regions', None), self._windows is not None, self.output, self.rrna, self.is_paired, self.args.ensure,
                       getattr(self.args, 'read_report', None), getattr(self.args, 'summary', None), self.bam_output)
@@ -1372,6 +1397,34 @@ def check_summary(path, output, rrna, is_paired, ensure, read_report=None, bam_o
             raise RuntimeError("--summary {} is also {}".format(path, what))
 
 
+def check_read_groups(read_groups, summary, inputs):
+    """--read_groups: the rules that hold before anything touches a device; returns the declared groups of mate 1's BAM
+    (bam.read_groups: [(id, fields)], header order), or None without the flag. The flag adds an object to the --summary file, so it
+    needs one; the groups are those of BAM records and of a BAM header, so every input is BAM; the @RG lines of the header must be a
+    dictionary (an ID each, none empty, none twice) of at most 65,536 groups. The header is read by the host's zlib."""
+    if not read_groups:
+        return None
+    if not summary:
+        raise RuntimeError("--read_groups adds the counters per read group to the --summary file: give --summary PATH too (checked before "
+                           "anything touches a device)")
+
+    def fmt(path):
+        try:
+            return fx.get_seq_format(path)
+        except ValueError:
+            return None
+    if not inputs or any(fmt(p) != "bam" for p in inputs):
+        raise RuntimeError("--read_groups counts the reads per RG tag of BAM records: every -i file must end with .bam or .ubam, got {} "
+                           "(checked before anything touches a device)".format(", ".join(str(p) for p in inputs or [])))
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("--read_groups runs on one rank (checked before anything touches a device)")
+    try:
+        header = _bammod.header(inputs[0])
+    except (OSError, ValueError) as e:
+        raise RuntimeError("--read_groups: cannot read the header of {}: {} (checked before anything touches a device)".format(inputs[0], e))
+    return _grpmod.check_groups(header)
+
+
 def check_windows(args):
     """--windows and its settings, checked before anything touches a device: None without the flag, else {"stride" (None = -l),
     "max_per_read", "fuse"}. RuntimeError for a setting without --windows, a stride outside 1..2^31-1 or more than 4096 (or fewer than
@@ -1479,6 +1532,12 @@ none: give label based on the mean probability of read pair.
                       help='(extension) BAM input only: -o / -r take .bam / .ubam names, and every output file is a BAM file - the header of\n'
                            'its input and the selected records, byte for byte as they stand in the input (every tag kept), in input\n'
                            'order. Secondary / supplementary records are in no output. No @PG line is added.')
+    args.add_argument('--read_groups', action='store_true',
+                      help='(extension) BAM input with --summary: the summary gains "read_groups" - units (reads or pairs) and bases per\n'
+                           'label for every @RG line of the header of the first -i file (by the records\' RG:Z tag; a pair counts in\n'
+                           'mate 1\'s group), and for the records without RG, with an RG that no @RG line declares, and with malformed\n'
+                           'tags. Counted on the GPU over the records as they stand in the input, which the run then keeps in GPU\n'
+                           'memory next to the FASTQ text (about 0.75 of its bytes more).')
     args.add_argument('--no_mate_check', action='store_true', help='(extension) with --interleaved: do not compare the ids of the mates')
     args.add_argument('-v', '--version', action='version', version='%(prog)s {version}'.format(version=__version__))
     return args
@@ -1491,6 +1550,7 @@ def main(argv=None, log_level=None):
     check_windows(args)                          # (before the model is loaded: nothing has touched a device yet)
     check_regions(getattr(args, 'regions', None), getattr(args, 'windows', False))
     check_bam(args.input, args.output, args.rrna, getattr(args, 'bam_output', False))
+    check_read_groups(getattr(args, 'read_groups', False), getattr(args, 'summary', None), args.input)
     seq_pred = Predictor(config, args, log_level=log_level)
     try:
         t0 = time.perf_counter()
