@@ -347,6 +347,27 @@ RD_API int rd_bam_gather(const uint8_t *norm, const int64_t *rec_tab, const int3
                   int64_t *seq_off, int32_t *seq_len, void *stream);
 RD_API int rd_bam_sample(const int64_t *rec_tab, const rd_fq_summary *summary, int64_t every, int32_t *samples, int64_t cap, void *stream);
 
+/* A BAM file shared by the ranks of a run (detect.py --bam_shard): where a record starts behind an arbitrary offset of the inflated
+ * bytes, and how many records a share holds. The rule of both is ribodetector_amd/bam.py (find_record_start, records).
+ * rd_bam_find_start: text [dev, 16-byte aligned] holds the window [0, end) of inflated bytes, end < 2^31; every offset of [lo, hi)
+ * (0 <= lo <= hi <= end) is a CANDIDATE. A candidate is CONFIRMED when it and the next RD_BAM_CONFIRM - 1 records of the chain from
+ * it each carry the signature of a record (block_size in 33 .. 2^26, refID / pos / next_refID / next_pos >= -1, lengths that fit in
+ * block_size, a name of printable bytes that ends in NUL) and lie in front of `end` as a whole, or when the chain reaches exactly
+ * `end` behind at least one such record and at_eof != 0 (the window ends where the file's data ends). It is REJECTED when a record of
+ * its chain fails, and UNDECIDED when the window ends before either (at_eof == 0 only). info [dev] int64[4]: info[0] = the smallest
+ * confirmed candidate or -1, info[1] = the smallest undecided one or -1, info[2] = 0, info[3] != 0: bad lo / hi / end, nothing was
+ * searched. A caller accepts info[0] only when info[1] is -1 or larger, and looks again with more bytes otherwise. The answer is a
+ * record start unless RD_BAM_CONFIRM records in a row are imitated by the payload of one; it need not be the first one behind lo (a
+ * record of more than 64 MiB does not carry the signature). No byte at or behind `end` is read, whatever the data says.
+ * rd_bam_count: the contract of rd_bam_index without norm, the tables and the text: the same walk from the same carry (text / pad /
+ * end / prev_text / prev / final as there), the same summary - n_records delivered, n_lines walked, consumed, status (RD_FQ_LINES
+ * cannot occur), bad_record, dirty, reserved = the bytes of FASTQ text the records would become. */
+#define RD_BAM_CONFIRM 8
+RD_API int rd_bam_find_start(const uint8_t *text, int64_t lo, int64_t hi, int64_t end, int32_t at_eof, int64_t *info, void *stream);
+RD_API size_t rd_bam_count_workspace_bytes(int64_t text_end);
+RD_API int rd_bam_count(uint8_t *text, int64_t pad, int64_t end, const uint8_t *prev_text, const rd_fq_summary *prev, int32_t final, rd_fq_summary *summary,
+                 void *workspace, size_t workspace_bytes, void *stream);
+
 /* The delivered records of a framed BAM batch as they stand in the input - block_size, fixed fields, name, CIGAR, packed bases,
  * qualities and every tag, nothing decoded - next to their FASTQ text (the rule: ribodetector_amd/bam.py select). The skipped records
  * lie between them, so the raw view is a table and a gather. rd_bam_index_src [host, no launch]: the address of the table of source

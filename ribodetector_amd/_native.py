@@ -25,7 +25,7 @@ SYMBOLS = [
     "rd_pair_fuse", "rd_count_labels", "rd_encode_codes", "rd_encode_onehot_padded", "rd_pack_plan",
     "rd_pack_onehot", "rd_profile_enable", "rd_profile_read", "rd_last_error", "rd_version",
     "rd_gz_workspace_bytes", "rd_gz_out_bound", "rd_gz_compress_selected", "rd_gz_eof_block", "rd_gz_inflate_members",
-    "rd_fastq_index_workspace_bytes", "rd_fastq_index", "rd_fastq_gather", "rd_fastq_sample", "rd_fastq_strip_mark", "rd_fasta_index_workspace_bytes", "rd_fasta_index", "rd_fasta_gather", "rd_fasta_sample", "rd_bam_index_workspace_bytes", "rd_bam_index", "rd_bam_gather", "rd_bam_sample", "rd_bam_index_src", "rd_bam_raw_tab", "rd_bam_raw_gather", "rd_select_workspace_bytes", "rd_select_pack", "rd_stream_create", "rd_stream_destroy", "rd_copy_bytes", "rd_gz_stream_workspace_bytes", "rd_gz_stream_inflate",
+    "rd_fastq_index_workspace_bytes", "rd_fastq_index", "rd_fastq_gather", "rd_fastq_sample", "rd_fastq_strip_mark", "rd_fasta_index_workspace_bytes", "rd_fasta_index", "rd_fasta_gather", "rd_fasta_sample", "rd_bam_index_workspace_bytes", "rd_bam_index", "rd_bam_gather", "rd_bam_sample", "rd_bam_index_src", "rd_bam_find_start", "rd_bam_count_workspace_bytes", "rd_bam_count", "rd_bam_raw_tab", "rd_bam_raw_gather", "rd_select_workspace_bytes", "rd_select_pack", "rd_stream_create", "rd_stream_destroy", "rd_copy_bytes", "rd_gz_stream_workspace_bytes", "rd_gz_stream_inflate",
     "rd_gz_range_workspace_bytes", "rd_gz_range_decode", "rd_gz_range_resolve_workspace_bytes", "rd_gz_range_resolve",
     "rd_report_workspace_bytes", "rd_report_out_bound", "rd_report_format",
     "rd_pair_split", "rd_pair_expand_labels",
@@ -36,6 +36,7 @@ SYMBOLS = [
 ]
 WINDOW_MAX = 4096       # include/ribodetector_amd.h RD_WINDOW_MAX: the most windows a read can have
 BAM_SEGMENT = 32768     # RD_BAM_SEGMENT: bytes per segment of the BAM framing (csrc/rd_bam_index.hpp)
+BAM_CONFIRM = 8         # RD_BAM_CONFIRM: records in a row that confirm a record start (csrc/rd_bam_shard.hpp; bam.find_record_start)
 BAM_RECORD, BAM_TRUNCATED = 6, 7      # RD_BAM_RECORD / RD_BAM_TRUNCATED: the two statuses rd_bam_index adds to RD_FQ_*
 WINDOW_FUSE = {"mean": 0, "max": 1}     # RD_WINDOW_MEAN / RD_WINDOW_MAX_D
 GROUPS_MAX = 65536      # RD_GROUPS_MAX: the most read groups a dictionary of rd_bam_group_rows holds
@@ -118,6 +119,10 @@ def lib():
     L.rd_bam_sample.argtypes = [vp, vp, i64, vp, i64, vp]
     L.rd_bam_index_src.argtypes = [vp, i64]
     L.rd_bam_index_src.restype = vp
+    L.rd_bam_find_start.argtypes = [vp, i64, i64, i64, i32, vp, vp]
+    L.rd_bam_count_workspace_bytes.argtypes = [i64]
+    L.rd_bam_count_workspace_bytes.restype = sz
+    L.rd_bam_count.argtypes = [vp, i64, i64, vp, vp, i32, vp, vp, sz, vp]
     L.rd_bam_raw_tab.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, vp]
     L.rd_bam_raw_gather.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, i64, vp, vp, vp, vp]
     L.rd_select_workspace_bytes.argtypes = [i64]

@@ -43,6 +43,10 @@ SKIP_FLAGS = 0x900
 MALFORMED = "malformed BAM record %d"
 TRUNCATED = "truncated BAM record at end of file"
 EOF_MEMBER = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+# --bam_shard (data_loader/bam_shard.py): a share of a rank begins where find_record_start says a record starts
+NO_START = "no BAM record start within %d bytes behind offset %d of %s"
+NOT_A_BOUNDARY = ("the share boundary at offset %d of %s is not a BAM record boundary (a byte pattern that looks like %d records in a row): "
+                  "run this file on one rank")
 
 
 def header_len(data):
@@ -182,6 +186,98 @@ def records(data, start=None):
 def fastq_text(data, start=None):
     """the FASTQ text of the records of `data` that count (module docstring); raises what records() raises"""
     return b"".join(r.fastq() for r in records(data, start) if not r.skipped)
+
+
+# ---- a record start at or behind an offset (detect.py --bam_shard; device side csrc/rd_bam_shard.hpp, C ABI rd_bam_find_start) ------
+
+CONFIRM = N.BAM_CONFIRM          # RD_BAM_CONFIRM: records in a row that make a candidate offset a record start
+
+
+def plausible(data, q, end):
+    """does offset q of `data` carry the SIGNATURE of a record (bam_plausible of csrc/rd_bam_index.hpp, restated)? block_size in
+    33..2^26; refID, pos, next_refID, next_pos >= -1; l_read_name >= 1; the lengths fit in block_size; the name's NUL where it belongs
+    when it lies in front of `end`; the first min(l_read_name - 1, 16) name bytes (those in front of `end`) in 33..126. No byte at or
+    behind `end` is looked at; q + 36 > end: False."""
+    if q + 36 > end:
+        return False
+    block, ref_id, pos = struct.unpack_from("<iii", data, q)
+    if block < 33 or block > (1 << 26):
+        return False
+    next_ref, next_pos = struct.unpack_from("<ii", data, q + 24)
+    if ref_id < -1 or pos < -1 or next_ref < -1 or next_pos < -1:
+        return False
+    l_name, n_cigar, l_seq = data[q + 12], struct.unpack_from("<H", data, q + 16)[0], struct.unpack_from("<I", data, q + 20)[0]
+    if l_name < 1 or 32 + l_name + 4 * n_cigar + (l_seq + 1) // 2 + l_seq > block:
+        return False
+    nul = q + 36 + l_name - 1
+    if nul < end and data[nul] != 0:
+        return False
+    for i in range(min(l_name - 1, 16)):
+        if q + 36 + i >= end:
+            break
+        if not 33 <= data[q + 36 + i] <= 126:
+            return False
+    return True
+
+
+CONFIRMED, REJECTED, UNDECIDED = 1, 0, -1
+
+
+def chain_verdict(data, q, end, at_eof, confirm=CONFIRM):
+    """the verdict on candidate q of find_record_start: the chain of records from q is followed for `confirm` records.
+    At p == end (behind at least one record): CONFIRMED with at_eof, else UNDECIDED. Fewer than 36 bytes in front of `end`: the
+    signature cannot be tested - REJECTED with at_eof (the walk of `records` ends in a truncated record there), else UNDECIDED. A
+    record that is not plausible: REJECTED. One that is, and does not lie in front of `end` as a whole: REJECTED with at_eof, else
+    UNDECIDED. (A plausible record that lies in front of `end` as a whole is well-formed by the rule of `records`: the signature holds
+    every one of its tests.) `confirm` such records: CONFIRMED."""
+    p = q
+    for _ in range(confirm):
+        if p == end:
+            return CONFIRMED if at_eof else UNDECIDED
+        if p + 36 > end:
+            return REJECTED if at_eof else UNDECIDED
+        if not plausible(data, p, end):
+            return REJECTED
+        block = struct.unpack_from("<i", data, p)[0]
+        if p + 4 + block > end:
+            return REJECTED if at_eof else UNDECIDED
+        p += 4 + block
+    return CONFIRMED
+
+
+def find_record_start(data, lo, hi, at_eof, confirm=CONFIRM):
+    """(found, undecided) among the candidate offsets [lo, hi) of the window `data` (inflated BAM bytes, hi <= len(data)): found = the
+    smallest candidate whose chain_verdict is CONFIRMED, undecided = the smallest one whose verdict is UNDECIDED (the window ends before
+    its chain is confirmed or rejected); -1: none. at_eof: the window ends where the file's data ends. A caller accepts `found` only
+    when no smaller candidate is undecided, and looks again with more bytes otherwise. `found` is a record start unless `confirm`
+    records in a row are imitated by the bytes of a record (a tag's payload, say); it need not be the FIRST one at or behind lo - a record
+    of more than 64 MiB is not plausible, and is stepped over."""
+    data = bytes(data)
+    end = len(data)
+    lo, hi = int(lo), int(hi)
+    if lo < 0 or hi > end:
+        raise ValueError("find_record_start: [lo, hi) does not lie in the window")
+    import numpy as np
+    # (nearly every offset is rejected by its block_size alone: those are sorted out at once, the rule is applied to the others)
+    a = np.frombuffer(data, dtype=np.uint8)
+    full = max(lo, min(hi, end - 35))               # candidates [lo, full) have their 36 fixed bytes in the window
+    cand = []
+    if full > lo:
+        # block_size in 33 .. 2^26: its top byte is 0..4 (a negative one: >= 0x80) - a test of one byte sorts out most offsets
+        few = lo + np.flatnonzero(a[lo + 3:full + 3] <= 4)
+        b = [a[few + k].astype(np.uint32) for k in range(4)]
+        block = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24)
+        cand = few[(block >= 33) & (block <= (1 << 26))].tolist()
+    found = undecided = -1
+    for q in cand + list(range(full, hi)):
+        if found >= 0 and undecided >= 0:
+            break
+        v = chain_verdict(data, q, end, at_eof, confirm)
+        if v == CONFIRMED and found < 0:
+            found = q
+        elif v == UNDECIDED and undecided < 0:
+            undecided = q
+    return found, undecided
 
 
 # ---- a writer that follows the specification (tests and tools make their inputs with it) --------------------------------------------

@@ -132,6 +132,9 @@ __device__ __forceinline__ bool bam_plausible(const BamBytes &b, int64_t q, int6
     return true;
 }
 
+// TABLES: the local lists of the delivered records are written (rd_bam_index); false: the records are counted only (rd_bam_count,
+// rd_bam_shard.hpp - `lists` is not touched)
+template <bool TABLES>
 __global__ __launch_bounds__(64) void rd_bam_walk_kernel(const uint8_t *__restrict__ text, const FqSummary *__restrict__ sum, BamSeg *__restrict__ seg,
                                                          int2 *__restrict__ lists) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[BAM_STAGE];
@@ -175,17 +178,19 @@ __global__ __launch_bounds__(64) void rd_bam_walk_kernel(const uint8_t *__restri
     BamSeg w = {};
     w.guess = -1;
     w.exit = (int32_t)lo;
-    if (entry >= 0) w = bam_walk(b, entry, hi, end, lists + s * BAM_LIST, lane == 0);
+    if (entry >= 0) w = bam_walk(b, entry, hi, end, TABLES ? lists + s * BAM_LIST : nullptr, TABLES && lane == 0);
     if (lane == 0) seg[s] = w;
 }
 
+// TABLES: as in the walk; false: seg_rbase / seg_nbase / seg_cnt / sc / rec_tab are not touched, and no table can be too small
+template <bool TABLES>
 __global__ __launch_bounds__(64) void rd_bam_stitch_kernel(const uint8_t *__restrict__ text, FqSummary *__restrict__ sum, BamSeg *__restrict__ seg,
                                                            int2 *__restrict__ lists, int nseg, int32_t *__restrict__ seg_rbase, int64_t *__restrict__ seg_nbase,
                                                            int32_t *__restrict__ seg_cnt, BamScratch *__restrict__ sc, int final, int64_t norm_cap,
                                                            int64_t cap_records, int64_t *__restrict__ rec_tab) {
     const int lane = threadIdx.x;
     if (sum->status != RD_FQ_OK) {
-        if (lane == 0) sc->nseg_used = 0;
+        if (TABLES && lane == 0) sc->nseg_used = 0;
         return;
     }
     const int64_t begin = sum->begin, end = sum->end;
@@ -234,7 +239,7 @@ __global__ __launch_bounds__(64) void rd_bam_stitch_kernel(const uint8_t *__rest
                     const int64_t tn = __shfl_up(nb, o);
                     if (lane >= o) { c += tc; wk += tw; nb += tn; }
                 }
-                if (live) {
+                if (TABLES && live) {
                     seg_rbase[s0 + lane] = (int32_t)n + c - c0;
                     seg_nbase[s0 + lane] = norm + nb - (on ? mine.norm : 0);
                     seg_cnt[s0 + lane] = c0;
@@ -265,7 +270,7 @@ __global__ __launch_bounds__(64) void rd_bam_stitch_kernel(const uint8_t *__rest
                 w.cnt = 0;
             } else {
                 if ((int64_t)w.guess != p) {         // the guess was wrong (or there was none): the walk from the true entry
-                    w = bam_walk(g, p, hi, end, lists + (int64_t)(s0 + k) * BAM_LIST, lane == 0);
+                    w = bam_walk(g, p, hi, end, TABLES ? lists + (int64_t)(s0 + k) * BAM_LIST : nullptr, TABLES && lane == 0);
                     w.exit = __builtin_amdgcn_readfirstlane(w.exit);       // (every lane walked the same chain)
                     w.kind = __builtin_amdgcn_readfirstlane(w.kind);
                     w.walked = __builtin_amdgcn_readfirstlane(w.walked);
@@ -284,17 +289,17 @@ __global__ __launch_bounds__(64) void rd_bam_stitch_kernel(const uint8_t *__rest
             if (lane == k) my_cnt = w.cnt;
             if (kind != BAM_RAN) { over = true; break; }
         }
-        if (s0 + lane < used) {
+        if (TABLES && s0 + lane < used) {
             seg_rbase[s0 + lane] = my_rbase;
             seg_nbase[s0 + lane] = my_nbase;
             seg_cnt[s0 + lane] = my_cnt;
         }
     }
     if (lane == 0) {
-        sc->nseg_used = used;
+        if (TABLES) sc->nseg_used = used;
         sum->n_lines = walked;                       // (BAM: the records walked, the skipped ones included)
         sum->dirty = rewalks;                        // (BAM: the segments walked again by the stitch)
-        if (n + 1 > cap_records || norm > norm_cap) {
+        if (TABLES && (n + 1 > cap_records || norm > norm_cap)) {
             sum->status = RD_FQ_LINES;               // the caller's tables are too small for this batch: framed again with full-size ones
             sum->n_records = 0;
             sum->consumed = begin;
@@ -303,7 +308,7 @@ __global__ __launch_bounds__(64) void rd_bam_stitch_kernel(const uint8_t *__rest
             sum->n_records = n;
             sum->consumed = p;
             sum->reserved = norm;
-            rec_tab[n] = norm;
+            if (TABLES) rec_tab[n] = norm;
             if (kind == BAM_ILL) {
                 sum->status = RD_BAM_RECORD;
                 sum->bad_record = (unsigned long long)walked;

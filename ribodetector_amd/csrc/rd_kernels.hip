@@ -29,6 +29,7 @@
 //   rd_report_*                        per-read report lines (id, label, probabilities) of a chunk (rd_report.hpp)
 //   rd_pair_*                          the mates of an interleaved chunk: pair table, mates' sequence tables, mate check (rd_pairs.hpp)
 //   rd_summary_*                       the QC counters of a run, added up chunk by chunk (rd_summary.hpp)
+//   rd_bam_find_*, rd_bam_count        a record start behind an offset of inflated BAM bytes, the records of a share (rd_bam_shard.hpp)
 //   rd_bam_tag_find, rd_bam_group_*    the optional fields of raw BAM records, and the counters per read group (rd_bam_tags.hpp)
 //   rd_window_*                        reads longer than max_len as several windows: the window table and the fusion of its logits (rd_windows.hpp)
 //   rd_region_*                        the rRNA stretches of reads classified over windows, as text lines (rd_regions.hpp)
@@ -47,6 +48,7 @@
 #include "rd_fastq_index.hpp"
 #include "rd_fasta_index.hpp"
 #include "rd_bam_index.hpp"
+#include "rd_bam_shard.hpp"
 #include "rd_bam_raw.hpp"
 #include "rd_report.hpp"
 #include "rd_pairs.hpp"
@@ -938,8 +940,8 @@ int rd_bam_index(uint8_t *text, int64_t pad, int64_t end, const uint8_t *prev_te
     hipStream_t st = (hipStream_t)stream;
     FqSummary *sum = (FqSummary *)summary;
     hipLaunchKernelGGL(rd_fq_begin_kernel<false>, dim3(1), dim3(FQ_THREADS), 0, st, text, pad, end, prev_text, (const FqSummary *)prev, (int)final, sum);
-    hipLaunchKernelGGL(rd_bam_walk_kernel, dim3(p.nseg), dim3(64), 0, st, text, sum, p.seg, p.lists);
-    hipLaunchKernelGGL(rd_bam_stitch_kernel, dim3(1), dim3(64), 0, st, text, sum, p.seg, p.lists, p.nseg, p.seg_rbase, p.seg_nbase, p.seg_cnt, p.sc, (int)final, norm_cap,
+    hipLaunchKernelGGL(rd_bam_walk_kernel<true>, dim3(p.nseg), dim3(64), 0, st, text, sum, p.seg, p.lists);
+    hipLaunchKernelGGL(rd_bam_stitch_kernel<true>, dim3(1), dim3(64), 0, st, text, sum, p.seg, p.lists, p.nseg, p.seg_rbase, p.seg_nbase, p.seg_cnt, p.sc, (int)final, norm_cap,
                        cap_records, rec_tab);
     hipLaunchKernelGGL(rd_bam_table_kernel, dim3(p.nseg), dim3(64), 0, st, text, sum, p.sc, p.lists, p.seg_rbase, p.seg_nbase, p.seg_cnt, rec_tab, hdr_tab, p.src_tab);
     int64_t grid = (4 * end / 3 + 64) / BAM_EMIT_BYTES + 1;      // (the text of a window is at most 4 / 3 of its bytes)
@@ -958,6 +960,41 @@ int rd_bam_gather(const uint8_t *norm, const int64_t *rec_tab, const int32_t *hd
 
 int rd_bam_sample(const int64_t *rec_tab, const rd_fq_summary *summary, int64_t every, int32_t *samples, int64_t cap, void *stream) {
     return fq_sample("rd_bam_sample", rd_fa_sample_kernel<true>, rec_tab, summary, every, samples, cap, stream);
+}
+
+// ---- a BAM file shared by the ranks of a run (rd_bam_shard.hpp)
+int rd_bam_find_start(const uint8_t *text, int64_t lo, int64_t hi, int64_t end, int32_t at_eof, int64_t *info, void *stream) {
+    if (!info || (!text && end > 0)) RD_FAIL(RD_E_INVALID, "rd_bam_find_start: null pointer");
+    if ((uintptr_t)text & 15) RD_FAIL(RD_E_INVALID, "rd_bam_find_start: text must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const bool bad = lo < 0 || hi < lo || end < hi || end >= 0x7fffffffLL;
+    hipLaunchKernelGGL(rd_bam_find_init_kernel, dim3(1), dim3(1), 0, st, (unsigned long long *)info, bad ? 1 : 0);
+    if (!bad && hi > lo) {
+        const int64_t grid = (hi - lo + BAM_FIND_CAND - 1) / BAM_FIND_CAND;      // (< 2^19)
+        hipLaunchKernelGGL(rd_bam_find_kernel, dim3((unsigned)grid), dim3(BAM_FIND_THREADS), 0, st, text, lo, hi, end, (int)at_eof, (unsigned long long *)info);
+    }
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+size_t rd_bam_count_workspace_bytes(int64_t text_end) {
+    if (text_end < 0 || text_end >= 0x7fffffffLL) return 0;
+    return bam_count_ws(nullptr, text_end).total;
+}
+
+int rd_bam_count(uint8_t *text, int64_t pad, int64_t end, const uint8_t *prev_text, const rd_fq_summary *prev, int32_t final, rd_fq_summary *summary, void *workspace,
+                 size_t workspace_bytes, void *stream) {
+    if (const int rc = fq_index_check("rd_bam_count", text, pad, end, prev_text, prev, (const int32_t *)text, 0, summary, workspace, false, false, nullptr)) return rc;
+    const BamCountWs p = bam_count_ws(workspace, end);
+    if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "rd_bam_count: workspace too small: %zu < %zu", workspace_bytes, p.total);
+    hipStream_t st = (hipStream_t)stream;
+    FqSummary *sum = (FqSummary *)summary;
+    hipLaunchKernelGGL(rd_fq_begin_kernel<false>, dim3(1), dim3(FQ_THREADS), 0, st, text, pad, end, prev_text, (const FqSummary *)prev, (int)final, sum);
+    hipLaunchKernelGGL(rd_bam_walk_kernel<false>, dim3(p.nseg), dim3(64), 0, st, text, sum, p.seg, (int2 *)nullptr);
+    hipLaunchKernelGGL(rd_bam_stitch_kernel<false>, dim3(1), dim3(64), 0, st, text, sum, p.seg, (int2 *)nullptr, p.nseg, (int32_t *)nullptr, (int64_t *)nullptr,
+                       (int32_t *)nullptr, (BamScratch *)nullptr, (int)final, (int64_t)0, (int64_t)0, (int64_t *)nullptr);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
 }
 
 // ---- the delivered BAM records as they stand in the input (rd_bam_raw.hpp): the source offsets rd_bam_index left in its workspace

@@ -484,13 +484,16 @@ class DeviceFeeder:
     PLAIN_FIRST = 12 << 20
     SLOTS = 2
 
-    def __init__(self, path, device, compressed, span=None, byte_range=None, fasta=False, keep_empty_tail=False, bam=False, keep_raw=False):
+    def __init__(self, path, device, compressed, span=None, byte_range=None, fasta=False, keep_empty_tail=False, bam=False, keep_raw=False, bam_header=True):
         """compressed: the file is BGZF (span = (first file byte, one past the last, text bytes to drop in front, text bytes to
         deliver) for a rank's share, fastx_parser.BgzfView.file_span); else plain text (byte_range = (start, end), record-aligned).
         bam: the inflated bytes are a BAM file's - its header is dropped, its records are framed by BamIndexer (keep_raw: which also keeps
-        the records as they stand in the input, for BAM outputs)"""
+        the records as they stand in the input, for BAM outputs); bam_header=False: the span is a share that starts behind the header, at
+        a record start (--bam_shard: the rank whose share starts at 0 drops the header). A share's end is a record boundary like the
+        file's end: the empty final batch that judges the last carry judges it too."""
         self.path, self.device, self.compressed, self.span, self.byte_range = str(path), torch.device(device), compressed, span, byte_range
         self.fasta, self.keep_empty_tail, self.bam, self.keep_raw = bool(fasta), bool(keep_empty_tail), bool(bam), bool(keep_raw)
+        self.bam_header = bool(bam_header)
         self._skip = 0                 # BAM: inflated bytes of the header still to drop in front of the next batch
         self._stop = False
         self.out = queue.Queue(maxsize=self.SLOTS)
@@ -578,7 +581,7 @@ class DeviceFeeder:
             return
         self._ready.set()
         try:
-            if self.bam:                 # (bad magic, a header the file ends in: raised here, in front of the first batch)
+            if self.bam and self.bam_header:      # (bad magic, a header the file ends in: raised here, in front of the first batch)
                 from .. import bam
                 self._skip = bam.header_bytes(self.path)
             if self.compressed == "stream":
@@ -898,11 +901,27 @@ class DeviceFeeder:
                     break
 
 
-def get_seq_chunks_device(seq_file, chunk_size=1048576, byte_range=None, first_chunk=None, schedule=None, device=None, stats=None, keep_raw=False):
+def _share_error(err, status, share, path, rank):
+    """the error a rank's share of a BAM file ends with (--bam_shard), from the one the framing gave: share = (start, end, size of the
+    inflated stream)"""
+    from .. import bam
+    a, b, size = share
+    whose = "" if rank is None else " of rank %d" % rank
+    if status == N.BAM_TRUNCATED and b < size:
+        return ValueError(bam.NOT_A_BOUNDARY % (b, path, bam.CONFIRM) + ("" if rank is None else " (the share of rank %d would start there)" % (rank + 1)))
+    if status == N.BAM_RECORD:
+        return ValueError("%s of the share%s that starts at inflated offset %d of %s" % (err, whose, a, path))
+    return err
+
+
+def get_seq_chunks_device(seq_file, chunk_size=1048576, byte_range=None, first_chunk=None, schedule=None, device=None, stats=None, keep_raw=False, rank=None):
     """fastx_parser.get_seq_chunks for FASTQ whose text stays on the device: DeviceChunk objects of exactly the scheduled number of
     records (fewer only at the end of the stream). byte_range: (start, end) of a plain file or a fastx_parser.BgzfRange. A damaged
     stream delivers the chunks before the damage, then raises ValueError like the host reader. keep_raw (BAM input only): every chunk
-    also carries its records as they stand in the input, chunk.raw = (bytes, raw_start) - what a BAM output is selected from."""
+    also carries its records as they stand in the input, chunk.raw = (bytes, raw_start) - what a BAM output is selected from.
+    BAM with a BgzfRange (--bam_shard; rank: whose share it is, for the messages): the share starts at a record start that a search found
+    (data_loader/bam_shard.py). A share whose chain of records does not land exactly on its end, in front of the file's end, ends in
+    bam.NOT_A_BOUNDARY - the next rank's start is no record start -, and "malformed BAM record N" names the share N counts in."""
     from . import fastx_parser as fx
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     torch.cuda.set_device(device)
@@ -911,7 +930,7 @@ def get_seq_chunks_device(seq_file, chunk_size=1048576, byte_range=None, first_c
         raise ValueError("keep_raw: %s is not a BAM file" % seq_file)
     kind = device_ingest_kind(seq_file)
     compressed = "stream" if kind == "stream" else (fmt.endswith("gz") or fmt == "bam")
-    span = None
+    span, share = None, None
     keep_tail = False            # a share that ends before the file does (FASTA: its last record counts even without a sequence)
     from . import gz_shard
     resident = byte_range if isinstance(byte_range, gz_shard.ResidentRange) else None
@@ -921,6 +940,8 @@ def get_seq_chunks_device(seq_file, chunk_size=1048576, byte_range=None, first_c
         a, b = byte_range
         c0, c1, drop = byte_range.view.file_span(a, b)
         keep_tail = b < byte_range.view.size
+        if fmt == "bam":
+            share = (int(a), int(b), int(byte_range.view.size))
         span, byte_range = (c0, c1, drop, b - a), None
     elif byte_range is not None:
         keep_tail = int(byte_range[1]) < os.path.getsize(seq_file)
@@ -928,7 +949,7 @@ def get_seq_chunks_device(seq_file, chunk_size=1048576, byte_range=None, first_c
         feeder = gz_shard.ResidentFeeder(resident)
     else:
         feeder = DeviceFeeder(seq_file, device, compressed, span=span, byte_range=byte_range, fasta=fmt.startswith("fa"), keep_empty_tail=keep_tail, bam=fmt == "bam",
-                              keep_raw=keep_raw)
+                              keep_raw=keep_raw, bam_header=share is None or share[0] == 0)
     skip_left = resident.skip if resident is not None else 0      # (mate files: the records in front of the ranks' common cut went to the rank before)
     want = chunk_size if not first_chunk else max(1, min(int(first_chunk), chunk_size))
     sched = list(schedule) if schedule else None
@@ -968,6 +989,8 @@ def get_seq_chunks_device(seq_file, chunk_size=1048576, byte_range=None, first_c
                 good = b.n
                 if b.status:             # a malformed record: the chunks in front of it are delivered, then the error
                     (err, good), eof, framing = feeder.ix.damage(b), True, True
+                    if share is not None:
+                        err = _share_error(err, b.status, share, seq_file, rank)
                 drop = min(skip_left, good)
                 skip_left -= drop
                 if good > drop:

@@ -32,7 +32,9 @@ as intervals in the read's bases, one text line each (regions.py has the rule; r
 lines on the post stream where the windows' final logits are). The lines travel like the per-read report's, as pieces of one more file.
 BAM input (an extension): -i x.bam / x.ubam, in all three layouts of the inputs (one file, two files, --interleaved). The file's BGZF
 members are inflated on the GPU and rd_bam_index (csrc/rd_bam_index.hpp; bam.py has the rule) frames the records and re-writes them as
-FASTQ text, so the chunks are FASTQ chunks and the outputs FASTQ files. One rank, device ingest only (check_bam).
+FASTQ text, so the chunks are FASTQ chunks and the outputs FASTQ files. Device ingest only; one rank (check_bam), or - --bam_shard - the
+sharded parse of the file's BGZF members: every rank frames its own share, which begins at a record start found by a search on the GPU
+(data_loader/bam_shard.py; a cut that is no record start ends the run before any output is joined).
 --bam_output (an extension, BAM input): the chunks also carry their records as they stand in the input (DeviceChunk.raw: rd_bam_raw_tab /
 rd_bam_raw_gather, csrc/rd_bam_raw.hpp), and the output kernels select from THAT view (_select_chunk): every output is a BAM file - the
 header of its input, the selected records byte for byte, BGZF members. Classification, report, summary and regions see the FASTQ view.
@@ -85,9 +87,13 @@ class colors:
 
 def part_path(path, rank):
     """name of rank `rank`'s part of an output file; keeps a trailing 'gz' because the writer compresses by name
-    (reference detect.py:738: read_file.endswith('gz'))"""
+    (reference detect.py:738: read_file.endswith('gz')) - and a trailing '.bam' / '.ubam' (--bam_output under --bam_shard), by which
+    the writer makes BGZF blocks"""
     if path.endswith('gz'):
         return '%s.part%d.gz' % (path[:-2].rstrip('.'), rank)
+    for ext in ('.bam', '.ubam'):
+        if path.endswith(ext):
+            return '%s.part%d%s' % (path[:-len(ext)], rank, ext)
     return '%s.part%d' % (path, rank)
 
 
@@ -239,6 +245,7 @@ class Predictor:
         self.mate_check = not getattr(args, 'no_mate_check', False)
         self.bam_output = bool(getattr(args, 'bam_output', False))       # BAM outputs: the selected records as they stand in the input
         self.read_groups = bool(getattr(args, 'read_groups', False))     # --summary gains the counters per BAM read group
+        self.bam_shard = bool(getattr(args, 'bam_shard', False))         # BAM input under several ranks: the sharded parse (data_loader/bam_shard.py)
         self._groups = None                      # ... groups.DeviceGroups (run_with_chunks)
         self._pairs = None                       # --interleaved: gz.DevicePairSplit (run_with_chunks)
         self._summary = None                     # --summary: summary.DeviceSummary (run_with_chunks)
@@ -749,7 +756,8 @@ class Predictor:
                 if arena is None and self._device_parse(path):
                     st = self.ingest.setdefault(os.path.basename(str(path)), {"path": "device"})
                     stream = dr.get_seq_chunks_device(path, chunk_size=chunk_reads, byte_range=byte_range, first_chunk=first, schedule=schedule,
-                                                      device=self.device, stats=st, keep_raw=self.bam_output or self.read_groups)
+                                                      device=self.device, stats=st, keep_raw=self.bam_output or self.read_groups,
+                                                      rank=self.rank if self.sharded_parse else None)
                 # one plain input file: its parser thread was the slowest stage of the pipeline - two readers over byte segments,
                 # small first chunks (mate files keep one reader each and exact chunk sizes: their chunks must pair up)
                 # (not an interleaved file: its chunks must hold whole pairs)
@@ -970,11 +978,15 @@ class Predictor:
             if self.is_paired and self.args.ensure == 'both':
                 self.logger.info('Discarded {}{}{}{} unclassified sequences'.format(
                     colors.BOLD, colors.OKCYAN, self.num_unknown, colors.ENDC))
-        for path in self.input:                    # (BAM input is one rank's: check_bam)
-            if fx.get_seq_format(path) == "bam":
-                ix = (self.ingest.get(os.path.basename(str(path))) or {}).get("indexer") or {}
-                self.logger.info('BAM input: {} records, {} secondary/supplementary skipped ({})'.format(
-                    ix.get("bam_records", 0), ix.get("bam_skipped", 0), path))
+        bam_in = [path for path in self.input if fx.get_seq_format(path) == "bam"]
+        if bam_in:                                 # (one rank, or --bam_shard: every rank walked the records of its share)
+            mine = [[((self.ingest.get(os.path.basename(str(path))) or {}).get("indexer") or {}).get(k, 0) for k in ("bam_records", "bam_skipped")]
+                    for path in bam_in]
+            per_rank = self._all_gather(mine) if self.sharded_parse else [mine]
+            for f, path in enumerate(bam_in):
+                if self.rank == 0:
+                    self.logger.info('BAM input: {} records, {} secondary/supplementary skipped ({})'.format(
+                        sum(r[f][0] for r in per_rank), sum(r[f][1] for r in per_rank), path))
         if self.interleaved:
             fx.check_even_records(self._records_seen)
         if self._windows is not None:              # every rank classified the windows of its own shard / byte range
@@ -999,10 +1011,13 @@ class Predictor:
         """--summary, at the end of a run that went well (every output file is closed): the ranks' counters summed, checked against
         the run's own counts and written by rank 0 as JSON"""
         acc = self._summary.acc
+        gacc = None if self._groups is None else self._groups.acc      # (BAM input: one rank, or --bam_shard - the groups of a rank's share)
         if self.multi:                             # every rank counted its own shard / byte range
             acc = rdist.reduce_counts(acc)
+            gacc = None if gacc is None else rdist.reduce_counts(gacc)
         if self.rank != 0:
             return
+        gacc = None if gacc is None else gacc.cpu().numpy()
         acc = acc.cpu().numpy()
         units = [int(x) for x in _summod.sections(acc)["units"]]
         if units != [self.num_unknown, self.num_nonrrna, self.num_rrna]:
@@ -1015,8 +1030,8 @@ class Predictor:
                                         self._windows, stride=int(self._windows["stride"] or self.len), classified=list(self._win_total),
                                         **({"regions": list(self._reg_total[0]), "reads_with_regions": list(self._reg_total[1])}
                                            if self._regions else {}))})
-        if self._groups is not None:               # (BAM input: one rank)
-            gacc, grp = self._groups.result(), self._groups
+        if self._groups is not None:
+            grp = self._groups
             got = _grpmod.units_per_class(gacc, grp.G)
             if got != units:
                 raise RuntimeError("--read_groups: the rows of the read groups hold {} unclassified / non-rRNA / rRNA units, the run {}".format(got, units))
@@ -1056,6 +1071,10 @@ class Predictor:
         # and writes the members of its share (positions in the decompressed stream, fx.BgzfView). RD_BGZF_SHARD=0: one decoding rank
         bgzf = (self.multi and not plain and os.environ.get("RD_BGZF_SHARD", "1") != "0"
                 and all(fx.get_seq_format(p) in ("fqgz", "fagz") and fx.bgzf_all_the_way(p) and fx.device_inflate_wanted(p) for p in self.input))
+        # ... and BAM inputs under --bam_shard (check_bam: every input is BAM, RD_BGZF_SHARD is not 0): the same layout, with views that
+        # find the record starts of a length-prefixed chain by a search on the GPU (data_loader/bam_shard.py)
+        bam_in = self.multi and self.bam_shard and all(fx.get_seq_format(p) == "bam" for p in self.input)
+        bgzf = bgzf or bam_in
         views = None
         if bgzf:                    # the member index: rank 0 walks the headers, the others receive the three arrays per file
             idx = [None]
@@ -1066,9 +1085,14 @@ class Predictor:
                     idx = [str(e)]
             dist.broadcast_object_list(idx, src=0)
             if isinstance(idx[0], str):
+                if bam_in:                  # (no one-decoder path for BAM under several ranks: raised by every rank, from the same index)
+                    raise RuntimeError("--bam_shard: {}: the file is not BGZF all the way - run on one rank".format(idx[0]))
                 if self.rank == 0:
                     self.logger.info('{}: one rank decodes'.format(idx[0]))
                 bgzf = False
+            elif bam_in:
+                from .data_loader import bam_shard
+                views = [bam_shard.BamView(p, index=i, device=self.device) for p, i in zip(self.input, idx[0])]
             else:
                 views = [fx.BgzfView(p, index=i) for p, i in zip(self.input, idx[0])]
         # ... and single-stream .gz inputs (what sequencers write; round 6): every rank decodes its own compressed range on its own GPU -
@@ -1115,7 +1139,8 @@ class Predictor:
                 files.append(((e, label), path, fx.open_for_write(self._part_files[-1] if self.sharded_parse else path)))
                 if self.sharded_parse:         # parts are joined later: the joined file gets ONE BGZF end-of-file block, at its end
                     files[-1][2].set_eof_marker(False)
-                if self.bam_output and label in (0, 1, -1):      # a BAM output starts with the header of its mate's input, byte for byte
+                # a BAM output starts with the header of its mate's input, byte for byte (the sharded parse: rank 0's part comes first)
+                if self.bam_output and label in (0, 1, -1) and (self.rank == 0 or not self.sharded_parse):
                     src = self.input[e if len(self.input) == 2 else 0]
                     if src not in headers:
                         headers[src] = np.frombuffer(_bammod.header(src), dtype=np.uint8)
@@ -1202,7 +1227,8 @@ class Predictor:
         tmps = [path + '.joining' for path in finals]
         self._part_files += tmps if self.rank == 0 else []
         # .gz files whose members were made on the device are BGZF: one end-of-file block (an empty member) behind the last part
-        tails = [_gzmod.eof_block() if (self.gzip_on_device and path.endswith('gz')) else b'' for path in finals]
+        tails = [_gzmod.eof_block() if ((self.gzip_on_device and path.endswith('gz')) or (self.bam_output and path.endswith(('.bam', '.ubam'))))
+                 else b'' for path in finals]
         if self.rank == 0:
             for f, tmp in enumerate(tmps):
                 with open(tmp, 'wb') as fh:
@@ -1259,7 +1285,7 @@ class Predictor:
                           self.args.ensure, self.bam_output)
         check_summary(getattr(self.args, 'summary', None), self.output, self.rrna, self.is_paired, self.args.ensure,
                       getattr(self.args, 'read_report', None), self.bam_output)
-        check_read_groups(self.read_groups, getattr(self.args, 'summary', None), self.input)
+        check_read_groups(self.read_groups, getattr(self.args, 'summary', None), self.input, self.bam_shard)
         self._windows = check_windows(self.args)
         check_regions(getattr(self.args, 'regions', None), self._windows is not None, self.output, self.rrna, self.is_paired, self.args.ensure,
                       getattr(self.args, 'read_report', None), getattr(self.args, 'summary', None), self.bam_output)
@@ -1324,11 +1350,13 @@ def unclassified_path(out, bam_output=False):
     return out + ('.unclassified.bam' if bam_output else '.unclassified.gz')
 
 
-def check_bam(inputs, output, rrna, bam_output=False):
+def check_bam(inputs, output, rrna, bam_output=False, bam_shard=False, interleaved=False):
     """BAM input (.bam / .ubam, ribodetector_amd/bam.py): the rules that hold before anything touches a device; returns whether the
     inputs are BAM. The records become FASTQ text on the device, so the outputs are FASTQ files; there is no host reader for BAM,
     so the switches and layouts that need one are refused. bam_output (--bam_output): every input is BAM and every -o / -r name ends
-    with .bam / .ubam - the selected records are written as they stand in the input (all outputs are BAM or none is)."""
+    with .bam / .ubam - the selected records are written as they stand in the input (all outputs are BAM or none is). bam_shard
+    (--bam_shard): BAM input under several ranks, each one with its own share of the records (data_loader/bam_shard.py) - the sharded
+    parse of BGZF members, so not with RD_BGZF_SHARD=0, and not an interleaved file (no byte range of one holds whole pairs by itself)."""
     def fmt(path):
         try:
             return fx.get_seq_format(path)
@@ -1349,6 +1377,9 @@ def check_bam(inputs, output, rrna, bam_output=False):
             raise RuntimeError("BAM output is not supported: {} (-o / -r take FASTQ names, plain or .gz; checked before anything touches a "
                                "device)".format(o))
     if "bam" not in kinds:
+        if bam_shard:
+            raise RuntimeError("--bam_shard shares BAM input between the ranks: every -i file must end with .bam or .ubam, got {} (checked "
+                               "before anything touches a device)".format(", ".join(str(p) for p in inputs or [])))
         return False
     if any(k != "bam" for k in kinds):
         raise RuntimeError("BAM input cannot be mixed with FASTQ / FASTA input files: {} (checked before anything touches a "
@@ -1361,9 +1392,16 @@ def check_bam(inputs, output, rrna, bam_output=False):
         if fx.ingest_env(name, "1") == "0":
             raise RuntimeError("BAM input is framed and inflated on the device only: it cannot run with {}=0 or RD_INGEST=host (checked "
                                "before anything touches a device)".format(name))
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise RuntimeError("BAM input runs on one rank: the multi-rank layouts use the host reader, which has no BAM support (checked "
-                           "before anything touches a device)")
+    multi = int(os.environ.get("WORLD_SIZE", "1")) > 1
+    if bam_shard and os.environ.get("RD_BGZF_SHARD", "1") == "0":
+        raise RuntimeError("--bam_shard is the sharded parse of BGZF members: it cannot run with RD_BGZF_SHARD=0 (checked before anything "
+                           "touches a device)")
+    if bam_shard and interleaved and multi:
+        raise RuntimeError("--bam_shard: an interleaved BAM is not shared by byte ranges: run on one rank (checked before anything touches "
+                           "a device)")
+    if multi and not bam_shard:
+        raise RuntimeError("BAM input runs on one rank: the multi-rank layouts use the host reader, which has no BAM support (or give "
+                           "--bam_shard; checked before anything touches a device)")
     return True
 
 
@@ -1397,7 +1435,7 @@ def check_summary(path, output, rrna, is_paired, ensure, read_report=None, bam_o
             raise RuntimeError("--summary {} is also {}".format(path, what))
 
 
-def check_read_groups(read_groups, summary, inputs):
+def check_read_groups(read_groups, summary, inputs, bam_shard=False):
     """--read_groups: the rules that hold before anything touches a device; returns the declared groups of mate 1's BAM
     (bam.read_groups: [(id, fields)], header order), or None without the flag. The flag adds an object to the --summary file, so it
     needs one; the groups are those of BAM records and of a BAM header, so every input is BAM; the @RG lines of the header must be a
@@ -1416,8 +1454,8 @@ def check_read_groups(read_groups, summary, inputs):
     if not inputs or any(fmt(p) != "bam" for p in inputs):
         raise RuntimeError("--read_groups counts the reads per RG tag of BAM records: every -i file must end with .bam or .ubam, got {} "
                            "(checked before anything touches a device)".format(", ".join(str(p) for p in inputs or [])))
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise RuntimeError("--read_groups runs on one rank (checked before anything touches a device)")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not bam_shard:       # (--bam_shard: every rank counts its share, the rows are summed)
+        raise RuntimeError("--read_groups runs on one rank (or give --bam_shard; checked before anything touches a device)")
     try:
         header = _bammod.header(inputs[0])
     except (OSError, ValueError) as e:
@@ -1538,6 +1576,11 @@ none: give label based on the mean probability of read pair.
                            'mate 1\'s group), and for the records without RG, with an RG that no @RG line declares, and with malformed\n'
                            'tags. Counted on the GPU over the records as they stand in the input, which the run then keeps in GPU\n'
                            'memory next to the FASTQ text (about 0.75 of its bytes more).')
+    args.add_argument('--bam_shard', action='store_true',
+                      help='(extension) BAM input under several ranks (torch.distributed.run): every rank inflates, frames, classifies and\n'
+                           'writes its own share of the records, like the ranks of a BGZF FASTQ run. The shares begin at record starts\n'
+                           'found by a search on the GPU (8 records in a row that look like records); a cut that is none ends the run\n'
+                           'with an error before any output is joined - run such a file on one rank. One rank: changes nothing.')
     args.add_argument('--no_mate_check', action='store_true', help='(extension) with --interleaved: do not compare the ids of the mates')
     args.add_argument('-v', '--version', action='version', version='%(prog)s {version}'.format(version=__version__))
     return args
@@ -1549,8 +1592,9 @@ def main(argv=None, log_level=None):
     config = ConfigParser.from_json(config_file)
     check_windows(args)                          # (before the model is loaded: nothing has touched a device yet)
     check_regions(getattr(args, 'regions', None), getattr(args, 'windows', False))
-    check_bam(args.input, args.output, args.rrna, getattr(args, 'bam_output', False))
-    check_read_groups(getattr(args, 'read_groups', False), getattr(args, 'summary', None), args.input)
+    check_bam(args.input, args.output, args.rrna, getattr(args, 'bam_output', False), getattr(args, 'bam_shard', False),
+              getattr(args, 'interleaved', False))
+    check_read_groups(getattr(args, 'read_groups', False), getattr(args, 'summary', None), args.input, getattr(args, 'bam_shard', False))
     seq_pred = Predictor(config, args, log_level=log_level)
     try:
         t0 = time.perf_counter()

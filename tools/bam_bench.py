@@ -13,6 +13,10 @@ timed calls of each, ALTERNATING the legs (model load excluded: Predictor.timing
   --bam_output   the same three measurements for BAM OUTPUT (detect.py --bam_output, csrc/rd_bam_raw.hpp): short / long time x.bam -> .bam
           --bam_output against x.bam -> .fq.gz - the same input file, the existing path is the yardstick; kernel times rd_bam_raw_tab +
           rd_bam_raw_gather (every record of the batch, one piece) behind one rd_bam_index call on the resident batch.
+  --shard        the measurements of --bam_shard (data_loader/bam_shard.py, csrc/rd_bam_shard.hpp): kernel times rd_bam_find_start on a 1 MiB
+          probe of either shape, and rd_bam_count against rd_bam_index - the yardstick, timed in the same process - on the same resident
+          batch; short times fastx_parser.plan_ranges over BamViews for two ranks that share the GPU (threads of this process: host-side
+          evidence only), one file and two files, and the one-rank CLI with and without --bam_shard, the legs alternating.
 Every fourth record of the BAM files is stored on the reverse strand (flag 0x10, bases reverse-complemented, qualities reversed), so
 that the text the two legs see is the same. The inputs are written by processes that never touch the GPU."""
 import argparse
@@ -239,6 +243,126 @@ def bench_kernel(calls, batch_bytes=128 << 20, raw_view=False):
                           "records_per_s": round(n / (med * 1e-6)), "kernel_split": "not measured here (see --trace)"}), flush=True)
 
 
+def _events(fn, calls, warm=3):
+    """sorted us per call of fn(), by device events"""
+    import torch
+    for _ in range(warm):
+        fn()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(calls + 1)]
+    ev[0].record()
+    for k in range(calls):
+        fn()
+        ev[k + 1].record()
+    torch.cuda.synchronize()
+    return sorted(ev[k].elapsed_time(ev[k + 1]) * 1e3 for k in range(calls))
+
+
+def _us(v):
+    return {"median": round(statistics.median(v), 1), "lowest": round(v[0], 1), "highest": round(v[-1], 1)}
+
+
+def bench_shard_kernels(calls, batch_bytes=128 << 20, probe=1 << 20):
+    """--shard: rd_bam_find_start on a 1 MiB probe, and rd_bam_count against rd_bam_index (the yardstick, in this process) on the same
+    resident batch, for both shapes"""
+    import numpy as np
+    import torch
+    from ribodetector_amd import _native as N
+    from ribodetector_amd import bam
+    lib, dev = N.lib(), torch.device("cuda:0")
+    st = N.stream_ptr(dev)
+    for shape, length in SHAPES.items():
+        size = 36 + NAME + length // 2 + length
+        n = batch_bytes // size
+        step = max(1, (64 << 20) // (2 * length))
+        raw = b"".join(_rows(min(step, n - f), f, length, seed=7 + f // step)[1].tobytes() for f in range(0, n, step))
+        pad, end = 64, 64 + len(raw)
+        text = torch.zeros(((end + 64 + 127) // 64) * 64, dtype=torch.uint8, device=dev)
+        text[pad:end] = torch.from_numpy(np.frombuffer(raw, np.uint8).copy()).to(dev)
+        # the probe: [0, 1 MiB) of the batch's bytes, asked from offset 1 (inside the first record), the window goes on behind it
+        win = text[pad:pad + probe + 64].clone()
+        info = torch.zeros(4, dtype=torch.int64, device=dev)
+        us = _events(lambda: N.check(lib.rd_bam_find_start(N.ptr(win), 1, probe, probe, 0, N.ptr(info), st), "rd_bam_find_start"), calls)
+        got = [int(x) for x in info.cpu()]
+        want = bam.find_record_start(raw[:probe], 1, probe, False)
+        assert (got[0], got[1]) == want and got[0] == size, (got, want, size)
+        print(json.dumps({"measurement": "shard_find_start", "shape": shape, "read_len": length, "probe_bytes": probe, "calls": calls, "found": got[0],
+                          "undecided": got[1], "us_per_call": _us(us), "GB_per_s": round(probe / statistics.median(us) / 1e3, 1)}), flush=True)
+        window = end - pad
+        cap_rec, norm_cap = window // 37 + 2, ((4 * window // 3 + 64 + 255) // 256) * 256
+        norm = torch.empty(norm_cap, dtype=torch.uint8, device=dev)
+        rec_tab, hdr_tab = torch.empty(cap_rec, dtype=torch.int64, device=dev), torch.empty(cap_rec, dtype=torch.int32, device=dev)
+        s_i, s_c = torch.zeros(8, dtype=torch.int64, device=dev), torch.zeros(8, dtype=torch.int64, device=dev)
+        ws_i = torch.empty(int(lib.rd_bam_index_workspace_bytes(end)), dtype=torch.uint8, device=dev)
+        ws_c = torch.empty(max(int(lib.rd_bam_count_workspace_bytes(end)), 256), dtype=torch.uint8, device=dev)
+
+        def index():
+            N.check(lib.rd_bam_index(N.ptr(text), pad, end, None, None, 1, N.ptr(norm), norm_cap, N.ptr(rec_tab), N.ptr(hdr_tab), cap_rec, N.ptr(s_i),
+                                     N.ptr(ws_i), ws_i.numel(), st), "rd_bam_index")
+
+        def count():
+            N.check(lib.rd_bam_count(N.ptr(text), pad, end, None, None, 1, N.ptr(s_c), N.ptr(ws_c), ws_c.numel(), st), "rd_bam_count")
+        ui, uc = _events(index, calls), _events(count, calls)
+        ui2 = _events(index, calls)                                  # (the yardstick once more behind the count: its own run-to-run spread)
+        a, b = s_i.cpu().numpy(), s_c.cpu().numpy()
+        assert (a == b).all() and int(b[3]) == n and int(b[6]) == 0, (a, b)
+        print(json.dumps({"measurement": "shard_count", "shape": shape, "read_len": length, "records": n, "window_bytes": window, "calls": calls,
+                          "rd_bam_index_us": _us(ui), "rd_bam_index_again_us": _us(ui2), "rd_bam_count_us": _us(uc),
+                          "count_over_index": round(statistics.median(uc) / statistics.median(ui), 4),
+                          "workspace_bytes": {"index": ws_i.numel(), "count": ws_c.numel()}, "summaries_equal": True}), flush=True)
+
+
+def bench_shard_plan(d, reads, world=2):
+    """--shard: the seconds fastx_parser.plan_ranges takes with BamView on the device for `world` ranks that share the one GPU - here
+    threads of this process with an in-process all_gather, so HOST-SIDE EVIDENCE ONLY: no launcher, no process group, one GPU.
+    One file, and the two-file case (the same file as both mates: every cut is verified by count_records)"""
+    import threading
+    import time
+    import torch
+    from ribodetector_amd.data_loader import bam_shard
+    from ribodetector_amd.data_loader import fastx_parser as fx
+    src = os.path.join(d, "short_%d.bam" % reads)
+    t0 = time.perf_counter()
+    index = fx.BgzfView.build_index(src)
+    t_index = time.perf_counter() - t0
+    for paths in ([src], [src, src]):
+        res, slots, bar, secs = [None] * world, [None] * world, threading.Barrier(world), [0.0] * world
+
+        def work(r):
+            torch.cuda.set_device(0)
+
+            def ag(obj):
+                slots[r] = obj
+                bar.wait()
+                out = list(slots)
+                bar.wait()
+                return out
+            views = [bam_shard.BamView(p, index=index, device=torch.device("cuda:0")) for p in paths]
+            t = time.perf_counter()
+            res[r] = [tuple(x) for x in fx.plan_ranges(paths, r, world, ag, views=views)]
+            secs[r] = time.perf_counter() - t
+            res[r].append([v.stats for v in views])
+        th = [threading.Thread(target=work, args=(r,)) for r in range(world)]
+        [t.start() for t in th]
+        [t.join() for t in th]
+        print(json.dumps({"measurement": "shard_plan_ranges", "evidence": "host-side only: %d threads of one process share one GPU" % world, "files": len(paths),
+                          "reads": reads, "world": world, "member_index_s": round(t_index, 3), "plan_ranges_s_per_rank": [round(s, 3) for s in secs],
+                          "ranges": [r[:-1] for r in res], "view_stats_rank0": res[0][-1]}), flush=True)
+
+
+def bench_shard_cli(d, reads, calls):
+    """--shard: the one-rank CLI with and without --bam_shard on the same file, the legs alternating: nothing is added on one rank"""
+    src = os.path.join(d, "short_%d.bam" % reads)
+    argv = {"without": ["-l", "100", "-i", src, "-o", os.path.join(d, "o_without.fq.gz")],
+            "with_bam_shard": ["-l", "100", "-i", src, "-o", os.path.join(d, "o_with.fq.gz"), "--bam_shard"]}
+    rate, last = timed_legs(argv, calls, reads)
+    med = {k: statistics.median(v) for k, v in rate.items()}
+    same = open(argv["without"][5], "rb").read() == open(argv["with_bam_shard"][5], "rb").read()
+    print(json.dumps({"measurement": "shard_one_rank_cli", "reads": reads, "read_len": 100, "calls": calls, "flow": "single-end x.bam -> .fq.gz, one rank",
+                      "reads_per_s": {k: _mlh(v) for k, v in rate.items()}, "ratio_of_medians": round(med["with_bam_shard"] / med["without"], 4),
+                      "with_flag_median_inside_no_flag_spread": bool(rate["without"][0] <= med["with_bam_shard"] <= rate["without"][-1]),
+                      "outputs_byte_identical": bool(same)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=1 << 22, help="reads of the short leg")
@@ -248,6 +372,7 @@ def main():
     ap.add_argument("--only", default=None, choices=["short", "long", "kernel"])
     ap.add_argument("--trace", default=None)
     ap.add_argument("--bam_output", action="store_true", help="the measurements of BAM output instead")
+    ap.add_argument("--shard", action="store_true", help="the measurements of --bam_shard instead")
     a = ap.parse_args()
     if a.trace:
         t, total = trace_times(a.trace)
@@ -255,13 +380,22 @@ def main():
                                                                                "largest": round(max(v), 1)} for k, v in sorted(t.items())}}))
         return
     which = [a.only] if a.only else ["short", "long", "kernel"]
-    jobs = [(s, n, a.bam_output) for s, n in (("short", a.reads), ("long", a.long_reads)) if s in which]
+    if a.shard:                                  # (the 100 bp file only: the probes and the batch of the 10 kb shape are made in memory)
+        which = [w for w in which if w != "long"]
+    jobs = [(s, n, a.bam_output or a.shard) for s, n in (("short", a.reads), ("long", a.long_reads)) if s in which]
     d = a.keep or tempfile.mkdtemp(prefix="rdbam", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
     os.makedirs(d, exist_ok=True)
     try:
         if jobs:
             make_inputs(d, jobs)                 # (before anything initialises the GPU)
         import ribodetector_amd  # noqa: F401
+        if a.shard:
+            if "kernel" in which:
+                bench_shard_kernels(20)
+            for s, n, _ in jobs:
+                bench_shard_plan(d, n)
+                bench_shard_cli(d, n, a.calls)
+            return
         for s, n, _ in jobs:
             (bench_cli_bam_output if a.bam_output else bench_cli)(d, s, n, a.calls)
         if "kernel" in which:
