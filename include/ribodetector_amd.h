@@ -488,6 +488,29 @@ RD_API int rd_bam_group_accumulate(const uint8_t *raw_a, const int64_t *raw_star
                                    const uint8_t *raw_b, const int64_t *raw_start_b, const int32_t *rows_b, int64_t first_b, int64_t stride_b,
                                    const int8_t *labels, int64_t n, int32_t G, int64_t *acc, int64_t *info, void *stream);
 
+/* The listed tags of raw BAM records as text behind the read names of the records' FASTQ text (the CLI's --bam_tags, an extension).
+ * The rule is ribodetector_amd/bam.py (tag_comment, fastq_text_tagged). text / rec_start: the FASTQ view of n_rec records (record k is
+ * text[rec_start[k] .. rec_start[k + 1]), '@name\n...'); raw / raw_start: the raw view of the SAME records. tags [host]: n_tags names
+ * of 2 bytes each ([A-Za-z][A-Za-z0-9], no name twice, 1 <= n_tags <= RD_BAM_TAGS_MAX). Record k of the tagged text is '@name', then
+ * '\tTG:T:text' for every listed tag, in list order, that rd_bam_tag_find finds in raw record k, then the rest of the record from its
+ * first '\n' on. A: TG:A:c; c C s S i I: TG:i:decimal; Z H: the bytes verbatim; B with an integer subtype s: TG:B:s and ',v' per
+ * element. Values of type f and B:f are left out and counted. A record gets NO comment and is counted as malformed when a listed tag's
+ * walk is malformed, an A / Z / H value holds a byte outside 0x20..0x7E, or an H value has odd length or a character that is no hex digit.
+ * out [dev, 16-byte aligned] uint8[out_cap] receives the tagged text, out_start [dev] int64[n_rec + 1] its record table. info [dev]
+ * int64[8 + RD_BAM_TAGS_MAX]: info[0] = records, info[1] = bytes of the tagged text, info[3] = fault - 1: the text needs more than
+ * out_cap bytes (info[1] says how many; nothing in out is written, the counters are valid), 2: nothing is to be trusted (a table entry
+ * outside its view, a FASTQ record that does not start with '@', a header line that runs past its record); info[4] = records with
+ * malformed tags, info[5] = float values skipped, info[8 + j] = records in which tag j was copied. The tagged text has no bound linear
+ * in text_bytes (text_bytes + 5 raw_bytes always holds it): a caller sizes out by a hint and repeats once on fault 1.
+ * workspace [dev, 256-byte aligned] of rd_bam_tag_splice_workspace_bytes(n_rec, n_tags) (0: bad arguments). Every length read from raw
+ * is checked against the record's end before the byte it points to is read (rd_bam_tag_find's contract). Asynchronous on `stream`;
+ * n_rec == 0: a no-op that zeroes info. */
+#define RD_BAM_TAGS_MAX 16
+RD_API size_t rd_bam_tag_splice_workspace_bytes(int64_t n_rec, int32_t n_tags);
+RD_API int rd_bam_tag_splice(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const uint8_t *raw, int64_t raw_bytes,
+                             const int64_t *raw_start, int64_t n_rec, const uint8_t *tags, int32_t n_tags, uint8_t *out, size_t out_cap,
+                             int64_t *out_start, int64_t *info, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Reads longer than max_len classified over WINDOWS of max_len bases (CLI extension `--windows`; the reference classifies read[:max_len],
  * reference detect.py:666-726, and that stays the rule without the flag). A window is one more (seq_off, seq_len) entry over the same
  * text, so rd_classify takes the window table as it takes a read table and its kernels do not change.

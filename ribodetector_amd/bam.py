@@ -29,6 +29,11 @@ with a NUL; B: subtype[1] (one of cCsSiIf) count:uint32 and count elements. Ever
 front of E, an unknown type, fewer than 3 bytes left in front of E: the tags are malformed. Read groups (detect.py --read_groups): the
 header text declares them ('@RG' lines, read_groups), a record names its group with RG:Z:<id>, and group_row says which row of the
 per-group counters a record is counted in.
+
+Tags in FASTQ header lines (detect.py --bam_tags; device side csrc/rd_bam_tagtext.hpp, C ABI rd_bam_tag_splice): tag_comment says what
+a record's listed tags become behind its read name - '\\tTG:T:text' per tag, SAM's text form, as `samtools fastq -T` writes it - and
+fastq_text_tagged is fastq_text with that comment in front of the first newline of every record. Float-typed values (f, B:f) are left
+out and counted; a record whose listed tags cannot be walked, or hold a byte that would break a FASTQ header line, gets no comment.
 """
 import struct
 import zlib
@@ -417,6 +422,102 @@ def find_tag(data, rec_off, tag):
             return (v, n, t)
         p = nxt
     return (TAG_NONE, 0, 0)
+
+
+# ---- tags as the comment of a FASTQ header line (detect.py --bam_tags; device side csrc/rd_bam_tagtext.hpp) ---------------------------------
+
+TAGS_MAX = N.BAM_TAGS_MAX        # RD_BAM_TAGS_MAX: the most names a tag list holds
+_TAG_INT = {ord("c"): "<b", ord("C"): "<B", ord("s"): "<h", ord("S"): "<H", ord("i"): "<i", ord("I"): "<I"}
+_HEX = frozenset(b"0123456789ABCDEFabcdef")
+
+
+def parse_tag_list(text):
+    """the names of a tag list 'MM,ML,RG' as 2-byte strings, in list order. ValueError: an empty list, a name that is not
+    [A-Za-z][A-Za-z0-9], a name that appears twice, more than TAGS_MAX names."""
+    names = [t for t in str(text).split(",")] if str(text) else []
+    if not names:
+        raise ValueError("the tag list is empty")
+    out = []
+    for t in names:
+        ok = len(t) == 2 and t.isascii() and t[0].isalpha() and t[1].isalnum()
+        if not ok:
+            raise ValueError("'%s' is not a tag name ([A-Za-z][A-Za-z0-9])" % t)
+        if t.encode() in out:
+            raise ValueError("the tag %s appears twice" % t)
+        out.append(t.encode())
+    if len(out) > TAGS_MAX:
+        raise ValueError("the list holds %d tags, more than %d" % (len(out), TAGS_MAX))
+    return out
+
+
+def tag_comment(data, rec_off, tags):
+    """(comment, copied, malformed, floats) of the record at data[rec_off:] and the listed tags (2-byte names, list order): comment =
+    the bytes that go behind the read name ('\\tTG:T:text' per tag that is present and not float-typed; b"" when there is none),
+    copied = one bool per listed tag (found and formatted), malformed = the record gets no comment because a listed tag gives
+    TAG_MALFORMED, an A / Z / H value of a listed tag holds a byte outside 0x20..0x7E, or an H value has odd length or a non-hex
+    character (copied is all False and floats 0 then), floats = the listed tags of type f or B:f, which are left out.
+    A c C s S i I: TG:A:c / TG:i:decimal; Z H: the bytes verbatim; B: TG:B:s and ',v' per element."""
+    data = bytes(data)
+    parts, copied, floats = [], [], 0
+    bad = (b"", [False] * len(tags), True, 0)
+    for tag in tags:
+        tag = bytes(tag)
+        off, n, t = find_tag(data, rec_off, tag)
+        if off == TAG_MALFORMED:
+            return bad
+        if off == TAG_NONE:
+            copied.append(False)
+            continue
+        v = data[off:off + n]
+        if t == ord("f") or (t == ord("B") and v[0] == ord("f")):
+            floats += 1
+            copied.append(False)
+            continue
+        if t in (ord("A"), ord("Z"), ord("H")):
+            if any(c < 0x20 or c > 0x7E for c in v):
+                return bad
+            if t == ord("H") and (n & 1 or any(c not in _HEX for c in v)):
+                return bad
+            text = bytes([t]) + b":" + v
+        elif t in _TAG_INT:
+            text = b"i:" + str(struct.unpack(_TAG_INT[t], v)[0]).encode()
+        else:                                             # B: subtype, count, elements
+            fmt, count = _TAG_INT[v[0]], struct.unpack_from("<I", v, 1)[0]
+            vals = struct.unpack_from("<%d%s" % (count, fmt[1]), v, 5)
+            text = b"B:" + v[:1] + b"".join(b",%d" % x for x in vals)
+        parts.append(b"\t" + tag + b":" + text)
+        copied.append(True)
+    return b"".join(parts), copied, False, floats
+
+
+def fastq_text_tagged(data, tags, start=None):
+    """fastq_text with every record's tag_comment inserted in front of its first newline (behind the read name). Skipped records stay
+    skipped; a record on the reverse strand gets the same comment as it would on the forward strand (tags are not reversed)."""
+    data = bytes(data)
+    out = []
+    for r in records(data, start):
+        if r.skipped:
+            continue
+        text = r.fastq()
+        at = text.index(b"\n")
+        out.append(text[:at] + tag_comment(data, r.offset, tags)[0] + text[at:])
+    return b"".join(out)
+
+
+def tag_counts(data, tags, start=None):
+    """the counters of a run with --bam_tags over the delivered records of `data`: {"copied": [records in which tag j was copied],
+    "malformed_records": ..., "float_values_skipped": ...}"""
+    data = bytes(data)
+    copied, mal, fl = [0] * len(tags), 0, 0
+    for r in records(data, start):
+        if r.skipped:
+            continue
+        _, c, m, f = tag_comment(data, r.offset, tags)
+        mal += bool(m)
+        fl += f
+        for j, x in enumerate(c):
+            copied[j] += bool(x)
+    return {"copied": copied, "malformed_records": mal, "float_values_skipped": fl}
 
 
 def read_groups(header_bytes):

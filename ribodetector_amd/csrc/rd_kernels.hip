@@ -31,6 +31,7 @@
 //   rd_summary_*                       the QC counters of a run, added up chunk by chunk (rd_summary.hpp)
 //   rd_bam_find_*, rd_bam_count        a record start behind an offset of inflated BAM bytes, the records of a share (rd_bam_shard.hpp)
 //   rd_bam_tag_find, rd_bam_group_*    the optional fields of raw BAM records, and the counters per read group (rd_bam_tags.hpp)
+//   rd_bam_tag_splice                  the listed tags as text behind the read names of the FASTQ text (rd_bam_tagtext.hpp)
 //   rd_window_*                        reads longer than max_len as several windows: the window table and the fusion of its logits (rd_windows.hpp)
 //   rd_region_*                        the rRNA stretches of reads classified over windows, as text lines (rd_regions.hpp)
 #include <stdlib.h>
@@ -54,6 +55,7 @@
 #include "rd_pairs.hpp"
 #include "rd_summary.hpp"
 #include "rd_bam_tags.hpp"
+#include "rd_bam_tagtext.hpp"
 #include "rd_windows.hpp"
 #include "rd_regions.hpp"
 
@@ -1209,6 +1211,73 @@ int rd_bam_group_accumulate(const uint8_t *raw_a, const int64_t *raw_start_a, co
     const int64_t tiles = (n + GR_THREADS - 1) / GR_THREADS;
     hipLaunchKernelGGL(rd_bam_group_acc_kernel, dim3((unsigned)(tiles < GR_MAX_WGS ? tiles : GR_MAX_WGS)), dim3(GR_THREADS), 0, st, raw_a, raw_start_a, rows_a, first_a,
                        stride_a, raw_b, raw_start_b, rows_b, first_b, stride_b, labels, n, G, acc, info);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+// the listed tags of a chunk's raw records as text behind the read names of its FASTQ text (rd_bam_tagtext.hpp): one walk per listed tag
+// (rd_bam_tag_find's kernel, into tables of the workspace), the count pass, the scan into out_start, the write pass
+namespace {
+TagTextWs tagtext_ws(void *workspace, int64_t n, int32_t n_tags) {
+    TagTextWs p;
+    Carver c(workspace);
+    const size_t cells = (size_t)n * (size_t)n_tags;
+    p.nb = (int)((n + 1 + TT_THREADS - 1) / TT_THREADS);
+    p.val_off = c.take<int64_t>(cells);
+    p.val_len = c.take<int32_t>(cells);
+    p.val_type = c.take<uint8_t>(cells);
+    p.tag_bytes = c.take<int64_t>(cells);
+    p.hdr = c.take<int64_t>((size_t)n);
+    p.flags = c.take<uint8_t>((size_t)n);
+    p.bsum = c.take<int64_t>((size_t)p.nb);
+    p.tot = c.take<int64_t>(4);
+    p.cnt = c.take<unsigned long long>(TT_CNT);
+    p.fault = c.take<int32_t>(1);
+    p.total = c.off;
+    return p;
+}
+bool tag_name_ok(const uint8_t *t) {
+    const bool a = (t[0] >= 'A' && t[0] <= 'Z') || (t[0] >= 'a' && t[0] <= 'z');
+    return a && ((t[1] >= 'A' && t[1] <= 'Z') || (t[1] >= 'a' && t[1] <= 'z') || (t[1] >= '0' && t[1] <= '9'));
+}
+}  // namespace
+
+size_t rd_bam_tag_splice_workspace_bytes(int64_t n_rec, int32_t n_tags) {
+    if (n_rec < 0 || n_rec > 0x7fffffffLL / 64 || n_tags < 1 || n_tags > RD_BAM_TAGS_MAX) return 0;
+    return tagtext_ws(nullptr, n_rec, n_tags).total;
+}
+
+int rd_bam_tag_splice(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const uint8_t *raw, int64_t raw_bytes, const int64_t *raw_start,
+                      int64_t n_rec, const uint8_t *tags, int32_t n_tags, uint8_t *out, size_t out_cap, int64_t *out_start, int64_t *info, void *workspace,
+                      size_t workspace_bytes, void *stream) {
+    if (n_rec < 0 || n_rec > 0x7fffffffLL / 64 || text_bytes < 0 || raw_bytes < 0) RD_FAIL(RD_E_INVALID, "rd_bam_tag_splice: bad n_rec, text_bytes or raw_bytes");
+    if (n_tags < 1 || n_tags > RD_BAM_TAGS_MAX) RD_FAIL(RD_E_INVALID, "rd_bam_tag_splice: n_tags=%d out of range [1,%d]", n_tags, RD_BAM_TAGS_MAX);
+    if (!tags) RD_FAIL(RD_E_INVALID, "rd_bam_tag_splice: null pointer");
+    TtNames names;
+    memset(&names, 0, sizeof(names));
+    for (int j = 0; j < n_tags; ++j) {
+        if (!tag_name_ok(tags + 2 * j)) RD_FAIL(RD_E_INVALID, "rd_bam_tag_splice: tag %d is not a name ([A-Za-z][A-Za-z0-9])", j);
+        for (int i = 0; i < j; ++i)
+            if (tags[2 * i] == tags[2 * j] && tags[2 * i + 1] == tags[2 * j + 1]) RD_FAIL(RD_E_INVALID, "rd_bam_tag_splice: tag %d appears twice", j);
+        names.b[2 * j] = tags[2 * j];
+        names.b[2 * j + 1] = tags[2 * j + 1];
+    }
+    if (!info) RD_FAIL(RD_E_INVALID, "rd_bam_tag_splice: null info");
+    hipStream_t st = (hipStream_t)stream;
+    if (n_rec == 0) {
+        RD_HIP(hipMemsetAsync(info, 0, (8 + RD_BAM_TAGS_MAX) * sizeof(int64_t), st));
+        return RD_OK;
+    }
+    if (!text || !rec_start || !raw_start || (!raw && raw_bytes > 0) || !out || !out_start || !workspace) RD_FAIL(RD_E_INVALID, "rd_bam_tag_splice: null pointer");
+    if (((uintptr_t)workspace & 255) || ((uintptr_t)out & 15)) RD_FAIL(RD_E_INVALID, "rd_bam_tag_splice: workspace must be 256-byte aligned, out 16-byte aligned");
+    const TagTextWs p = tagtext_ws(workspace, n_rec, n_tags);
+    if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "rd_bam_tag_splice: workspace too small: %zu < %zu", workspace_bytes, p.total);
+    const int64_t cap = (int64_t)(out_cap < (size_t)INT64_MAX ? out_cap : (size_t)INT64_MAX);
+    RD_HIP(hipMemsetAsync(p.cnt, 0, (size_t)((char *)p.fault - (char *)p.cnt) + sizeof(int32_t), st));      // (the counters and the fault word)
+    if (tag_lanes(raw_bytes, n_rec) == 16)
+        tagtext_launch<16>(text, text_bytes, rec_start, raw, raw_bytes, raw_start, n_rec, n_tags, names, out, cap, out_start, info, p, st);
+    else
+        tagtext_launch<4>(text, text_bytes, rec_start, raw, raw_bytes, raw_start, n_rec, n_tags, names, out, cap, out_start, info, p, st);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }

@@ -40,6 +40,10 @@ rd_bam_raw_gather, csrc/rd_bam_raw.hpp), and the output kernels select from THAT
 header of its input, the selected records byte for byte, BGZF members. Classification, report, summary and regions see the FASTQ view.
 --read_groups (an extension, BAM input, with --summary): the chunks carry the same raw view, and every chunk's units are counted per
 read group on the post stream (groups.py: rd_bam_tag_find / rd_bam_group_rows / rd_bam_group_accumulate); the summary gains "read_groups".
+--bam_tags LIST (an extension, BAM input, FASTQ outputs): the chunks carry the raw view, and every chunk gets one more view, the TAGGED
+text - its FASTQ text with the listed tags of every record behind the read name (bamtags.py: rd_bam_tag_splice, csrc/rd_bam_tagtext.hpp;
+bam.tag_comment has the rule). It depends on the chunk alone, so it is made on the copy stream when the chunk is submitted; the output
+kernels select from that view (_select_chunk), everything else sees the untagged FASTQ view.
 """
 import argparse
 import functools
@@ -58,6 +62,7 @@ import torch.distributed as dist
 from . import __version__
 from . import _native as _native_mod
 from . import bam as _bammod
+from . import bamtags as _tagmod
 from . import dist as rdist
 from . import groups as _grpmod
 from . import gz as _gzmod
@@ -247,7 +252,9 @@ class Predictor:
         self.read_groups = bool(getattr(args, 'read_groups', False))     # --summary gains the counters per BAM read group
         self.bam_shard = bool(getattr(args, 'bam_shard', False))         # BAM input under several ranks: the sharded parse (data_loader/bam_shard.py)
         self._groups = None                      # ... groups.DeviceGroups (run_with_chunks)
-        self._pairs = None                       # --interleaved: gz.DevicePairSplit (run_with_chunks)
+        self.bam_tags = _tagmod.parse_list(args.bam_tags) if getattr(args, 'bam_tags', None) is not None else None     # --bam_tags: the listed names (2 bytes each)
+        self._tags = None                        # ... bamtags.DeviceBamTags, one per input file (run_with_chunks)
+        self._pairs = None                      # --interleaved: gz.DevicePairSplit (run_with_chunks)
         self._summary = None                     # --summary: summary.DeviceSummary (run_with_chunks)
         self._windows = None                     # --windows: {"stride", "max_per_read", "fuse"} (stride None = -l); detect() sets it
         self._win_classified = [0, 0]            # windows this rank classified, per mate
@@ -511,6 +518,7 @@ class Predictor:
             cur.wait_stream(cs)
         # (dev_in stays referenced by the ticket: its tensors were allocated on the copy stream and must not return to that
         # stream's pool while other streams read them - and the deferred float64 pass reads the bases until the post-pass has run)
+        tagged = self._tag_chunks(chunks, on_dev) if self._tags is not None else None      # --bam_tags: the view the outputs select from
         if plans is None:
             outs = [self.model.classify_bytes(a, o, l, self.len, want_labels=not self.is_paired) for a, o, l in dev_in]
         else:                                       # (the window tables: the reads' own entries where nothing is longer than -l)
@@ -539,7 +547,7 @@ class Predictor:
             else:
                 labels = outs[0][1].view(torch.int8)
             host = None if self.gathers_labels else _pinned(labels)
-            pieces = self._select_chunk(chunks, dev_in, labels, lo, hi, on_dev, pairs)
+            pieces = self._select_chunk(chunks, dev_in, labels, lo, hi, on_dev, pairs, tagged)
             if self._report is not None:
                 pieces[REPORT] = self._report_chunk(chunks, dev_in, outs, labels, lo, hi, pairs)
             regions = None
@@ -561,9 +569,27 @@ class Predictor:
             done.record(post)
         return {"n": n, "bounds": bounds, "labels": labels, "host": host, "finish": finish, "done": done, "keep": (dev_in, outs, plans),
                 "pieces": pieces, "pairs": pairs, "chunk": chunks[0], "totals": [t for c in chunks for t in (c.total, c.raw_total) if t is not None] if on_dev else (), "summary": sum_info,
-                "regions": regions, "groups": grp_info, "keep_raw": keep_raw}
+                "regions": regions, "groups": grp_info, "keep_raw": keep_raw, "tagged": tagged}
 
-    def _select_chunk(self, chunks, dev_in, labels, lo, hi, on_dev, pairs=None):
+    def _tag_chunks(self, chunks, on_dev):
+        """--bam_tags: [(tagged text, its record table)] of every input's chunk (bamtags.DeviceBamTags.splice), made on the COPY stream
+        behind the chunk's `ready` event - not behind the recurrences of the chunk before, which fill the main stream. The host waits
+        there for the call's verdict and sizes (a chunk that did not fit its hint is spliced again), as it waits for the window plans.
+        The ticket keeps the views: they were allocated on the copy stream and are read on the post stream."""
+        if not on_dev:
+            raise RuntimeError("--bam_tags: the chunk's text is not on the device (BAM input is device ingest only)")
+        out = []
+        with torch.cuda.stream(self._copy_stream):
+            for c, tg in zip(chunks, self._tags):
+                self._copy_stream.wait_event(c.ready)
+                _native_mod.wait_event(c.ready)
+                if any(t is not None and int(t[0]) < 0 for t in (c.total, c.raw_total)):
+                    raise RuntimeError("device chunk assembly failed (rd_fastq_gather)")
+                text, out_start, _ = tg.splice(c)
+                out.append((text, out_start))
+        return out
+
+    def _select_chunk(self, chunks, dev_in, labels, lo, hi, on_dev, pairs=None, tagged=None):
         """{(mate, label): [Piece]}: the label files whose records of this chunk are selected on the device, on the post stream beside
         the next chunk's recurrences, so that only the selected bytes travel to the host. A chunk whose text lives on the device: every
         file's, deflated (.gz outputs: BGZF members, csrc/rd_deflate.hpp) or packed into one text (rd_select_pack). Otherwise the .gz
@@ -592,6 +618,14 @@ class Predictor:
                         views[e] = (raw, raw_start[0:2 * (hi - lo) + 1:2].contiguous(), labels.view(torch.int8))
                     else:
                         views[e] = (raw, raw_start, self._pairs.expand(labels.view(torch.int8), e, slot=pairs["ring"]))
+                elif tagged is not None:            # --bam_tags: the text with the tags behind the read names, selected like the text
+                    ttext, tstart = tagged[e if pairs is None else 0]
+                    if pairs is None:
+                        views[e] = (ttext, tstart, labels.view(torch.int8))
+                    elif len(self.output) == 1:     # pair k = tagged records 2 k and 2 k + 1
+                        views[e] = (ttext, tstart[0:2 * (hi - lo) + 1:2].contiguous(), labels.view(torch.int8))
+                    else:
+                        views[e] = (ttext, tstart, self._pairs.expand(labels.view(torch.int8), e, slot=pairs["ring"]))
                 elif pairs is None:
                     views[e] = self._device_text(chunks[e], dev_in[e][0], lo, hi) + (labels.view(torch.int8),)
                 elif len(self.output) == 1:         # interleaved output: the pairs are the records
@@ -756,7 +790,7 @@ class Predictor:
                 if arena is None and self._device_parse(path):
                     st = self.ingest.setdefault(os.path.basename(str(path)), {"path": "device"})
                     stream = dr.get_seq_chunks_device(path, chunk_size=chunk_reads, byte_range=byte_range, first_chunk=first, schedule=schedule,
-                                                      device=self.device, stats=st, keep_raw=self.bam_output or self.read_groups,
+                                                      device=self.device, stats=st, keep_raw=self.bam_output or self.read_groups or self.bam_tags is not None,
                                                       rank=self.rank if self.sharded_parse else None)
                 # one plain input file: its parser thread was the slowest stage of the pipeline - two readers over byte segments,
                 # small first chunks (mate files keep one reader each and exact chunk sizes: their chunks must pair up)
@@ -987,6 +1021,13 @@ class Predictor:
                 if self.rank == 0:
                     self.logger.info('BAM input: {} records, {} secondary/supplementary skipped ({})'.format(
                         sum(r[f][0] for r in per_rank), sum(r[f][1] for r in per_rank), path))
+        if self._tags is not None:                 # --bam_tags: every rank tagged the records of its own share
+            mine = _tagmod.as_vector([t.counts() for t in self._tags], len(self.bam_tags)).tolist()
+            per_rank = self._all_gather(mine) if self.sharded_parse else [mine]
+            total = [sum(int(r[k]) for r in per_rank) for k in range(len(mine))]
+            self._tag_total = _tagmod.from_vector(total, len(self.bam_tags), len(self._tags))
+            if self.rank == 0:
+                self.logger.info(_tagmod.log_line(self.bam_tags, self._tag_total))
         if self.interleaved:
             fx.check_even_records(self._records_seen)
         if self._windows is not None:              # every rank classified the windows of its own shard / byte range
@@ -1036,6 +1077,8 @@ class Predictor:
             if got != units:
                 raise RuntimeError("--read_groups: the rows of the read groups hold {} unclassified / non-rRNA / rRNA units, the run {}".format(got, units))
             rg = doc["read_groups"] = _grpmod.to_json(gacc, grp.groups, bool(self.is_paired), input=self.input[0])
+        if self._tags is not None:
+            doc["bam_tags"] = _tagmod.to_json(self.bam_tags, self._tag_total)
         _summod.write_json(path, doc)
         frac = doc["reads"]["rRNA_fraction"]
         self.logger.info('rRNA fraction: {} (summary: {})'.format("n/a" if frac is None else "%.6f" % frac, path))
@@ -1191,6 +1234,8 @@ class Predictor:
         self._summary = _summod.DeviceSummary(self.device) if getattr(self.args, 'summary', None) else None
         # --read_groups: the same units per read group of mate 1's BAM, one more int64 array that every chunk adds to
         self._groups = _grpmod.DeviceGroups(self.device, _bammod.header(self.input[0])) if self.read_groups else None
+        # --bam_tags: the tagged view of every chunk, and the counters of the tags copied, per input file
+        self._tags = [_tagmod.DeviceBamTags(self.device, self.bam_tags) for _ in self.input] if self.bam_tags is not None else None
         self._win_classified = [0, 0]
         # --regions: the lines of every chunk, formatted on the device; mate 1's writer appends the pieces (and deflates a .gz file)
         self._regions = bool(getattr(self.args, 'regions', None))
@@ -1286,6 +1331,7 @@ class Predictor:
         check_summary(getattr(self.args, 'summary', None), self.output, self.rrna, self.is_paired, self.args.ensure,
                       getattr(self.args, 'read_report', None), self.bam_output)
         check_read_groups(self.read_groups, getattr(self.args, 'summary', None), self.input, self.bam_shard)
+        check_bam_tags(getattr(self.args, 'bam_tags', None), self.input, self.bam_output)
         self._windows = check_windows(self.args)
         check_regions(getattr(self.args, 'regions', None), self._windows is not None, self.output, self.rrna, self.is_paired, self.args.ensure,
                       getattr(self.args, 'read_report', None), getattr(self.args, 'summary', None), self.bam_output)
@@ -1435,6 +1481,23 @@ def check_summary(path, output, rrna, is_paired, ensure, read_report=None, bam_o
             raise RuntimeError("--summary {} is also {}".format(path, what))
 
 
+def check_bam_tags(bam_tags, inputs, bam_output=False):
+    """--bam_tags LIST: the rules that hold before anything touches a device; returns the listed names (2 bytes each, list order), or
+    None without the flag. The list holds 1..16 names [A-Za-z][A-Za-z0-9], none twice (bamtags.parse_list); every input is BAM (the
+    tags are those of BAM records); not with --bam_output, whose outputs keep every tag as it stands."""
+    if bam_tags is None:
+        return None
+    names = _tagmod.parse_list(bam_tags)
+    other = [p for p in inputs or [] if fx.get_seq_format(p) != "bam"]
+    if other or not inputs:
+        raise RuntimeError("--bam_tags copies the tags of BAM records into the FASTQ header lines: every -i file must end with .bam or .ubam, got {} "
+                           "(checked before anything touches a device)".format(", ".join(other) or "no input"))
+    if bam_output:
+        raise RuntimeError("--bam_tags writes the tags into FASTQ header lines; with --bam_output the outputs are BAM files that keep every tag "
+                           "already: give one of the two (checked before anything touches a device)")
+    return names
+
+
 def check_read_groups(read_groups, summary, inputs, bam_shard=False):
     """--read_groups: the rules that hold before anything touches a device; returns the declared groups of mate 1's BAM
     (bam.read_groups: [(id, fields)], header order), or None without the flag. The flag adds an object to the --summary file, so it
@@ -1581,6 +1644,14 @@ none: give label based on the mean probability of read pair.
                            'writes its own share of the records, like the ranks of a BGZF FASTQ run. The shares begin at record starts\n'
                            'found by a search on the GPU (8 records in a row that look like records); a cut that is none ends the run\n'
                            'with an error before any output is joined - run such a file on one rank. One rank: changes nothing.')
+    args.add_argument('--bam_tags', default=None, type=str, metavar='LIST',
+                      help='(extension) BAM input, FASTQ outputs: LIST = tag names separated by commas (MM,ML,RG; at most 16). Every FASTQ\n'
+                           'record written carries the listed tags of its BAM record behind the read name, in list order, in SAM\'s\n'
+                           'text form: @name<TAB>MM:Z:...<TAB>ML:B:C,... (what samtools fastq -T writes and minimap2 -y reads). A tag a\n'
+                           'record does not have adds nothing. Float-typed values (f, B:f) are NOT copied; they are counted. A record\n'
+                           'whose listed tags are malformed, or hold a byte that no header line may hold, gets no comment and is\n'
+                           'counted. Formatted on the GPU; the run keeps the records as they stand in the input and the tagged text in\n'
+                           'GPU memory next to the FASTQ text. Not with --bam_output, which keeps every tag already.')
     args.add_argument('--no_mate_check', action='store_true', help='(extension) with --interleaved: do not compare the ids of the mates')
     args.add_argument('-v', '--version', action='version', version='%(prog)s {version}'.format(version=__version__))
     return args
@@ -1595,6 +1666,7 @@ def main(argv=None, log_level=None):
     check_bam(args.input, args.output, args.rrna, getattr(args, 'bam_output', False), getattr(args, 'bam_shard', False),
               getattr(args, 'interleaved', False))
     check_read_groups(getattr(args, 'read_groups', False), getattr(args, 'summary', None), args.input, getattr(args, 'bam_shard', False))
+    check_bam_tags(getattr(args, 'bam_tags', None), args.input, getattr(args, 'bam_output', False))
     seq_pred = Predictor(config, args, log_level=log_level)
     try:
         t0 = time.perf_counter()

@@ -17,6 +17,11 @@ timed calls of each, ALTERNATING the legs (model load excluded: Predictor.timing
           probe of either shape, and rd_bam_count against rd_bam_index - the yardstick, timed in the same process - on the same resident
           batch; short times fastx_parser.plan_ranges over BamViews for two ranks that share the GPU (threads of this process: host-side
           evidence only), one file and two files, and the one-rank CLI with and without --bam_shard, the legs alternating.
+  --bam_tags     the measurements of --bam_tags (bamtags.py, csrc/rd_bam_tagtext.hpp): short = `--reads` reads of 100 bp with NM:i XS:A RG:Z
+          (the records of tools/groups_bench.py) -> .gz, the legs no flag (the yardstick: the behaviour without the feature) and --bam_tags RG,
+          alternating, with the peak of torch's allocator in each leg; long = `--long_reads` reads of 10 kb with MM:Z of 2 kB and ML:B:C of
+          2,000 elements, --bam_tags MM,ML --windows --chunk_size 1; kernel = rd_bam_tag_splice ALONE on a resident chunk of both
+          shapes, 20 calls with device events.
 Every fourth record of the BAM files is stored on the reverse strand (flag 0x10, bases reverse-complemented, qualities reversed), so
 that the text the two legs see is the same. The inputs are written by processes that never touch the GPU."""
 import argparse
@@ -363,6 +368,106 @@ def bench_shard_cli(d, reads, calls):
                       "outputs_byte_identical": bool(same)}), flush=True)
 
 
+def _make_tagged(job):
+    """the BAM files of the --bam_tags measurements: groups_bench's records (short: its 100 bp file; long: 10 kb with MM:Z and ML:B:C)"""
+    d, shape, reads = job
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import groups_bench
+    from ribodetector_amd import bam, synth
+    if shape == "short":
+        groups_bench._make((d, reads))
+        return
+    path = os.path.join(d, "mm_%d.bam" % reads)
+    if os.path.exists(path):
+        return
+    step = 4096
+    with open(path + ".raw", "wb") as fh:
+        fh.write(bam.encode_header(text=b"@HD\tVN:1.6\tSO:unsorted\n@RG\tID:grp000\n"))
+        for first in range(0, reads, step):
+            rec = groups_bench.records(min(step, reads - first), SHAPES["long"], 1, True, seed=3 + first // step)[0]
+            rec[:, 36 + NAME:36 + NAME + SHAPES["long"] // 2] &= 0x77          # (bases among = A C M G R S V: no code the text cannot hold)
+            rec[:, 36 + NAME:36 + NAME + SHAPES["long"] // 2] |= 0x11
+            fh.write(rec.tobytes())
+    synth.bgzip_file(path + ".raw", path, level=1, threads=8)
+    os.remove(path + ".raw")
+
+
+def bench_cli_bam_tags(d, shape, reads, calls):
+    """x.bam -> .fq.gz without the flag (the yardstick) against the same with --bam_tags: one input file, the legs alternating"""
+    import torch
+    from ribodetector_amd import detect
+    extra = ["--windows", "--chunk_size", "1"] if shape == "long" else []
+    src = os.path.join(d, ("rg_%d.bam" if shape == "short" else "mm_%d.bam") % reads)
+    tags = "RG" if shape == "short" else "MM,ML"
+    argv = {"no_flag": ["-l", "100", "-i", src, "-o", os.path.join(d, "o_plain.fq.gz")] + extra,
+            "bam_tags": ["-l", "100", "-i", src, "-o", os.path.join(d, "o_tags.fq.gz"), "--bam_tags", tags] + extra}
+    for k in argv:
+        detect.main(argv[k], log_level="WARNING")
+    secs, peak, last = {k: [] for k in argv}, {}, {}
+    for _ in range(calls):
+        for k in argv:
+            torch.cuda.reset_peak_memory_stats()
+            last[k] = detect.main(argv[k], log_level="WARNING")
+            secs[k].append(last[k].timing["detect_s"])
+            peak[k] = max(peak.get(k, 0), torch.cuda.max_memory_allocated())
+    rate = {k: sorted(reads / s for s in v) for k, v in secs.items()}
+    med = {k: statistics.median(v) for k, v in rate.items()}
+    yard = rate["no_flag"]
+    outside = 0.0 if yard[0] <= med["bam_tags"] <= yard[-1] else (med["bam_tags"] / yard[0] - 1 if med["bam_tags"] < yard[0] else med["bam_tags"] / yard[-1] - 1)
+    same = all(getattr(last["bam_tags"], a) == getattr(last["no_flag"], a) for a in ("num_read", "num_rrna", "num_nonrrna"))
+    print(json.dumps({"measurement": shape + "_bam_tags", "reads": reads, "read_len": SHAPES[shape], "calls": calls, "tags": tags,
+                      "flow": "single-end x.bam -> .fq.gz, without | with --bam_tags " + tags + (", --windows --chunk_size 1" if extra else ""),
+                      "input_bytes": os.path.getsize(src), "output_bytes": {k: os.path.getsize(v[5]) for k, v in argv.items()},
+                      "reads_per_s": {k: _mlh(v) for k, v in rate.items()}, "ratio_of_medians": round(med["bam_tags"] / med["no_flag"], 4),
+                      "with_flag_median_inside_no_flag_spread": bool(outside == 0.0), "outside_the_spread_by": round(outside, 4),
+                      "peak_allocated_MB": {k: round(v / 1e6) for k, v in peak.items()}, "flag_adds_MB": round((peak["bam_tags"] - peak["no_flag"]) / 1e6),
+                      "same_counts": bool(same), "copied": last["bam_tags"]._tag_total[0]["copied"], "splice_repeats": sum(t.repeats for t in last["bam_tags"]._tags)}),
+          flush=True)
+
+
+def bench_kernel_bam_tags(calls):
+    """rd_bam_tag_splice alone on a resident chunk of both shapes: 2^20 records of 100 bp (RG) and 8,192 of 10 kb (MM, ML)"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import groups_bench
+    from ribodetector_amd import bam, bamtags
+    dev = torch.device("cuda:0")
+    for shape, n, length, long_tags, tags in (("short", 1 << 20, 100, False, [b"RG"]), ("long", 8192, 10000, True, [b"MM", b"ML"])):
+        rec, size, t_bytes, _ = groups_bench.records(n, length, 1, long_tags)
+        frec = 2 * length + NAME + 5
+        fq = np.full((n, frec), ord("A"), np.uint8)
+        fq[:, 0] = ord("@")
+        fq[:, 1:NAME] = ord("r")
+        fq[:, NAME] = fq[:, NAME + 1 + length] = fq[:, NAME + 3 + length] = fq[:, -1] = 10
+        fq[:, NAME + 2 + length] = ord("+")
+        raw = torch.from_numpy(rec.reshape(-1)).to(dev)
+        text = torch.from_numpy(fq.reshape(-1)).to(dev)
+        rs = torch.arange(n + 1, dtype=torch.int64, device=dev) * frec
+        st = torch.arange(n + 1, dtype=torch.int64, device=dev) * size
+        cap = bamtags.default_hint(text.numel(), raw.numel())
+        out = torch.empty(((cap + 255) // 256) * 256 + 256, dtype=torch.uint8, device=dev)
+        us = _events(lambda: bamtags.splice(text, rs, raw, st, n, tags, cap, out=out), calls)
+        _, out_start, info = bamtags.splice(text, rs, raw, st, n, tags, cap, out=out)
+        info = info.cpu().tolist()
+        k = n // 2
+        a, b = int(out_start[k]), int(out_start[k + 1])
+        data = bam.encode_header() + rec[k].tobytes()
+        want = fq[k].tobytes()[:NAME] + bam.tag_comment(data, bam.header_len(data), tags)[0] + fq[k].tobytes()[NAME:]
+        assert info[3] == 0 and info[8:8 + len(tags)] == [n] * len(tags) and bytes(out[a:b].cpu().numpy()) == want, info
+        med = statistics.median(us)
+        # the text is read and the tagged text written once; the raw view's fixed part and tags are read by every walk, the values again by the
+        # count and the write pass; per record and tag 21 bytes of tables are written and read twice, per record 25 bytes of tables
+        value_bytes = info[1] - text.numel()
+        moved = text.numel() + info[1] + n * (36 + t_bytes) * len(tags) + 2 * value_bytes + n * (len(tags) * 21 * 3 + 25 * 3)
+        print(json.dumps({"measurement": "kernel_bam_tags", "what": "rd_bam_tag_splice", "shape": shape, "read_len": length, "records": n, "tags": [t.decode() for t in tags],
+                          "text_bytes": text.numel(), "raw_bytes": raw.numel(), "tagged_bytes": info[1], "calls": calls, "us_per_call": _us(us),
+                          "bytes_moved": moved, "TB_per_s": round(moved / med / 1e6, 3),
+                          "fraction_of_hbm_bound_pass_at_8TBps": round(moved / 8e12 / (med * 1e-6), 4)}), flush=True)
+        del raw, text, out
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=1 << 22, help="reads of the short leg")
@@ -373,6 +478,7 @@ def main():
     ap.add_argument("--trace", default=None)
     ap.add_argument("--bam_output", action="store_true", help="the measurements of BAM output instead")
     ap.add_argument("--shard", action="store_true", help="the measurements of --bam_shard instead")
+    ap.add_argument("--bam_tags", action="store_true", help="the measurements of --bam_tags instead")
     a = ap.parse_args()
     if a.trace:
         t, total = trace_times(a.trace)
@@ -382,6 +488,24 @@ def main():
     which = [a.only] if a.only else ["short", "long", "kernel"]
     if a.shard:                                  # (the 100 bp file only: the probes and the batch of the 10 kb shape are made in memory)
         which = [w for w in which if w != "long"]
+    if a.bam_tags:
+        d = a.keep or tempfile.mkdtemp(prefix="rdbam", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+        os.makedirs(d, exist_ok=True)
+        try:
+            jobs = [(d, s, n) for s, n in (("short", a.reads), ("long", a.long_reads)) if s in which]
+            if jobs:
+                import multiprocessing as mp
+                with mp.get_context("spawn").Pool(len(jobs)) as pool:          # (before anything initialises the GPU)
+                    pool.map(_make_tagged, jobs)
+            import ribodetector_amd  # noqa: F401
+            for _, s, n in jobs:
+                bench_cli_bam_tags(d, s, n, a.calls)
+            if "kernel" in which:
+                bench_kernel_bam_tags(20)
+        finally:
+            if not a.keep:
+                shutil.rmtree(d, ignore_errors=True)
+        return
     jobs = [(s, n, a.bam_output or a.shard) for s, n in (("short", a.reads), ("long", a.long_reads)) if s in which]
     d = a.keep or tempfile.mkdtemp(prefix="rdbam", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
     os.makedirs(d, exist_ok=True)
