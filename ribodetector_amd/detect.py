@@ -73,6 +73,7 @@ from .data_loader import device_reader as dr
 from .data_loader import fastx_parser as fx
 from .model import model as module_arch
 from .parse_config import ConfigParser
+from .ticket import RegionRepeat, Ticket
 
 cd = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_CHUNK_READS = 1 << 20      # records per chunk when --chunk_size is not given (reference: whole file in RAM)
@@ -110,6 +111,22 @@ TEXT_FILES = (REPORT, REGIONS)  # files of text made on the device, not of a lab
 def _pinned(t):
     """a pinned host copy of a device tensor, queued on the current stream (read it once an event recorded behind it has passed)"""
     return torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
+
+
+def record_view(source, n, labels, e, interleaved=False, outs=2, pair_table=None, expand=None):
+    """(text, record table, selecting labels) of mate e's records, as DeviceGzip.compress_selected and DeviceSelect.pack_selected take
+    them - the one place that knows the three layouts. source: (text, record table) of this rank's n units; labels: the unit labels.
+      two input files: record k of mate e's source is unit k;
+      interleaved, one output: pair k is records 2 k and 2 k + 1, so the table is every second entry - pair_table where the source
+        has that table already (rd_pair_split wrote it), else a copy of the entries;
+      interleaved, two outputs: mate e's records of the full table - expand(labels, e) labels record 2 k + e as pair k and the other
+        mate's records RD_LABEL_SKIP, which no file selects (the run: DevicePairSplit.expand; the host: fx.expand_pair_labels)."""
+    text, table = source
+    if not interleaved:
+        return text, table, labels
+    if outs == 1:
+        return text, table[0:2 * n + 1:2].contiguous() if pair_table is None else pair_table, labels
+    return text, table, expand(labels, e)
 
 
 class Piece(NamedTuple):
@@ -245,6 +262,9 @@ class Predictor:
         self._shared = None                      # gzip input, several ranks of one node: one decode per node (decided once per run)
         self._chunk_reads = None
         self._use_device = None                  # does the text of the inputs stay on the device? decided once per run
+        # the options that a hand-built Namespace may lack (tests, API users) are read here, once; everything below uses the attributes
+        self.report_path, self.summary_path, self.regions_path, self.bam_tags_arg = (
+            getattr(args, k, None) for k in ('read_report', 'summary', 'regions', 'bam_tags'))
         self._report = None                      # --read_report: gz.DeviceReport (run_with_chunks)
         self.interleaved = bool(getattr(args, 'interleaved', False))     # paired-end reads from ONE interleaved FASTQ file
         self.mate_check = not getattr(args, 'no_mate_check', False)
@@ -252,7 +272,7 @@ class Predictor:
         self.read_groups = bool(getattr(args, 'read_groups', False))     # --summary gains the counters per BAM read group
         self.bam_shard = bool(getattr(args, 'bam_shard', False))         # BAM input under several ranks: the sharded parse (data_loader/bam_shard.py)
         self._groups = None                      # ... groups.DeviceGroups (run_with_chunks)
-        self.bam_tags = _tagmod.parse_list(args.bam_tags) if getattr(args, 'bam_tags', None) is not None else None     # --bam_tags: the listed names (2 bytes each)
+        self.bam_tags = _tagmod.parse_list(self.bam_tags_arg) if self.bam_tags_arg is not None else None     # ... the listed names (2 bytes each)
         self._tags = None                        # ... bamtags.DeviceBamTags, one per input file (run_with_chunks)
         self._pairs = None                      # --interleaved: gz.DevicePairSplit (run_with_chunks)
         self._summary = None                     # --summary: summary.DeviceSummary (run_with_chunks)
@@ -412,17 +432,21 @@ class Predictor:
             ln = tlen[lo:hi].to(self.device, non_blocking=True)
         return arena, off, ln
 
-    def _device_text(self, chunk, arena, lo, hi):
-        """text (arena: from _to_device) and int64 record starts on the device of records [lo, hi) of one mate's chunk"""
+    def _fastq_view(self, chunks, dev_in, e, lo, hi, pairs=None):
+        """the FASTQ view of mate e's units [lo, hi) of a chunk as a source of record_view: ((text, int64 record starts) on the device,
+        table of the pairs or None). Interleaved: one text for both mates, and rd_pair_split left the table of its pairs beside it."""
+        if pairs is not None:
+            return (pairs["text"], pairs["rec_start"]), pairs["pair_start"]
+        chunk = chunks[e]
         if isinstance(chunk, dr.DeviceChunk):
-            return chunk.dev[0], chunk.dev[3]
-        return arena, chunk.tensors[3][lo:hi + 1].to(self.device, non_blocking=True) - int(chunk.rec_start[lo])
+            return (chunk.dev[0], chunk.dev[3]), None
+        return (dev_in[e][0], chunk.tensors[3][lo:hi + 1].to(self.device, non_blocking=True) - int(chunk.rec_start[lo])), None
 
-    def _split_pairs(self, chunk, lo, hi, on_dev):
+    def _split_pairs(self, tk, chunk, lo, hi, on_dev, ring):
         """--interleaved: pairs [lo, hi) of a chunk of 2n records as two mates. The split runs once the chunk's tables are on the device
         (a device chunk: behind its `ready` event; a host chunk: after the H2D of records [2 lo, 2 hi)). Returns (dev_in of the two
         mates over the ONE text, pairs): pairs = the text with its record table and its pair table, for the outputs and the report, and
-        the pinned verdict of the mate check, which collect_chunk reads after the event it waits for anyway."""
+        the pinned verdict of the mate check, which the ticket's "pairs" check reads after the event collect_chunk waits for anyway."""
         cs, cur = self._copy_stream, torch.cuda.current_stream(self.device)
         if on_dev:
             cur.wait_event(chunk.ready)
@@ -432,11 +456,10 @@ class Predictor:
             with torch.cuda.stream(cs):
                 rs = chunk.tensors[3][2 * lo:2 * hi + 1].to(self.device, non_blocking=True) - int(chunk.rec_start[2 * lo])
             cur.wait_stream(cs)
-        ring = self._pair_seq % self.GZ_RING
-        self._pair_seq += 1
         pair_start, m1, m2, info = self._pairs.split(text, rs, so, sl, hi - lo, check_ids=self.mate_check, slot=ring)
-        pairs = {"text": text, "rec_start": rs, "pair_start": pair_start, "info": _pinned(info), "ring": ring, "lo": lo,
+        pairs = {"text": text, "rec_start": rs, "pair_start": pair_start, "info": _pinned(info), "lo": lo,
                  "first_record": self._chunk_first_record, "keep": (so, sl)}
+        tk.checks["pairs"] = functools.partial(self._check_pairs, chunk, pairs)
         return [(text,) + m1, (text,) + m2], pairs
 
     def _read_work(self, seq_len):
@@ -447,7 +470,7 @@ class Predictor:
             work = work * _winmod.counts(ln, self.len, self._windows["stride"] or self.len, self._windows["max_per_read"])
         return work
 
-    def _plan_windows(self, chunks, lo, hi, on_dev):
+    def _plan_windows(self, tk, chunks, lo, hi, on_dev, ring):
         """--windows: the chunk's tables reach the device and the window table of every mate is planned and written on the COPY stream
         (behind the chunk's `ready` event or its H2D - not behind the recurrences of the chunk before, which fill the main stream); the
         host waits there, once, for the numbers of windows, which size the tables and the classify calls. The main stream then waits
@@ -456,7 +479,7 @@ class Predictor:
         w, pairs = self._windows, None
         with torch.cuda.stream(cs):
             if self.interleaved:
-                dev_in, pairs = self._split_pairs(chunks[0], lo, hi, on_dev)
+                dev_in, pairs = self._split_pairs(tk, chunks[0], lo, hi, on_dev, ring)
             elif on_dev:
                 dev_in = [c.dev[:3] for c in chunks]
                 for c in chunks:
@@ -488,10 +511,13 @@ class Predictor:
         raise MateMismatch("interleaved input: records {} and {} are not mates (ids '{}' and '{}'): a record is missing or the file is "
                            "not interleaved; --no_mate_check turns this check off".format(first, first + 1, ids[0], ids[1]))
 
-    def submit_chunk(self, chunks):
+    def submit_chunk(self, chunks, seq=None):
         """Enqueue one chunk: H2D on the copy stream, kernels on the compute stream, D2H of the labels into pinned memory.
-        Nothing here waits for the GPU, so the next chunk's H2D overlaps this chunk's kernels. Returns a ticket for
-        collect_chunk()."""
+        Nothing here waits for the GPU, so the next chunk's H2D overlaps this chunk's kernels. seq: the chunk's number in the run
+        (None: the one behind the last chunk's); it picks the ring slot of every buffer that the pair split, the selection, the report
+        and the regions write for this chunk. Returns a Ticket for collect_chunk()."""
+        seq = self._chunk_seq if seq is None else seq
+        self._chunk_seq, ring = seq + 1, seq % self.GZ_RING
         n = fx.interleaved_pairs(chunks[0]) if self.interleaved else len(chunks[0].seq_len)
         bounds = None
         if self.gathers_labels:                     # equal bases (= recurrence steps) per rank, not equal read counts
@@ -504,11 +530,15 @@ class Predictor:
         cs = self._copy_stream
         cur = torch.cuda.current_stream(self.device)
         on_dev = isinstance(chunks[0], dr.DeviceChunk)      # text and index already in HBM (data_loader/device_reader.py): nothing to copy
+        tk = Ticket(n, bounds, chunks[0])
+        totals = [t for c in chunks for t in (c.total, c.raw_total) if t is not None] if on_dev else ()
+        if totals:                                  # the bytes rd_fastq_gather made of the chunk's views, pinned behind `ready`
+            tk.checks["totals"] = functools.partial(self._check_totals, totals)
         pairs = plans = None
         if self._windows is not None:
-            dev_in, pairs, plans = self._plan_windows(chunks, lo, hi, on_dev)
+            dev_in, pairs, plans = self._plan_windows(tk, chunks, lo, hi, on_dev, ring)
         elif self.interleaved:
-            dev_in, pairs = self._split_pairs(chunks[0], lo, hi, on_dev)
+            dev_in, pairs = self._split_pairs(tk, chunks[0], lo, hi, on_dev, ring)
         elif on_dev:
             dev_in = [c.dev[:3] for c in chunks]
             for c in chunks:
@@ -516,8 +546,6 @@ class Predictor:
         else:
             dev_in = [self._to_device(c, lo, hi, cs) for c in chunks]
             cur.wait_stream(cs)
-        # (dev_in stays referenced by the ticket: its tensors were allocated on the copy stream and must not return to that
-        # stream's pool while other streams read them - and the deferred float64 pass reads the bases until the post-pass has run)
         tagged = self._tag_chunks(chunks, on_dev) if self._tags is not None else None      # --bam_tags: the view the outputs select from
         if plans is None:
             outs = [self.model.classify_bytes(a, o, l, self.len, want_labels=not self.is_paired) for a, o, l in dev_in]
@@ -542,40 +570,36 @@ class Predictor:
                     if plans is not None:            # the pass read the read-level tables: a read of several windows gets its fused logits back
                         self.model.window_fuse(plans[k], self._windows["fuse"], logits=outs[k][0], labels=outs[k][1],
                                                want_labels=outs[k][1] is not None, only_multi=True)
-            if self.is_paired:
-                labels = module_arch.pair_fuse(outs[0][0], outs[1][0], self.args.ensure)
-            else:
-                labels = outs[0][1].view(torch.int8)
-            host = None if self.gathers_labels else _pinned(labels)
-            pieces = self._select_chunk(chunks, dev_in, labels, lo, hi, on_dev, pairs, tagged)
+            labels = module_arch.pair_fuse(outs[0][0], outs[1][0], self.args.ensure) if self.is_paired else outs[0][1].view(torch.int8)
+            tk.labels, tk.host = labels, None if self.gathers_labels else _pinned(labels)
+            tk.pieces = self._select_chunk(chunks, dev_in, labels, lo, hi, on_dev, ring, pairs, tagged)
             if self._report is not None:
-                pieces[REPORT] = self._report_chunk(chunks, dev_in, outs, labels, lo, hi, pairs)
-            regions = None
+                tk.pieces[REPORT] = self._report_chunk(chunks, dev_in, outs, labels, lo, hi, ring, pairs)
             if self._regions:
-                regions = self._regions_chunk(chunks, dev_in, plans, lo, hi, pairs)
-                pieces[REGIONS] = [regions["piece"]]
-            sum_info = None
-            if self._summary is not None:           # --summary: this rank's units of the chunk, counted where they are (rd_summary_accumulate)
-                sum_info = _pinned(self._summary.add(dev_in[0], outs[0][0], dev_in[1] if self.is_paired else None,
-                                                     outs[1][0] if self.is_paired else None, labels.view(torch.int8)))
-            grp_info, keep_raw = None, None
+                piece, reg = self._regions_chunk(chunks, dev_in, plans, lo, hi, pairs, ring=ring)
+                tk.pieces[REGIONS] = [piece]
+                tk.checks["regions"] = functools.partial(self._finish_regions, tk.pieces, reg)
+            if self._summary is not None:          # --summary: this rank's units of the chunk, counted where they are (rd_summary_accumulate)
+                info = _pinned(self._summary.add(dev_in[0], outs[0][0], dev_in[1] if self.is_paired else None,
+                                                 outs[1][0] if self.is_paired else None, labels.view(torch.int8)))
+                tk.checks["summary"] = functools.partial(self._check_counted, "summary: the chunk's sequence tables or labels", info)
             if self._groups is not None:            # --read_groups: the same units per read group, over the chunks' raw records
-                grp_info = _pinned(self._groups.add(chunks, labels.view(torch.int8), self.interleaved))
-                keep_raw = [c.raw for c in chunks]
-            finish = None
+                info = _pinned(self._groups.add(chunks, labels.view(torch.int8), self.interleaved))
+                tk.checks["groups"] = functools.partial(self._check_counted, "read groups: the chunk's labels or group rows", info)
             if self.gathers_labels:                 # label gather (1 B per read) queued behind the kernels, collected later
-                _, finish = rdist.gather_labels(labels, n, dst=0, bounds=bounds, async_op=True)
-            done = _native_mod.new_event()
-            done.record(post)
-        return {"n": n, "bounds": bounds, "labels": labels, "host": host, "finish": finish, "done": done, "keep": (dev_in, outs, plans),
-                "pieces": pieces, "pairs": pairs, "chunk": chunks[0], "totals": [t for c in chunks for t in (c.total, c.raw_total) if t is not None] if on_dev else (), "summary": sum_info,
-                "regions": regions, "groups": grp_info, "keep_raw": keep_raw, "tagged": tagged}
+                _, tk.finish = rdist.gather_labels(labels, n, dst=0, bounds=bounds, async_op=True)
+            tk.done = _native_mod.new_event()
+            tk.done.record(post)
+        # what the ticket only keeps alive: the tensors of dev_in (of pairs, of the tagged views; --read_groups: the raw views) were
+        # allocated on the copy stream and must not return to that stream's pool while other streams read them - and the deferred
+        # float64 pass reads the bases until the post-pass has run
+        tk.keep = (dev_in, outs, plans, pairs, tagged, [c.raw for c in chunks] if self._groups is not None else None)
+        return tk
 
     def _tag_chunks(self, chunks, on_dev):
         """--bam_tags: [(tagged text, its record table)] of every input's chunk (bamtags.DeviceBamTags.splice), made on the COPY stream
         behind the chunk's `ready` event - not behind the recurrences of the chunk before, which fill the main stream. The host waits
-        there for the call's verdict and sizes (a chunk that did not fit its hint is spliced again), as it waits for the window plans.
-        The ticket keeps the views: they were allocated on the copy stream and are read on the post stream."""
+        there for the call's verdict and sizes (a chunk that did not fit its hint is spliced again), as it waits for the window plans."""
         if not on_dev:
             raise RuntimeError("--bam_tags: the chunk's text is not on the device (BAM input is device ingest only)")
         out = []
@@ -583,13 +607,12 @@ class Predictor:
             for c, tg in zip(chunks, self._tags):
                 self._copy_stream.wait_event(c.ready)
                 _native_mod.wait_event(c.ready)
-                if any(t is not None and int(t[0]) < 0 for t in (c.total, c.raw_total)):
-                    raise RuntimeError("device chunk assembly failed (rd_fastq_gather)")
+                self._check_totals((c.total, c.raw_total))     # (here already: the splice reads the views before collect_chunk runs)
                 text, out_start, _ = tg.splice(c)
                 out.append((text, out_start))
         return out
 
-    def _select_chunk(self, chunks, dev_in, labels, lo, hi, on_dev, pairs=None, tagged=None):
+    def _select_chunk(self, chunks, dev_in, labels, lo, hi, on_dev, ring, pairs=None, tagged=None):
         """{(mate, label): [Piece]}: the label files whose records of this chunk are selected on the device, on the post stream beside
         the next chunk's recurrences, so that only the selected bytes travel to the host. A chunk whose text lives on the device: every
         file's, deflated (.gz outputs: BGZF members, csrc/rd_deflate.hpp) or packed into one text (rd_select_pack). Otherwise the .gz
@@ -601,37 +624,22 @@ class Predictor:
             files = self._gz_files
         else:
             return {}
-        ring = self._gz_seq % self.GZ_RING
-        self._gz_seq += 1
         # (own writer: half of the worst-case output size is reserved - an incompressible chunk falls back to the host's deflate; under
         # the label gather the full bound, every rank must take the same path; a chunk on the device has no host text to fall back to)
         frac = 1.0 if on_dev or self.gathers_labels else 0.5
         pieces = {}
         views = {}                                  # mate -> (text, record table, labels) that select the records of its files
         for e, lab in files:
-            if e not in views:
+            if e not in views:                      # the source is chosen once per chunk and mate; record_view knows the layouts
+                f, pair_table = e if pairs is None else 0, None
                 if self.bam_output:                 # the records as they stand in the input (DeviceChunk.raw), selected like the text's
-                    raw, raw_start = chunks[e if pairs is None else 0].raw
-                    if pairs is None:
-                        views[e] = (raw, raw_start, labels.view(torch.int8))
-                    elif len(self.output) == 1:     # pair k = raw records 2 k and 2 k + 1
-                        views[e] = (raw, raw_start[0:2 * (hi - lo) + 1:2].contiguous(), labels.view(torch.int8))
-                    else:
-                        views[e] = (raw, raw_start, self._pairs.expand(labels.view(torch.int8), e, slot=pairs["ring"]))
+                    source = chunks[f].raw
                 elif tagged is not None:            # --bam_tags: the text with the tags behind the read names, selected like the text
-                    ttext, tstart = tagged[e if pairs is None else 0]
-                    if pairs is None:
-                        views[e] = (ttext, tstart, labels.view(torch.int8))
-                    elif len(self.output) == 1:     # pair k = tagged records 2 k and 2 k + 1
-                        views[e] = (ttext, tstart[0:2 * (hi - lo) + 1:2].contiguous(), labels.view(torch.int8))
-                    else:
-                        views[e] = (ttext, tstart, self._pairs.expand(labels.view(torch.int8), e, slot=pairs["ring"]))
-                elif pairs is None:
-                    views[e] = self._device_text(chunks[e], dev_in[e][0], lo, hi) + (labels.view(torch.int8),)
-                elif len(self.output) == 1:         # interleaved output: the pairs are the records
-                    views[e] = (pairs["text"], pairs["pair_start"], labels.view(torch.int8))
-                else:                               # split output: mate e's records of the full table (the other mate's: RD_LABEL_SKIP)
-                    views[e] = (pairs["text"], pairs["rec_start"], self._pairs.expand(labels.view(torch.int8), e, slot=pairs["ring"]))
+                    source = tagged[f]
+                else:
+                    source, pair_table = self._fastq_view(chunks, dev_in, e, lo, hi, pairs)
+                views[e] = record_view(source, hi - lo, labels.view(torch.int8), e, pairs is not None, len(self.output), pair_table,
+                                       None if pairs is None else functools.partial(self._pairs.expand, slot=ring))
             text, rs, sel = views[e]
             gz = (e, lab) in self._gz_files
             if gz:
@@ -642,15 +650,15 @@ class Predictor:
             pieces[(e, lab)] = [Piece(out, info, not gz, info, "gzip" if gz else "select")]
         return pieces
 
-    def _report_chunk(self, chunks, dev_in, outs, labels, lo, hi, pairs=None):
+    def _report_chunk(self, chunks, dev_in, outs, labels, lo, hi, ring, pairs=None):
         """--read_report: the pieces of the lines of records [lo, hi) of the chunk, formatted where mate 1's text, its record starts
         and the final logits already are (rd_report_format, on the post stream after the float64 pass and the pair fusion), then
         deflated there too for a .gz report (its line starts are a record table of the report text: rd_gz_compress_selected of all of
-        it; members that do not fit the reserved half fall back to the text, which the host deflates). Own ring of buffers: the label
-        files' slots are not shared."""
-        ring = self._rep_seq % self.GZ_RING
-        self._rep_seq += 1
-        text, rs = self._device_text(chunks[0], dev_in[0][0], lo, hi) if pairs is None else (pairs["text"], pairs["pair_start"])
+        it; members that do not fit the reserved half fall back to the text, which the host deflates). Own buffers in the chunk's ring
+        slot: the label files' are not shared."""
+        source, pair_table = self._fastq_view(chunks, dev_in, 0, lo, hi, pairs)
+        # (a line per unit: mate 1's records, or the pairs of an interleaved chunk as its records - whatever the outputs are)
+        text, rs, _ = record_view(source, hi - lo, labels, 0, pairs is not None, 1, pair_table)
         rep, line_start, info = self._report.format(text, rs, outs[0][0], outs[1][0] if self.is_paired else None, labels.view(torch.int8), slot=ring)
         fault = _pinned(info)
         piece = Piece(rep, fault, True, fault, "report")
@@ -660,27 +668,27 @@ class Predictor:
             piece = Piece(out, _pinned(ginfo), False, fault, "report", fallback=piece)
         return [piece]
 
-    def _regions_chunk(self, chunks, dev_in, plans, lo, hi, pairs=None, need=None):
+    def _regions_chunk(self, chunks, dev_in, plans, lo, hi, pairs=None, ring=None, need=None):
         """--regions: the piece of the region lines of units [lo, hi) of the chunk, formatted where the records' text, the reads'
         lengths, the window plans and the windows' final logits already are (rd_region_format, on the post stream after the float64
-        pass). Own ring of buffers. The lines have no bound in the text's bytes, so a hint sizes the buffer (RD_REGIONS_HINT, else
-        regions.default_hint) and _finish_regions formats the chunk again - need = the bytes the first call asked for - when it was too
-        small. A .gz file: the text goes to the host's writer, which deflates it."""
-        if pairs is None:
-            tabs = [self._device_text(chunks[e], dev_in[e][0], lo, hi) for e in range(len(dev_in))]
-            stride = 1
-        else:                                       # one text, one record table: mate 2's records are the odd entries
-            tabs, stride = [(pairs["text"], pairs["rec_start"]), (pairs["text"], pairs["rec_start"][1:])], 2
+        pass), and the RegionRepeat that _finish_regions reads. Own buffer in the chunk's ring slot. The lines have no bound in the
+        text's bytes, so a hint sizes the buffer (RD_REGIONS_HINT, else regions.default_hint) and _finish_regions formats the chunk
+        again - need = the bytes the first call asked for, no ring slot: a buffer of its own - when it was too small. A .gz file: the
+        text goes to the host's writer, which deflates it."""
+        # The sources are record_view's, its answer is not: rd_region_format selects nothing by label, it walks every record of a mate. An
+        # interleaved chunk's mate has the full table from entry e on, read with a stride of 2 - record_view skips the other mate by label.
+        tabs = [self._fastq_view(chunks, dev_in, e, lo, hi, pairs)[0] for e in range(len(dev_in))]
+        stride = 1 if pairs is None else 2
+        if pairs is not None:
+            tabs[1] = (tabs[1][0], tabs[1][1][1:])
         args = []
         for (text, rs), (_, _, ln), plan in zip(tabs, dev_in, plans):
             args += [text, rs, ln, plan]
         if need is None:
-            ring = self._reg_seq % self.GZ_RING
-            self._reg_seq += 1
             text_bytes = sum(int(t.numel()) for t, _ in tabs[:1 if stride == 2 else 2])
             cap = _regmod.default_hint(text_bytes, hi - lo, sum(p["total"] for p in plans), len(plans))
         else:
-            ring, cap = None, int(need)
+            cap = int(need)
         buf = self._reg_out.get(ring)
         if buf is None or buf.numel() < cap:
             buf = torch.empty(((cap * 5 // 4 + 255) // 256) * 256, dtype=torch.uint8, device=self.device)
@@ -689,69 +697,57 @@ class Predictor:
         # (a hint from the environment is taken at its word, also where the ring's buffer has grown beyond it)
         out, info = self.model.window_regions(*args, rec_stride=stride, out=buf, out_cap=cap if os.environ.get(_regmod.HINT_ENV) and need is None else None)
         info = _pinned(info)
-        return {"piece": Piece(out, info, True, info, "regions"), "info": info, "again": (chunks, dev_in, plans, lo, hi, pairs)}
+        return Piece(out, info, True, info, "regions"), RegionRepeat(info, chunks, dev_in, plans, lo, hi, pairs)
 
-    def _finish_regions(self, tk):
-        """the verdict of rd_region_format on this rank's units of a chunk, once the event behind it has passed: the counters are added
-        up; lines that did not fit (fault 1) are formatted once more with the bytes they need, before the piece is handed on"""
-        reg = tk.get("regions")
-        if reg is None:
-            return
-        info = reg["info"]
+    def _finish_regions(self, pieces, reg):
+        """the verdict of rd_region_format on this rank's units of a chunk (the ticket's "regions" check), once the event behind it has
+        passed: the counters are added up; lines that did not fit (fault 1) are formatted once more with the bytes they need, and
+        their piece replaces the first one among the ticket's pieces before they are handed to the writer or the gather"""
+        info = reg.info
         if int(info[3]) == 1:
             self.regions_repeats += 1
             post = self._post_stream
             with torch.cuda.stream(post):
-                reg = self._regions_chunk(*reg["again"], need=int(info[1]))
+                piece, reg = self._regions_chunk(reg.chunks, reg.dev_in, reg.plans, reg.lo, reg.hi, reg.pairs, need=int(info[1]))
                 done = _native_mod.new_event()
                 done.record(post)
             _native_mod.wait_event(done)
-            info = reg["info"]
-            tk["regions"], tk["pieces"][REGIONS] = reg, [reg["piece"]]
+            info, pieces[REGIONS] = reg.info, [piece]
         if int(info[3]):
             raise RuntimeError("device regions: the chunk's record tables, lengths or window plans do not describe its text (fault %d)" % int(info[3]))
         for k in range(4):
             self._reg_counts[k] += int(info[4 + k])
-        tk["regions"] = None                        # (the tables of the chunk are no longer needed)
 
     def collect_chunk(self, tk):
-        """Labels of a submitted chunk: int8 numpy on rank 0 (whole chunk, input order), None elsewhere."""
-        if self.gathers_labels:
-            if tk["pairs"] is not None or tk["summary"] is not None or tk["regions"] is not None or tk.get("groups") is not None:     # every rank checks the mates, the counters and the regions of its own shard
-                _native_mod.wait_event(tk["done"])
-            if tk["pairs"] is not None:
-                self._check_pairs(tk["chunk"], tk["pairs"])
-            self._check_summary(tk)
-            self._finish_regions(tk)
-            labels = tk["finish"]()
-            if tk["pieces"]:
-                self._gather_pieces(tk)
-            return None if self.rank != 0 else labels.cpu().numpy()
-        _native_mod.wait_event(tk["done"])         # (a blocking event: the thread sleeps in the driver, it does not spin a host core)
-        for t in tk.get("totals", ()):
-            if int(t[0]) < 0:
-                raise RuntimeError("device chunk assembly failed (rd_fastq_gather)")
-        if tk["pairs"] is not None:
-            self._check_pairs(tk["chunk"], tk["pairs"])
-        self._check_summary(tk)
-        self._finish_regions(tk)
-        return tk["host"].numpy()
+        """Labels of a submitted chunk: int8 numpy on rank 0 (whole chunk, input order), None elsewhere. The host waits for the chunk's
+        `done` event (the label gather of a chunk without checks: in the collectives alone), then every rank runs its shard's checks."""
+        if tk.checks or not self.gathers_labels:
+            _native_mod.wait_event(tk.done)        # (a blocking event: the thread sleeps in the driver, it does not spin a host core)
+        tk.run_checks()
+        if not self.gathers_labels:
+            return tk.host.numpy()
+        labels = tk.finish()
+        if tk.pieces:
+            self._gather_pieces(tk)
+        return None if self.rank != 0 else labels.cpu().numpy()
 
     @staticmethod
-    def _check_summary(tk):
-        """the verdict of rd_summary_accumulate on this rank's units of a chunk, once the event behind it has passed"""
-        if tk["summary"] is not None and int(tk["summary"][0]):
-            raise RuntimeError("device summary: the chunk's sequence tables or labels are not what the counters can take (fault %d); "
-                               "nothing of the chunk was counted" % int(tk["summary"][0]))
-        if tk.get("groups") is not None and int(tk["groups"][0]):
-            raise RuntimeError("device read groups: the chunk's labels or group rows are not what the counters can take (fault %d); "
-                               "nothing of the chunk was counted" % int(tk["groups"][0]))
+    def _check_totals(totals):
+        """the verdict of rd_fastq_gather on a device chunk's views (pinned totals; None: no such view), once its `ready` event has passed"""
+        if any(t is not None and int(t[0]) < 0 for t in totals):
+            raise RuntimeError("device chunk assembly failed (rd_fastq_gather)")
+
+    @staticmethod
+    def _check_counted(what, info):
+        """the verdict of rd_summary_accumulate / rd_bam_group_accumulate on this rank's units of a chunk, once the event behind it passed"""
+        if int(info[0]):
+            raise RuntimeError("device %s are not what the counters can take (fault %d); nothing of the chunk was counted" % (what, int(info[0])))
 
     def _gather_pieces(self, tk):
         """label gather: the pieces every rank made of its shard travel to rank 0, which appends them in rank order = input order
         (sizes first: one small all-gather per chunk; then one padded gather per output file)"""
-        _native_mod.wait_event(tk["done"])
-        pieces = tk["pieces"]
+        _native_mod.wait_event(tk.done)
+        pieces = tk.pieces
         own = [(key, pieces[key][0]) for key in pieces]
         mine = [p.size() for _, p in own]
         sizes = rdist.all_gather_sizes(mine)
@@ -906,7 +902,8 @@ class Predictor:
 
     def _writer_items(self, chunks, labels):
         """what every writer thread gets of a chunk: (chunk, labels) whose records of one label are its files' - what the host writes
-        itself (fh.write_selected: plain outputs of host-parsed chunks, device pieces that did not fit)"""
+        itself (fh.write_selected: plain outputs of host-parsed chunks, device pieces that did not fit). The layouts are record_view's,
+        over chunks instead of tables: fx.pair_view and fx.expand_pair_labels are the host's forms of its two interleaved answers."""
         if not self.interleaved:
             return [(chunks[e], labels) for e in range(len(self.output))]
         c = chunks[0]
@@ -963,7 +960,7 @@ class Predictor:
                     break
                 self._mark("labels")
                 self._stage_s["classify"] += time.perf_counter() - t0
-                counts[0] += tk["n"]
+                counts[0] += tk.n
                 if self._first_chunk is None:
                     self._first_chunk = (time.perf_counter(), counts[0])
                 if writes:
@@ -973,7 +970,7 @@ class Predictor:
                         counts[i] += int((labels == lab).sum())
                     t0 = time.perf_counter()
                     for w, (c, lab) in zip(writers, self._writer_items(chunks, labels)):
-                        w.q.put((c, lab, tk["pieces"]))
+                        w.q.put((c, lab, tk.pieces))
                     self._stage_s["wait_writer"] += time.perf_counter() - t0
                     if self.rank == 0:
                         self.logger.info('{}{}{} sequences finished!'.format(colors.OKGREEN, counts[0], colors.ENDC))
@@ -1012,35 +1009,34 @@ class Predictor:
             if self.is_paired and self.args.ensure == 'both':
                 self.logger.info('Discarded {}{}{}{} unclassified sequences'.format(
                     colors.BOLD, colors.OKCYAN, self.num_unknown, colors.ENDC))
+        # The counters of every rank's own share, summed over the ranks (_sum_ranks). Which flag says that the shares differ: BAM records
+        # and tags are counted where the file is framed, and BAM input under several ranks is the sharded parse only (--bam_shard;
+        # check_bam) - sharded_parse. Windows and regions are counted where units are classified: both layouts of several ranks - multi.
         bam_in = [path for path in self.input if fx.get_seq_format(path) == "bam"]
         if bam_in:                                 # (one rank, or --bam_shard: every rank walked the records of its share)
-            mine = [[((self.ingest.get(os.path.basename(str(path))) or {}).get("indexer") or {}).get(k, 0) for k in ("bam_records", "bam_skipped")]
-                    for path in bam_in]
-            per_rank = self._all_gather(mine) if self.sharded_parse else [mine]
+            total = self._sum_ranks([((self.ingest.get(os.path.basename(str(path))) or {}).get("indexer") or {}).get(k, 0)
+                                     for path in bam_in for k in ("bam_records", "bam_skipped")], self.sharded_parse)
             for f, path in enumerate(bam_in):
                 if self.rank == 0:
-                    self.logger.info('BAM input: {} records, {} secondary/supplementary skipped ({})'.format(
-                        sum(r[f][0] for r in per_rank), sum(r[f][1] for r in per_rank), path))
+                    self.logger.info('BAM input: {} records, {} secondary/supplementary skipped ({})'.format(total[2 * f], total[2 * f + 1], path))
         if self._tags is not None:                 # --bam_tags: every rank tagged the records of its own share
-            mine = _tagmod.as_vector([t.counts() for t in self._tags], len(self.bam_tags)).tolist()
-            per_rank = self._all_gather(mine) if self.sharded_parse else [mine]
-            total = [sum(int(r[k]) for r in per_rank) for k in range(len(mine))]
+            total = self._sum_ranks(_tagmod.as_vector([t.counts() for t in self._tags], len(self.bam_tags)).tolist(), self.sharded_parse)
             self._tag_total = _tagmod.from_vector(total, len(self.bam_tags), len(self._tags))
             if self.rank == 0:
                 self.logger.info(_tagmod.log_line(self.bam_tags, self._tag_total))
         if self.interleaved:
             fx.check_even_records(self._records_seen)
+        mates = range(2 if self.is_paired else 1)
         if self._windows is not None:              # every rank classified the windows of its own shard / byte range
-            per_rank = self._all_gather(self._win_classified) if self.multi else [self._win_classified]
-            self._win_total = [sum(int(r[e]) for r in per_rank) for e in range(2 if self.is_paired else 1)]
+            total = self._sum_ranks(self._win_classified, self.multi)
+            self._win_total = [total[e] for e in mates]
             if self.rank == 0:
                 self.logger.info('Classified {}{}{}{} windows ({} mode, at most {} per read)'.format(
                     colors.BOLD, colors.OKCYAN, " + ".join(str(x) for x in self._win_total), colors.ENDC, self._windows["fuse"],
                     self._windows["max_per_read"]))
         if self._regions:                          # likewise: every rank formatted the regions of its own units
-            per_rank = self._all_gather(self._reg_counts) if self.multi else [self._reg_counts]
-            mates = range(2 if self.is_paired else 1)
-            self._reg_total = [[sum(int(r[k + e]) for r in per_rank) for e in mates] for k in (0, 2)]
+            total = self._sum_ranks(self._reg_counts, self.multi)
+            self._reg_total = [[total[k + e] for e in mates] for k in (0, 2)]
             if self.rank == 0:
                 self.logger.info('Wrote {}{}{}{} rRNA regions in {} reads'.format(
                     colors.BOLD, colors.OKCYAN, " + ".join(str(x) for x in self._reg_total[0]), colors.ENDC,
@@ -1064,7 +1060,7 @@ class Predictor:
         if units != [self.num_unknown, self.num_nonrrna, self.num_rrna]:
             raise RuntimeError("--summary: the device counted {} unclassified / non-rRNA / rRNA units, the run {}".format(
                 units, [self.num_unknown, self.num_nonrrna, self.num_rrna]))
-        path = self.args.summary
+        path = self.summary_path
         doc = _summod.to_json(acc, {"version": __version__, "paired": bool(self.is_paired), "interleaved": self.interleaved, "len": int(self.len),
                                     "ensure": self.args.ensure, "model": self.state_key, "inputs": list(self.input),
                                     "windows": None if self._windows is None else dict(
@@ -1096,6 +1092,12 @@ class Predictor:
         out = [None] * self.world
         dist.all_gather_object(out, obj)
         return out
+
+    def _sum_ranks(self, mine, shares):
+        """a list of integers, one list per rank -> their sums per column; shares: do the ranks hold different shares (a collective
+        that every rank calls) - else this rank's list is the whole run's"""
+        per_rank = self._all_gather(mine) if shares else [mine]
+        return [sum(int(r[k]) for r in per_rank) for k in range(len(mine))]
 
     def _plan_ranks(self):
         """How the ranks share the input - the run's layout (module docstring): sets sharded_parse and, under it, this rank's share of
@@ -1197,14 +1199,13 @@ class Predictor:
             unclf = [unclassified_path(path, self.bam_output) for path in self.output]
             open_(-1, unclf)
             log('Writing unclassified sequences into file: {}{}{}'.format(colors.OKYELLOW, ", ".join(unclf), colors.ENDC))
-        rep_path = getattr(self.args, 'read_report', None)
+        rep_path, reg_path = self.report_path, self.regions_path
         if rep_path:
             log('Writing per-read report into file: {}{}{}'.format(colors.OKBLUE, rep_path, colors.ENDC))
             open_(REPORT[1], [rep_path])
             if self.rank == 0:                 # (the sharded parse: rank 0's part comes first in the joined file)
                 hdr = np.frombuffer(_gzmod.REPORT_HEADER_PE if self.is_paired else _gzmod.REPORT_HEADER_SE, dtype=np.uint8)
                 files[-1][2].write_text(hdr.ctypes.data, hdr.size)
-        reg_path = getattr(self.args, 'regions', None)
         if reg_path:
             log('Writing rRNA regions into file: {}{}{}'.format(colors.OKBLUE, reg_path, colors.ENDC))
             open_(REGIONS[1], [reg_path])
@@ -1217,39 +1218,39 @@ class Predictor:
         """what the GPU makes of the outputs: which (mate, label) files it deflates or packs, and the --read_report's lines"""
         # which (mate, label) files are gzip outputs deflated on the device: every rank deflates the records it classified - and writes
         # them itself (one rank, or the sharded parse) or, under the label gather, sends the members to rank 0
-        self._gz_files, self._gz_seq = [], 0
+        self._gz_files = []
+        self._chunk_seq = 0                        # chunks submitted (submit_chunk): chunk k's buffers are those of ring slot k % GZ_RING
         if self.gzip_on_device:                    # (the same list on every rank: it is derived from the arguments)
             self._gz_files = self.gz_output_files(self.output, self.rrna, self.is_paired, self.args.ensure)
         # every (mate, label) file this run writes; for chunks on the device the plain ones are packed there (rd_select_pack)
         self._out_files = out_files
         if any(self._device_parse(p) for p in self.input):
             self._sel = _gzmod.DeviceSelect(self.device)
-        self._pairs, self._pair_seq = (_gzmod.DevicePairSplit(self.device) if self.interleaved else None), 0
+        self._pairs = _gzmod.DevicePairSplit(self.device) if self.interleaved else None
         # --read_report: one line per read (pair), formatted on the device for every chunk; mate 1's writer appends the pieces
-        rep_path = getattr(self.args, 'read_report', None)
+        rep_path = self.report_path
         self._report = _gzmod.DeviceReport(self.device) if rep_path else None
         self._rep_gz = bool(rep_path) and self.gzip_on_device and rep_path.endswith('gz')      # (else the host's writer deflates a .gz report)
-        self._rep_seq = 0
         # --summary: the run's QC counters, one int64 array per rank that every chunk adds to on the post stream
-        self._summary = _summod.DeviceSummary(self.device) if getattr(self.args, 'summary', None) else None
+        self._summary = _summod.DeviceSummary(self.device) if self.summary_path else None
         # --read_groups: the same units per read group of mate 1's BAM, one more int64 array that every chunk adds to
         self._groups = _grpmod.DeviceGroups(self.device, _bammod.header(self.input[0])) if self.read_groups else None
         # --bam_tags: the tagged view of every chunk, and the counters of the tags copied, per input file
         self._tags = [_tagmod.DeviceBamTags(self.device, self.bam_tags) for _ in self.input] if self.bam_tags is not None else None
         self._win_classified = [0, 0]
         # --regions: the lines of every chunk, formatted on the device; mate 1's writer appends the pieces (and deflates a .gz file)
-        self._regions = bool(getattr(self.args, 'regions', None))
-        self._reg_out, self._reg_seq, self._reg_counts, self.regions_repeats = {}, 0, [0, 0, 0, 0], 0
+        self._regions = bool(self.regions_path)
+        self._reg_out, self._reg_counts, self.regions_repeats = {}, [0, 0, 0, 0], 0
         if self._gz_files or self._rep_gz:
             self._gz = _gzmod.DeviceGzip(self.device)
 
     def _in_flight(self, stream):
         """chunk k+1 is submitted (its H2D starts) before the labels of chunk k are waited for"""
         prev = None
-        for chunks in stream:
+        for seq, chunks in enumerate(stream):
             t0 = time.perf_counter()
             self._mark("chunk_of_%d_read" % len(chunks[0].seq_len), t0)    # (the first chunks' way through the pipeline)
-            tk = self.submit_chunk(chunks)
+            tk = self.submit_chunk(chunks, seq)
             self._mark("submitted")
             self._stage_s["classify"] += time.perf_counter() - t0
             if prev is not None:
@@ -1326,15 +1327,13 @@ class Predictor:
         except RuntimeError as e:
             self.logger.error('{}{}{}'.format(colors.FAIL, _COUNT_ERRORS.get(str(e), str(e)), colors.ENDC))
             raise
-        check_read_report(self.args.read_report if hasattr(self.args, 'read_report') else None, self.output, self.rrna, self.is_paired,
-                          self.args.ensure, self.bam_output)
-        check_summary(getattr(self.args, 'summary', None), self.output, self.rrna, self.is_paired, self.args.ensure,
-                      getattr(self.args, 'read_report', None), self.bam_output)
-        check_read_groups(self.read_groups, getattr(self.args, 'summary', None), self.input, self.bam_shard)
-        check_bam_tags(getattr(self.args, 'bam_tags', None), self.input, self.bam_output)
+        check_read_report(self.report_path, self.output, self.rrna, self.is_paired, self.args.ensure, self.bam_output)
+        check_summary(self.summary_path, self.output, self.rrna, self.is_paired, self.args.ensure, self.report_path, self.bam_output)
+        check_read_groups(self.read_groups, self.summary_path, self.input, self.bam_shard)
+        check_bam_tags(self.bam_tags_arg, self.input, self.bam_output)
         self._windows = check_windows(self.args)
-        check_regions(getattr(self.args, 'regions', None), self._windows is not None, self.output, self.rrna, self.is_paired, self.args.ensure,
-                      getattr(self.args, 'read_report', None), getattr(self.args, 'summary', None), self.bam_output)
+        check_regions(self.regions_path, self._windows is not None, self.output, self.rrna, self.is_paired, self.args.ensure,
+                      self.report_path, self.summary_path, self.bam_output)
         # reference batch-size heuristic (detect.py:558-568); kept because --chunk_size is expressed in these batches
         denom = (2 * self.len * 6.4) if self.is_paired else (self.len * 6.4)
         self.batch_size = 2 ** math.floor(math.log2(((self.args.memory - 2) * 1024 * 1024) / denom))
@@ -1662,11 +1661,10 @@ def main(argv=None, log_level=None):
     config_file = os.path.join(cd, 'config.json') if args.config is None else args.config
     config = ConfigParser.from_json(config_file)
     check_windows(args)                          # (before the model is loaded: nothing has touched a device yet)
-    check_regions(getattr(args, 'regions', None), getattr(args, 'windows', False))
-    check_bam(args.input, args.output, args.rrna, getattr(args, 'bam_output', False), getattr(args, 'bam_shard', False),
-              getattr(args, 'interleaved', False))
-    check_read_groups(getattr(args, 'read_groups', False), getattr(args, 'summary', None), args.input, getattr(args, 'bam_shard', False))
-    check_bam_tags(getattr(args, 'bam_tags', None), args.input, getattr(args, 'bam_output', False))
+    check_regions(args.regions, args.windows)    # (args is the parser's own Namespace: every option is there)
+    check_bam(args.input, args.output, args.rrna, args.bam_output, args.bam_shard, args.interleaved)
+    check_read_groups(args.read_groups, args.summary, args.input, args.bam_shard)
+    check_bam_tags(args.bam_tags, args.input, args.bam_output)
     seq_pred = Predictor(config, args, log_level=log_level)
     try:
         t0 = time.perf_counter()
