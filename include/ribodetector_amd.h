@@ -511,6 +511,24 @@ RD_API int rd_bam_tag_splice(const uint8_t *text, int64_t text_bytes, const int6
                              const int64_t *raw_start, int64_t n_rec, const uint8_t *tags, int32_t n_tags, uint8_t *out, size_t out_cap,
                              int64_t *out_start, int64_t *info, void *workspace, size_t workspace_bytes, void *stream);
 
+/* rd_bam_tag_splice with flags (the CLI's --bam_tag_floats): rd_bam_tag_splice is this call with flags = 0. A flag bit that is not
+ * listed here is RD_E_INVALID (nothing is launched). RD_BAM_TAGS_FLOATS: a listed tag of type f becomes 'TG:f:text', a B array with
+ * subtype f 'TG:B:f' and ',text' per element (none: 'TG:B:f' alone), text = the value as rd_float_text writes it; such a tag counts as
+ * copied (info[8 + j]) and info[5] is 0. An f value whose length is not 4 makes the record malformed, as for the integer types. info
+ * keeps its layout, the workspace is that of rd_bam_tag_splice_workspace_bytes, and text_bytes + 5 raw_bytes still holds the tagged
+ * text (an element of 4 bytes prints as at most 13).
+ * rd_float_text: the float32 values with the bit patterns bits [dev] uint32[n] as text, the rule of ribodetector_amd/bam.py (float_g):
+ * what printf("%g", (double)v) prints - the EXACT value m 2^e rounded to 6 significant decimal digits, ties to even, in fixed form when
+ * the decimal exponent after rounding is in -4..5, else d.ddddde+XX, trailing zeros removed; inf, nan, 0; '-' in front when the sign bit
+ * is set (-0, -inf and -nan included). Value k: text [dev, 16-byte aligned] uint8[16 n] bytes [16 k, 16 k + len[k]), the slot of 16 bytes
+ * written whole by one store (zero behind the text); len [dev] uint8[n], 1..12. Integer arithmetic throughout, no double (csrc/
+ * rd_float_text.hpp). n == 0: a no-op; a null pointer: RD_E_INVALID. Asynchronous on `stream`. */
+#define RD_BAM_TAGS_FLOATS 1u
+RD_API int rd_bam_tag_splice_ex(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const uint8_t *raw, int64_t raw_bytes,
+                                const int64_t *raw_start, int64_t n_rec, const uint8_t *tags, int32_t n_tags, uint8_t *out, size_t out_cap,
+                                int64_t *out_start, int64_t *info, void *workspace, size_t workspace_bytes, uint32_t flags, void *stream);
+RD_API int rd_float_text(const uint32_t *bits, int64_t n, uint8_t *text, uint8_t *len, void *stream);
+
 /* Reads longer than max_len classified over WINDOWS of max_len bases (CLI extension `--windows`; the reference classifies read[:max_len],
  * reference detect.py:666-726, and that stays the rule without the flag). A window is one more (seq_off, seq_len) entry over the same
  * text, so rd_classify takes the window table as it takes a read table and its kernels do not change.

@@ -31,7 +31,7 @@ SYMBOLS = [
     "rd_pair_split", "rd_pair_expand_labels",
     "rd_summary_words", "rd_summary_accumulate",
     "rd_bam_tag_find", "rd_bam_group_rows", "rd_bam_group_accumulate",
-    "rd_bam_tag_splice_workspace_bytes", "rd_bam_tag_splice",
+    "rd_bam_tag_splice_workspace_bytes", "rd_bam_tag_splice", "rd_bam_tag_splice_ex", "rd_float_text",
     "rd_window_workspace_bytes", "rd_window_plan", "rd_window_fill", "rd_window_fuse",
     "rd_region_workspace_bytes", "rd_region_format",
 ]
@@ -42,7 +42,9 @@ BAM_RECORD, BAM_TRUNCATED = 6, 7      # RD_BAM_RECORD / RD_BAM_TRUNCATED: the tw
 WINDOW_FUSE = {"mean": 0, "max": 1}     # RD_WINDOW_MEAN / RD_WINDOW_MAX_D
 GROUPS_MAX = 65536      # RD_GROUPS_MAX: the most read groups a dictionary of rd_bam_group_rows holds
 BAM_TAGS_MAX = 16       # RD_BAM_TAGS_MAX: the most tags rd_bam_tag_splice copies into the header lines
-LABEL_SKIP = 2          # include/ribodetector_amd.h RD_LABEL_SKIP: the record label that no output file selects
+BAM_TAGS_FLOATS = 1     # RD_BAM_TAGS_FLOATS: the flag of rd_bam_tag_splice_ex that formats f and B:f values
+FLOAT_TEXT_SLOT = 16    # bytes per value in the text rd_float_text writes
+LABEL_SKIP = 2         # include/ribodetector_amd.h RD_LABEL_SKIP: the record label that no output file selects
 
 
 class RdWeights(C.Structure):
@@ -146,6 +148,8 @@ def lib():
     L.rd_bam_tag_splice_workspace_bytes.argtypes = [i64, i32]
     L.rd_bam_tag_splice_workspace_bytes.restype = sz
     L.rd_bam_tag_splice.argtypes = [vp, i64, vp, vp, i64, vp, i64, C.c_char_p, i32, vp, sz, vp, vp, vp, sz, vp]
+    L.rd_bam_tag_splice_ex.argtypes = [vp, i64, vp, vp, i64, vp, i64, C.c_char_p, i32, vp, sz, vp, vp, vp, sz, C.c_uint32, vp]
+    L.rd_float_text.argtypes = [vp, i64, vp, vp, vp]
     L.rd_window_workspace_bytes.argtypes = [i64]
     L.rd_window_workspace_bytes.restype = sz
     L.rd_window_plan.argtypes = [vp, i64, i32, i64, i32, vp, vp, vp, sz, vp]

@@ -33,7 +33,9 @@ per-group counters a record is counted in.
 Tags in FASTQ header lines (detect.py --bam_tags; device side csrc/rd_bam_tagtext.hpp, C ABI rd_bam_tag_splice): tag_comment says what
 a record's listed tags become behind its read name - '\\tTG:T:text' per tag, SAM's text form, as `samtools fastq -T` writes it - and
 fastq_text_tagged is fastq_text with that comment in front of the first newline of every record. Float-typed values (f, B:f) are left
-out and counted; a record whose listed tags cannot be walked, or hold a byte that would break a FASTQ header line, gets no comment.
+out and counted, or, with floats=True (--bam_tag_floats), written as float_g says: printf's %g, stated in whole numbers (device side
+csrc/rd_float_text.hpp, C ABI rd_float_text / rd_bam_tag_splice_ex). A record whose listed tags cannot be walked, or hold a byte that
+would break a FASTQ header line, gets no comment.
 """
 import struct
 import zlib
@@ -450,14 +452,61 @@ def parse_tag_list(text):
     return out
 
 
-def tag_comment(data, rec_off, tags):
+_P10 = [10 ** i for i in range(52)]      # (5 - X <= 50 for the smallest denormal, X - 5 <= 33 for the largest float)
+
+
+def float_g(bits):
+    """the text of the float32 with bit pattern `bits` (detect.py --bam_tag_floats; device side csrc/rd_float_text.hpp, C ABI
+    rd_float_text): what a C library's printf("%g", (double)v) prints, stated in whole numbers.
+    '-' in front when the sign bit is set (-0, -inf and -nan included). Infinity is 'inf', a NaN 'nan', zero '0'. Every other value,
+    denormals included, is the EXACT number m 2^e, rounded to 6 significant decimal digits, ties to the even digit (a tie needs an
+    exact half at the 7th digit: 100000.5, 1234565). X is the decimal exponent AFTER the rounding (999999.5 -> 1.00000 10^6: X = 6).
+    X < -4 or X >= 6: d.ddddde+XX / e-XX, the trailing zeros of the fraction removed and the point with them when none is left, the
+    exponent with at least two digits. Else fixed notation with 5 - X decimals, trailing zeros and then the point removed.
+    At most 12 bytes ('-1.17549e-38')."""
+    bits = int(bits) & 0xffffffff
+    sign = b"-" if bits >> 31 else b""
+    ef, mf = (bits >> 23) & 0xff, bits & 0x7fffff
+    if ef == 0xff:
+        return sign + (b"nan" if mf else b"inf")
+    if ef == 0 and mf == 0:
+        return sign + b"0"
+    m, e = (mf | 0x800000, ef - 150) if ef else (mf, -149)
+    num, den = (m << e, 1) if e >= 0 else (m, 1 << -e)            # the value = num / den
+    if num >= den:                                        # X = floor(log10 v)
+        X = len(str(num // den)) - 1
+    else:
+        X = -1
+        while num * _P10[-X] < den:
+            X -= 1
+    a, b = (num * _P10[5 - X], den) if X <= 5 else (num, den * _P10[X - 5])          # v 10^(5 - X) = a / b, in [10^5, 10^6)
+    n, r = divmod(a, b)
+    if 2 * r > b or (2 * r == b and n & 1):               # above the half, or the half itself and an odd last digit
+        n += 1
+    if n == 1000000:                                      # 999999.5 and above: the rounding carried into the next decade
+        n, X = 100000, X + 1
+    digits = str(n)
+    if X < -4 or X >= 6:
+        frac = digits[1:].rstrip("0")
+        text = digits[0] + ("." + frac if frac else "") + "e%s%02d" % ("-" if X < 0 else "+", abs(X))
+    elif X >= 0:
+        frac = digits[X + 1:].rstrip("0")
+        text = digits[:X + 1] + ("." + frac if frac else "")
+    else:
+        text = "0." + "0" * (-X - 1) + digits.rstrip("0")
+    return sign + text.encode()
+
+
+def tag_comment(data, rec_off, tags, floats=False):
     """(comment, copied, malformed, floats) of the record at data[rec_off:] and the listed tags (2-byte names, list order): comment =
     the bytes that go behind the read name ('\\tTG:T:text' per tag that is present and not float-typed; b"" when there is none),
     copied = one bool per listed tag (found and formatted), malformed = the record gets no comment because a listed tag gives
     TAG_MALFORMED, an A / Z / H value of a listed tag holds a byte outside 0x20..0x7E, or an H value has odd length or a non-hex
     character (copied is all False and floats 0 then), floats = the listed tags of type f or B:f, which are left out.
-    A c C s S i I: TG:A:c / TG:i:decimal; Z H: the bytes verbatim; B: TG:B:s and ',v' per element."""
-    data = bytes(data)
+    A c C s S i I: TG:A:c / TG:i:decimal; Z H: the bytes verbatim; B: TG:B:s and ',v' per element.
+    floats=True (--bam_tag_floats): an f value is TG:f:float_g, a B:f array TG:B:f and ',float_g' per element ('TG:B:f' alone when it
+    has none); such a tag counts as copied, and the floats returned are 0."""
+    data, floats_on = bytes(data), bool(floats)
     parts, copied, floats = [], [], 0
     bad = (b"", [False] * len(tags), True, 0)
     for tag in tags:
@@ -470,10 +519,18 @@ def tag_comment(data, rec_off, tags):
             continue
         v = data[off:off + n]
         if t == ord("f") or (t == ord("B") and v[0] == ord("f")):
-            floats += 1
-            copied.append(False)
-            continue
-        if t in (ord("A"), ord("Z"), ord("H")):
+            if not floats_on:
+                floats += 1
+                copied.append(False)
+                continue
+            if t == ord("f"):
+                if n != 4:
+                    return bad
+                text = b"f:" + float_g(struct.unpack("<I", v)[0])
+            else:
+                count = struct.unpack_from("<I", v, 1)[0]
+                text = b"B:f" + b"".join(b"," + float_g(x) for x in struct.unpack_from("<%dI" % count, v, 5))
+        elif t in (ord("A"), ord("Z"), ord("H")):
             if any(c < 0x20 or c > 0x7E for c in v):
                 return bad
             if t == ord("H") and (n & 1 or any(c not in _HEX for c in v)):
@@ -490,7 +547,7 @@ def tag_comment(data, rec_off, tags):
     return b"".join(parts), copied, False, floats
 
 
-def fastq_text_tagged(data, tags, start=None):
+def fastq_text_tagged(data, tags, start=None, floats=False):
     """fastq_text with every record's tag_comment inserted in front of its first newline (behind the read name). Skipped records stay
     skipped; a record on the reverse strand gets the same comment as it would on the forward strand (tags are not reversed)."""
     data = bytes(data)
@@ -500,11 +557,11 @@ def fastq_text_tagged(data, tags, start=None):
             continue
         text = r.fastq()
         at = text.index(b"\n")
-        out.append(text[:at] + tag_comment(data, r.offset, tags)[0] + text[at:])
+        out.append(text[:at] + tag_comment(data, r.offset, tags, floats)[0] + text[at:])
     return b"".join(out)
 
 
-def tag_counts(data, tags, start=None):
+def tag_counts(data, tags, start=None, floats=False):
     """the counters of a run with --bam_tags over the delivered records of `data`: {"copied": [records in which tag j was copied],
     "malformed_records": ..., "float_values_skipped": ...}"""
     data = bytes(data)
@@ -512,7 +569,7 @@ def tag_counts(data, tags, start=None):
     for r in records(data, start):
         if r.skipped:
             continue
-        _, c, m, f = tag_comment(data, r.offset, tags)
+        _, c, m, f = tag_comment(data, r.offset, tags, floats)
         mal += bool(m)
         fl += f
         for j, x in enumerate(c):

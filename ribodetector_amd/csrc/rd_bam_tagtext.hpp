@@ -2,7 +2,9 @@
 // view of a chunk (rd_bam_tt_* kernels; C ABI rd_bam_tag_splice, the CLI's --bam_tags). Part of the single translation unit
 // rd_kernels.hip (included from there, behind rd_bam_tags.hpp, whose walk finds the values); DESIGN.md §3.25.
 // The rule is ribodetector_amd/bam.py (tag_comment, fastq_text_tagged): record k of the FASTQ view, '@name\n...', becomes
-// '@name' + comment + '\n...', comment = '\tTG:T:text' per listed tag of raw record k that is present and not float-typed.
+// '@name' + comment + '\n...', comment = '\tTG:T:text' per listed tag of raw record k that is present and not float-typed. With floats on
+// (template parameter F of the count and the write pass; rd_bam_tag_splice_ex with RD_BAM_TAGS_FLOATS) an f value is TG:f:text and a B:f
+// array TG:B:f and ',text' per element, text = the value's %g form (rd_float_text.hpp: ft_format); without, they are counted and left out.
 //
 // The values come from rd_bam_tag_find_kernel, once per listed tag: (val_off, val_len, val_type)[tag][record] - every length is
 // checked there against the record's end, so a value lies inside its record. L lanes (4 or 16, the mapping of the walk) share a record:
@@ -10,7 +12,8 @@
 //   rd_bam_tt_count_kernel<L>  the header line's end (the first '\n' of the FASTQ record: 16 bytes per lane and step, a ballot finds
 //                              the first), then per listed tag the bytes of its text - the lanes of the group stride over the bytes
 //                              of a Z / H value (and validate them: 0x20..0x7E, H: hex digits, even length) and over the elements of a
-//                              B array (1 + sign + digits each); the partial sums meet in shuffles BEHIND the strided loops, where
+//                              B array (1 + sign + digits each; F: an f value is an array of one element without the comma, so the
+//                              formatter stands once in each pass); the partial sums meet in shuffles BEHIND the strided loops, where
 //                              every lane of the wave stands again. Writes the record's tagged length (into out_start), the header
 //                              length, a flag (1: malformed tags - no comment; 2: a record that is none) and tag_bytes[tag][record];
 //                              counts the copied tags, the malformed records and the skipped float values per workgroup in LDS
@@ -26,6 +29,7 @@
 #include "rd_common.hpp"
 #include "rd_deflate.hpp"
 #include "rd_bam_tags.hpp"
+#include "rd_float_text.hpp"
 
 namespace {
 
@@ -63,6 +67,12 @@ __device__ __forceinline__ int64_t tt_load_int(const uint8_t *__restrict__ p, ui
     return t == 'i' ? (int64_t)(int32_t)v : (int64_t)v;
 }
 
+__device__ __forceinline__ uint32_t tt_load_u32(const uint8_t *__restrict__ p) {
+    uint32_t v;
+    __builtin_memcpy(&v, p, 4);
+    return v;
+}
+
 __device__ __forceinline__ int tt_dec_len(int64_t v) {      // '-' and digits of |v| < 2^32
     const uint32_t u = (uint32_t)(v < 0 ? -v : v);
     int d = 1;
@@ -95,7 +105,7 @@ __device__ __forceinline__ void tt_copy(uint8_t *__restrict__ out, int64_t o0, c
     }
 }
 
-template <int L>
+template <int L, bool F>
 __global__ __launch_bounds__(TT_THREADS) void rd_bam_tt_count_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const int64_t *__restrict__ rec_start,
                                                                     const uint8_t *__restrict__ raw, int64_t raw_bytes, const int64_t *__restrict__ raw_start,
                                                                     int64_t n_rec, int n_tags, const int64_t *__restrict__ val_off,
@@ -172,8 +182,17 @@ __global__ __launch_bounds__(TT_THREADS) void rd_bam_tt_count_kernel(const uint8
                 } else if (tt_is_int(vt)) {
                     if (vl != tg_elem_size(vt)) lbad = 1;
                     else if (sub == 0) tb = 6 + tt_dec_len(tt_load_int(v, vt));
-                } else if (vt == 'f') {
+                } else if (vt == 'f' && !F) {
                     is_float = 1;
+                } else if (F && (vt == 'f' || (vt == 'B' && vl >= 5 && v[0] == 'f'))) {      // 'TG:f:' text / 'TG:B:f' and ',' text per element
+                    const int comma = vt == 'B';
+                    const uint8_t *__restrict__ fe = v + 5 * comma;
+                    const int64_t count = comma ? (vl - 5) / 4 : 1;
+                    if (!comma && vl != 4) lbad = 1;
+                    else {
+                        if (sub == 0) tb = 6 + comma;
+                        for (int64_t i = sub; i < count; i += L) tb += comma + ft_length(tt_load_u32(fe + 4 * i));
+                    }
                 } else if (vt == 'Z' || vt == 'H') {
                     const bool hex = vt == 'H';
                     if (hex && (vl & 1)) lbad = 1;
@@ -264,7 +283,7 @@ __global__ __launch_bounds__(TT_THREADS) void rd_bam_tt_off_kernel(int64_t *__re
     }
 }
 
-template <int L>
+template <int L, bool F>
 __global__ __launch_bounds__(TT_THREADS) void rd_bam_tt_write_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ rec_start,
                                                                     const uint8_t *__restrict__ raw, int64_t n_rec, int n_tags, TtNames names,
                                                                     const int64_t *__restrict__ val_off, const int32_t *__restrict__ val_len,
@@ -294,7 +313,7 @@ __global__ __launch_bounds__(TT_THREADS) void rd_bam_tt_write_kernel(const uint8
         int64_t count = 0, run = 0;                       // a B array: its elements and where the next one's text goes
         const uint8_t *__restrict__ el = raw;
         uint8_t st = 'C';
-        int es = 1;
+        int es = 1, comma = 1;                            // (F: 0 for the one element that an f value is)
         if (tb > 0) {
             const uint8_t *__restrict__ v = raw + val_off[at];
             const int64_t vl = val_len[at];
@@ -320,6 +339,13 @@ __global__ __launch_bounds__(TT_THREADS) void rd_bam_tt_write_kernel(const uint8
                 count = (vl - 5) / es;
                 el = v + 5;
                 run = o + 7;
+            } else if (F && vt == 'f') {
+                st = 'f';
+                es = 4;
+                count = 1;
+                el = v;
+                run = o + 6;
+                comma = 0;
             }
         }
         for (int64_t i0 = 0;; i0 += L) {
@@ -327,10 +353,15 @@ __global__ __launch_bounds__(TT_THREADS) void rd_bam_tt_write_kernel(const uint8
             const int64_t i = i0 + sub;
             int64_t x = 0;
             int dl = 0, mine = 0;
+            uint64_t ft[2] = {0, 0};
+            const bool fl = F && st == 'f';
             if (i < count) {
-                x = tt_load_int(el + i * es, st);
-                dl = tt_dec_len(x);
-                mine = 1 + dl;
+                if (fl) dl = ft_format(tt_load_u32(el + i * es), ft);
+                else {
+                    x = tt_load_int(el + i * es, st);
+                    dl = tt_dec_len(x);
+                }
+                mine = (F ? comma : 1) + dl;
             }
             int inc = mine;
 #pragma unroll
@@ -341,8 +372,10 @@ __global__ __launch_bounds__(TT_THREADS) void rd_bam_tt_write_kernel(const uint8
             const int total = __shfl(inc, gbase + L - 1);
             if (mine) {
                 uint8_t *__restrict__ q = out + run + (inc - mine);
-                q[0] = ',';
-                tt_put_dec(q + 1, x, dl);
+                const int c = F ? comma : 1;
+                if (c) q[0] = ',';
+                if (fl) ft_put(q + c, ft, dl);
+                else tt_put_dec(q + c, x, dl);
             }
             run += total;
         }
@@ -361,7 +394,7 @@ struct TagTextWs {
     size_t total;
 };
 
-template <int L>
+template <int L, bool F>
 void tagtext_launch(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const uint8_t *raw, int64_t raw_bytes, const int64_t *raw_start, int64_t n_rec,
                     int32_t n_tags, const TtNames &names, uint8_t *out, int64_t cap, int64_t *out_start, int64_t *info, const TagTextWs &p, hipStream_t st) {
     const int64_t per = TT_THREADS / L;
@@ -369,13 +402,13 @@ void tagtext_launch(const uint8_t *text, int64_t text_bytes, const int64_t *rec_
     for (int j = 0; j < n_tags; ++j)
         tag_find_launch<L>(raw, raw_bytes, raw_start, n_rec, (uint32_t)names.b[2 * j] | ((uint32_t)names.b[2 * j + 1] << 8), p.val_off + (size_t)j * n_rec,
                            p.val_len + (size_t)j * n_rec, p.val_type + (size_t)j * n_rec, st);
-    hipLaunchKernelGGL(rd_bam_tt_count_kernel<L>, grid, dim3(TT_THREADS), 0, st, text, text_bytes, rec_start, raw, raw_bytes, raw_start, n_rec, (int)n_tags,
+    hipLaunchKernelGGL((rd_bam_tt_count_kernel<L, F>), grid, dim3(TT_THREADS), 0, st, text, text_bytes, rec_start, raw, raw_bytes, raw_start, n_rec, (int)n_tags,
                        (const int64_t *)p.val_off, (const int32_t *)p.val_len, (const uint8_t *)p.val_type, p.tag_bytes, p.hdr, p.flags, out_start, p.cnt, p.fault);
     hipLaunchKernelGGL(rd_bam_tt_sum_kernel, dim3(p.nb), dim3(TT_THREADS), 0, st, (const int64_t *)out_start, n_rec, p.bsum);
     hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, p.bsum, p.nb, p.tot, (int64_t)INT64_MAX);
     hipLaunchKernelGGL(rd_bam_tt_off_kernel, dim3(p.nb), dim3(TT_THREADS), 0, st, out_start, n_rec, (const int64_t *)p.bsum, (const int64_t *)p.tot,
                        (const unsigned long long *)p.cnt, (const int32_t *)p.fault, cap, info);
-    hipLaunchKernelGGL(rd_bam_tt_write_kernel<L>, grid, dim3(TT_THREADS), 0, st, text, rec_start, raw, n_rec, (int)n_tags, names, (const int64_t *)p.val_off,
+    hipLaunchKernelGGL((rd_bam_tt_write_kernel<L, F>), grid, dim3(TT_THREADS), 0, st, text, rec_start, raw, n_rec, (int)n_tags, names, (const int64_t *)p.val_off,
                        (const int32_t *)p.val_len, (const uint8_t *)p.val_type, (const int64_t *)p.tag_bytes, (const int64_t *)p.hdr, (const uint8_t *)p.flags,
                        (const int64_t *)out_start, out, (const int64_t *)info);
 }

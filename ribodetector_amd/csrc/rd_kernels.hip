@@ -32,6 +32,7 @@
 //   rd_bam_find_*, rd_bam_count        a record start behind an offset of inflated BAM bytes, the records of a share (rd_bam_shard.hpp)
 //   rd_bam_tag_find, rd_bam_group_*    the optional fields of raw BAM records, and the counters per read group (rd_bam_tags.hpp)
 //   rd_bam_tag_splice                  the listed tags as text behind the read names of the FASTQ text (rd_bam_tagtext.hpp)
+//   rd_float_text                      float32 values as their exact %g text; the f / B:f values of rd_bam_tag_splice_ex (rd_float_text.hpp)
 //   rd_window_*                        reads longer than max_len as several windows: the window table and the fusion of its logits (rd_windows.hpp)
 //   rd_region_*                        the rRNA stretches of reads classified over windows, as text lines (rd_regions.hpp)
 #include <stdlib.h>
@@ -1250,6 +1251,17 @@ size_t rd_bam_tag_splice_workspace_bytes(int64_t n_rec, int32_t n_tags) {
 int rd_bam_tag_splice(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const uint8_t *raw, int64_t raw_bytes, const int64_t *raw_start,
                       int64_t n_rec, const uint8_t *tags, int32_t n_tags, uint8_t *out, size_t out_cap, int64_t *out_start, int64_t *info, void *workspace,
                       size_t workspace_bytes, void *stream) {
+    return rd_bam_tag_splice_ex(text, text_bytes, rec_start, raw, raw_bytes, raw_start, n_rec, tags, n_tags, out, out_cap, out_start, info, workspace, workspace_bytes, 0u,
+                                stream);
+}
+
+// flags & RD_BAM_TAGS_FLOATS: the count and the write pass that format f and B:f values (rd_float_text.hpp); the tables and the
+// workspace are the same
+int rd_bam_tag_splice_ex(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const uint8_t *raw, int64_t raw_bytes, const int64_t *raw_start,
+                         int64_t n_rec, const uint8_t *tags, int32_t n_tags, uint8_t *out, size_t out_cap, int64_t *out_start, int64_t *info, void *workspace,
+                         size_t workspace_bytes, uint32_t flags, void *stream) {
+    if (flags & ~RD_BAM_TAGS_FLOATS) RD_FAIL(RD_E_INVALID, "rd_bam_tag_splice: unknown flag bits 0x%x", flags & ~RD_BAM_TAGS_FLOATS);
+    const bool floats = (flags & RD_BAM_TAGS_FLOATS) != 0;
     if (n_rec < 0 || n_rec > 0x7fffffffLL / 64 || text_bytes < 0 || raw_bytes < 0) RD_FAIL(RD_E_INVALID, "rd_bam_tag_splice: bad n_rec, text_bytes or raw_bytes");
     if (n_tags < 1 || n_tags > RD_BAM_TAGS_MAX) RD_FAIL(RD_E_INVALID, "rd_bam_tag_splice: n_tags=%d out of range [1,%d]", n_tags, RD_BAM_TAGS_MAX);
     if (!tags) RD_FAIL(RD_E_INVALID, "rd_bam_tag_splice: null pointer");
@@ -1274,10 +1286,27 @@ int rd_bam_tag_splice(const uint8_t *text, int64_t text_bytes, const int64_t *re
     if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "rd_bam_tag_splice: workspace too small: %zu < %zu", workspace_bytes, p.total);
     const int64_t cap = (int64_t)(out_cap < (size_t)INT64_MAX ? out_cap : (size_t)INT64_MAX);
     RD_HIP(hipMemsetAsync(p.cnt, 0, (size_t)((char *)p.fault - (char *)p.cnt) + sizeof(int32_t), st));      // (the counters and the fault word)
-    if (tag_lanes(raw_bytes, n_rec) == 16)
-        tagtext_launch<16>(text, text_bytes, rec_start, raw, raw_bytes, raw_start, n_rec, n_tags, names, out, cap, out_start, info, p, st);
+    const bool wide = tag_lanes(raw_bytes, n_rec) == 16;
+    if (wide && floats)
+        tagtext_launch<16, true>(text, text_bytes, rec_start, raw, raw_bytes, raw_start, n_rec, n_tags, names, out, cap, out_start, info, p, st);
+    else if (wide)
+        tagtext_launch<16, false>(text, text_bytes, rec_start, raw, raw_bytes, raw_start, n_rec, n_tags, names, out, cap, out_start, info, p, st);
+    else if (floats)
+        tagtext_launch<4, true>(text, text_bytes, rec_start, raw, raw_bytes, raw_start, n_rec, n_tags, names, out, cap, out_start, info, p, st);
     else
-        tagtext_launch<4>(text, text_bytes, rec_start, raw, raw_bytes, raw_start, n_rec, n_tags, names, out, cap, out_start, info, p, st);
+        tagtext_launch<4, false>(text, text_bytes, rec_start, raw, raw_bytes, raw_start, n_rec, n_tags, names, out, cap, out_start, info, p, st);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+// float32 bit patterns as their %g text (rd_float_text.hpp), one 16-byte slot and one length per value
+int rd_float_text(const uint32_t *bits, int64_t n, uint8_t *text, uint8_t *len, void *stream) {
+    if (n < 0) RD_FAIL(RD_E_INVALID, "rd_float_text: n=%lld is negative", (long long)n);
+    if (n == 0) return RD_OK;
+    if (!bits || !text || !len) RD_FAIL(RD_E_INVALID, "rd_float_text: null pointer");
+    if (((uintptr_t)bits & 3) || ((uintptr_t)text & 15)) RD_FAIL(RD_E_INVALID, "rd_float_text: bits must be 4-byte aligned, text 16-byte aligned");
+    const int64_t wgs = (n + FT_THREADS - 1) / FT_THREADS;
+    hipLaunchKernelGGL(rd_float_text_kernel, dim3((unsigned)(wgs < FT_MAX_WGS ? wgs : FT_MAX_WGS)), dim3(FT_THREADS), 0, (hipStream_t)stream, bits, n, text, len);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }

@@ -43,7 +43,8 @@ read group on the post stream (groups.py: rd_bam_tag_find / rd_bam_group_rows / 
 --bam_tags LIST (an extension, BAM input, FASTQ outputs): the chunks carry the raw view, and every chunk gets one more view, the TAGGED
 text - its FASTQ text with the listed tags of every record behind the read name (bamtags.py: rd_bam_tag_splice, csrc/rd_bam_tagtext.hpp;
 bam.tag_comment has the rule). It depends on the chunk alone, so it is made on the copy stream when the chunk is submitted; the output
-kernels select from that view (_select_chunk), everything else sees the untagged FASTQ view.
+kernels select from that view (_select_chunk), everything else sees the untagged FASTQ view. --bam_tag_floats: the tagged view is built
+with the f and B:f values written in %g form (rd_bam_tag_splice_ex; bam.float_g has the rule) instead of skipped and counted.
 """
 import argparse
 import functools
@@ -273,6 +274,7 @@ class Predictor:
         self.bam_shard = bool(getattr(args, 'bam_shard', False))         # BAM input under several ranks: the sharded parse (data_loader/bam_shard.py)
         self._groups = None                      # ... groups.DeviceGroups (run_with_chunks)
         self.bam_tags = _tagmod.parse_list(self.bam_tags_arg) if self.bam_tags_arg is not None else None     # ... the listed names (2 bytes each)
+        self.bam_tag_floats = bool(getattr(args, 'bam_tag_floats', False))      # ... with the f and B:f values as %g text
         self._tags = None                        # ... bamtags.DeviceBamTags, one per input file (run_with_chunks)
         self._pairs = None                      # --interleaved: gz.DevicePairSplit (run_with_chunks)
         self._summary = None                     # --summary: summary.DeviceSummary (run_with_chunks)
@@ -1074,7 +1076,7 @@ class Predictor:
                 raise RuntimeError("--read_groups: the rows of the read groups hold {} unclassified / non-rRNA / rRNA units, the run {}".format(got, units))
             rg = doc["read_groups"] = _grpmod.to_json(gacc, grp.groups, bool(self.is_paired), input=self.input[0])
         if self._tags is not None:
-            doc["bam_tags"] = _tagmod.to_json(self.bam_tags, self._tag_total)
+            doc["bam_tags"] = _tagmod.to_json(self.bam_tags, self._tag_total, floats=self.bam_tag_floats)
         _summod.write_json(path, doc)
         frac = doc["reads"]["rRNA_fraction"]
         self.logger.info('rRNA fraction: {} (summary: {})'.format("n/a" if frac is None else "%.6f" % frac, path))
@@ -1236,7 +1238,7 @@ class Predictor:
         # --read_groups: the same units per read group of mate 1's BAM, one more int64 array that every chunk adds to
         self._groups = _grpmod.DeviceGroups(self.device, _bammod.header(self.input[0])) if self.read_groups else None
         # --bam_tags: the tagged view of every chunk, and the counters of the tags copied, per input file
-        self._tags = [_tagmod.DeviceBamTags(self.device, self.bam_tags) for _ in self.input] if self.bam_tags is not None else None
+        self._tags = [_tagmod.DeviceBamTags(self.device, self.bam_tags, floats=self.bam_tag_floats) for _ in self.input] if self.bam_tags is not None else None
         self._win_classified = [0, 0]
         # --regions: the lines of every chunk, formatted on the device; mate 1's writer appends the pieces (and deflates a .gz file)
         self._regions = bool(self.regions_path)
@@ -1330,7 +1332,7 @@ class Predictor:
         check_read_report(self.report_path, self.output, self.rrna, self.is_paired, self.args.ensure, self.bam_output)
         check_summary(self.summary_path, self.output, self.rrna, self.is_paired, self.args.ensure, self.report_path, self.bam_output)
         check_read_groups(self.read_groups, self.summary_path, self.input, self.bam_shard)
-        check_bam_tags(self.bam_tags_arg, self.input, self.bam_output)
+        check_bam_tags(self.bam_tags_arg, self.input, self.bam_output, floats=self.bam_tag_floats)
         self._windows = check_windows(self.args)
         check_regions(self.regions_path, self._windows is not None, self.output, self.rrna, self.is_paired, self.args.ensure,
                       self.report_path, self.summary_path, self.bam_output)
@@ -1480,11 +1482,15 @@ def check_summary(path, output, rrna, is_paired, ensure, read_report=None, bam_o
             raise RuntimeError("--summary {} is also {}".format(path, what))
 
 
-def check_bam_tags(bam_tags, inputs, bam_output=False):
+def check_bam_tags(bam_tags, inputs, bam_output=False, floats=False):
     """--bam_tags LIST: the rules that hold before anything touches a device; returns the listed names (2 bytes each, list order), or
     None without the flag. The list holds 1..16 names [A-Za-z][A-Za-z0-9], none twice (bamtags.parse_list); every input is BAM (the
-    tags are those of BAM records); not with --bam_output, whose outputs keep every tag as it stands."""
+    tags are those of BAM records); not with --bam_output, whose outputs keep every tag as it stands. floats (--bam_tag_floats) says
+    how the float values of the listed tags are written, so it needs the list."""
     if bam_tags is None:
+        if floats:
+            raise RuntimeError("--bam_tag_floats says how --bam_tags writes float values: give --bam_tags LIST with it "
+                               "(checked before anything touches a device)")
         return None
     names = _tagmod.parse_list(bam_tags)
     other = [p for p in inputs or [] if fx.get_seq_format(p) != "bam"]
@@ -1647,10 +1653,14 @@ none: give label based on the mean probability of read pair.
                       help='(extension) BAM input, FASTQ outputs: LIST = tag names separated by commas (MM,ML,RG; at most 16). Every FASTQ\n'
                            'record written carries the listed tags of its BAM record behind the read name, in list order, in SAM\'s\n'
                            'text form: @name<TAB>MM:Z:...<TAB>ML:B:C,... (what samtools fastq -T writes and minimap2 -y reads). A tag a\n'
-                           'record does not have adds nothing. Float-typed values (f, B:f) are NOT copied; they are counted. A record\n'
-                           'whose listed tags are malformed, or hold a byte that no header line may hold, gets no comment and is\n'
-                           'counted. Formatted on the GPU; the run keeps the records as they stand in the input and the tagged text in\n'
+                           'record does not have adds nothing. Float-typed values (f, B:f) are NOT copied; they are counted\n'
+                           '(--bam_tag_floats writes them). A record whose listed tags are malformed, or hold a byte that no header\n'
+                           'line may hold, gets no comment and is counted. Formatted on the GPU; the run keeps the records as they stand in the input and the tagged text in\n'
                            'GPU memory next to the FASTQ text. Not with --bam_output, which keeps every tag already.')
+    args.add_argument('--bam_tag_floats', action='store_true',
+                      help='(extension) with --bam_tags: a listed tag of type f is written as TG:f:value and a B:f array as\n'
+                           'TG:B:f,value,... instead of being skipped, value = what printf("%%g") prints (6 significant digits of the\n'
+                           'exact float32, ties to even). Formatted on the GPU in integer arithmetic.')
     args.add_argument('--no_mate_check', action='store_true', help='(extension) with --interleaved: do not compare the ids of the mates')
     args.add_argument('-v', '--version', action='version', version='%(prog)s {version}'.format(version=__version__))
     return args
@@ -1664,7 +1674,7 @@ def main(argv=None, log_level=None):
     check_regions(args.regions, args.windows)    # (args is the parser's own Namespace: every option is there)
     check_bam(args.input, args.output, args.rrna, args.bam_output, args.bam_shard, args.interleaved)
     check_read_groups(args.read_groups, args.summary, args.input, args.bam_shard)
-    check_bam_tags(args.bam_tags, args.input, args.bam_output)
+    check_bam_tags(args.bam_tags, args.input, args.bam_output, floats=args.bam_tag_floats)
     seq_pred = Predictor(config, args, log_level=log_level)
     try:
         t0 = time.perf_counter()

@@ -21,7 +21,11 @@ timed calls of each, ALTERNATING the legs (model load excluded: Predictor.timing
           (the records of tools/groups_bench.py) -> .gz, the legs no flag (the yardstick: the behaviour without the feature) and --bam_tags RG,
           alternating, with the peak of torch's allocator in each leg; long = `--long_reads` reads of 10 kb with MM:Z of 2 kB and ML:B:C of
           2,000 elements, --bam_tags MM,ML --windows --chunk_size 1; kernel = rd_bam_tag_splice ALONE on a resident chunk of both
-          shapes, 20 calls with device events.
+          shapes, 20 calls with device events. With float values (--bam_tag_floats, csrc/rd_float_text.hpp): kernel adds rd_float_text
+          ALONE on 2^24 resident values (uniform random bit patterns; qs-like values 5.0-40.0) and rd_bam_tag_splice_ex with floats on
+          over the 100 bp shape with a qs:f tag (list qs,RG) against the SAME call on records whose qs is a qs:i of 7 digits - existing
+          code, the yardstick - the two alternating; short adds `--reads` reads with qs:f -> .gz, --bam_tags qs,RG without (the
+          yardstick: the values are skipped) and with --bam_tag_floats.
 Every fourth record of the BAM files is stored on the reverse strand (flag 0x10, bases reverse-complemented, qualities reversed), so
 that the text the two legs see is the same. The inputs are written by processes that never touch the GPU."""
 import argparse
@@ -425,6 +429,139 @@ def bench_cli_bam_tags(d, shape, reads, calls):
           flush=True)
 
 
+def _make_qs(job):
+    """the BAM file of the float measurement: groups_bench's 100 bp records with qs:f (5.0-40.0) in front of RG:Z"""
+    d, reads = job
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import numpy as np
+    from ribodetector_amd import bam, synth
+    path = os.path.join(d, "qs_%d.bam" % reads)
+    if os.path.exists(path):
+        return
+    ids = [b"grp%03d" % g for g in range(24)]
+    step = 1 << 18
+    with open(path + ".raw", "wb") as fh:
+        fh.write(bam.encode_header(text=b"@HD\tVN:1.6\tSO:unsorted\n" + b"".join(b"@RG\tID:" + i + b"\n" for i in ids)))
+        for first in range(0, reads, step):
+            n = min(step, reads - first)
+            _, rec = _rows(n, first, 100, seed=1000 + first // step)
+            w = rec.shape[1]
+            full = np.zeros((n, w + 7 + 10), np.uint8)
+            full[:, :w] = rec
+            full[:, :4] = np.frombuffer(struct.pack("<i", full.shape[1] - 4), np.uint8)
+            full[:, w:w + 3] = np.frombuffer(b"qsf", np.uint8)
+            full[:, w + 3:w + 7] = np.random.default_rng(first).uniform(5.0, 40.0, n).astype(np.float32).view(np.uint8).reshape(n, 4)
+            full[:, w + 7:w + 10] = np.frombuffer(b"RGZ", np.uint8)
+            full[:, w + 10:-1] = np.frombuffer(b"".join(ids), np.uint8).reshape(len(ids), 6)[((first + np.arange(n)) // 1000) % len(ids)]
+            fh.write(full.tobytes())
+    synth.bgzip_file(path + ".raw", path, level=6, threads=8)
+    os.remove(path + ".raw")
+
+
+def bench_cli_bam_tag_floats(d, reads, calls):
+    """qs_N.bam -> .fq.gz with --bam_tags qs,RG: without --bam_tag_floats (the yardstick: qs is skipped and counted) against with it"""
+    src = os.path.join(d, "qs_%d.bam" % reads)
+    argv = {k: ["-l", "100", "-i", src, "-o", os.path.join(d, "o_%s.fq.gz" % k), "--bam_tags", "qs,RG"] + fl
+            for k, fl in (("skipped", []), ("floats", ["--bam_tag_floats"]))}
+    rate, last = timed_legs(argv, calls, reads)
+    med = {k: statistics.median(v) for k, v in rate.items()}
+    yard = rate["skipped"]
+    total = {k: last[k]._tag_total[0] for k in argv}
+    assert total["floats"]["copied"] == [reads, reads] and total["floats"]["float_values_skipped"] == 0 and total["skipped"]["float_values_skipped"] == reads
+    out_bytes = {k: os.path.getsize(v[5]) for k, v in argv.items()}
+    print(json.dumps({"measurement": "short_bam_tag_floats", "reads": reads, "read_len": 100, "calls": calls, "tags": "qs,RG",
+                      "flow": "single-end x.bam (qs:f, RG:Z) -> .fq.gz, --bam_tags qs,RG without | with --bam_tag_floats", "input_bytes": os.path.getsize(src),
+                      "output_bytes": out_bytes, "reads_per_s": {k: _mlh(v) for k, v in rate.items()}, "ratio_of_medians": round(med["floats"] / med["skipped"], 4),
+                      "with_flag_median_inside_no_flag_spread": bool(yard[0] <= med["floats"] <= yard[-1]),
+                      "text_bytes_added_per_record": round(sum(len(b"\tqs:f:%g" % x) for x in (5.0 + 35.0 * k / 997 for k in range(997))) / 997, 1),
+                      "gz_bytes_added_per_record": round((out_bytes["floats"] - out_bytes["skipped"]) / reads, 2)}), flush=True)
+
+
+def bench_kernel_float_text(calls):
+    """rd_float_text alone on 2^24 resident values: uniform random bit patterns, and qs-like values 5.0-40.0"""
+    import numpy as np
+    import torch
+    from ribodetector_amd import bam, bamtags
+    dev = torch.device("cuda:0")
+    n = 1 << 24
+    rng = np.random.default_rng(1)
+    for what, host in (("uniform random bit patterns", rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)),
+                       ("qs-like values 5.0-40.0", rng.uniform(5.0, 40.0, n).astype(np.float32).view(np.uint32))):
+        bits = torch.from_numpy(host.view(np.int32)).to(dev)
+        us = _events(lambda: bamtags.float_text(bits), calls)
+        text, length = bamtags.float_text(bits)
+        text, length = text[:4096].cpu().numpy(), length[:4096].cpu().numpy()
+        assert all(text[k, :length[k]].tobytes() == bam.float_g(int(host[k])) for k in range(4096))
+        med = statistics.median(us)
+        print(json.dumps({"measurement": "kernel_float_text", "what": "rd_float_text", "values": n, "distribution": what, "calls": calls, "us_per_call": _us(us),
+                          "values_per_s": round(n / (med * 1e-6)), "bytes_moved": 21 * n, "TB_per_s": round(21 * n / med / 1e6, 3),
+                          "fraction_of_hbm_bound_pass_at_8TBps": round(21 * n / 8e12 / (med * 1e-6), 4)}), flush=True)
+        del bits
+    torch.cuda.empty_cache()
+
+
+def bench_kernel_bam_tags_floats(calls):
+    """rd_bam_tag_splice_ex with floats on over 2^20 records of 100 bp with qs:f (list qs,RG) against rd_bam_tag_splice over the same
+    records with qs:i of 7 digits (existing code, the yardstick): the legs alternate, one event pair per call"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import groups_bench
+    from ribodetector_amd import bam, bamtags
+    dev = torch.device("cuda:0")
+    n, length, tags = 1 << 20, 100, [b"qs", b"RG"]
+    base, size, t_bytes, _ = groups_bench.records(n, length, 1, False)
+    rng = np.random.default_rng(2)
+    frec = 2 * length + NAME + 5
+    fq = np.full((n, frec), ord("A"), np.uint8)
+    fq[:, 0] = ord("@")
+    fq[:, 1:NAME] = ord("r")
+    fq[:, NAME] = fq[:, NAME + 1 + length] = fq[:, NAME + 3 + length] = fq[:, -1] = 10
+    fq[:, NAME + 2 + length] = ord("+")
+    text = torch.from_numpy(fq.reshape(-1)).to(dev)
+    rs = torch.arange(n + 1, dtype=torch.int64, device=dev) * frec
+    st = torch.arange(n + 1, dtype=torch.int64, device=dev) * (size + 7)
+    legs = {}
+    for leg, letter, values in (("qs_f", b"f", rng.uniform(5.0, 40.0, n).astype(np.float32).view(np.uint8)),
+                                ("qs_i", b"i", rng.integers(10 ** 6, 10 ** 7, n).astype(np.int32).view(np.uint8))):
+        rec = np.zeros((n, size + 7), np.uint8)
+        rec[:, :size] = base
+        rec[:, :4] = np.frombuffer(struct.pack("<i", size + 3), np.uint8)
+        rec[:, size:size + 3] = np.frombuffer(b"qs" + letter, np.uint8)
+        rec[:, size + 3:] = values.reshape(n, 4)
+        raw = torch.from_numpy(rec.reshape(-1)).to(dev)
+        cap = bamtags.default_hint(text.numel(), raw.numel())
+        out = torch.empty(((cap + 255) // 256) * 256 + 256, dtype=torch.uint8, device=dev)
+        legs[leg] = (rec, raw, cap, out, leg == "qs_f")
+    call = {leg: (lambda v=v: bamtags.splice(text, rs, v[1], st, n, tags, v[2], out=v[3], floats=v[4])) for leg, v in legs.items()}
+    for _ in range(3):
+        for leg in call:
+            call[leg]()
+    ev = {leg: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(calls)] for leg in call}
+    for k in range(calls):
+        for leg in call:
+            ev[leg][k][0].record()
+            call[leg]()
+            ev[leg][k][1].record()
+    torch.cuda.synchronize()
+    us = {leg: sorted(a.elapsed_time(b) * 1e3 for a, b in ev[leg]) for leg in call}
+    tagged = {}
+    for leg, (rec, raw, cap, out, floats) in legs.items():
+        _, out_start, info = call[leg]()
+        info = info.cpu().tolist()
+        k = n // 2
+        a, b = int(out_start[k]), int(out_start[k + 1])
+        data = bam.encode_header() + rec[k].tobytes()
+        want = fq[k].tobytes()[:NAME] + bam.tag_comment(data, bam.header_len(data), tags, floats=floats)[0] + fq[k].tobytes()[NAME:]
+        assert info[3] == 0 and info[5] == 0 and info[8:10] == [n, n] and bytes(out[a:b].cpu().numpy()) == want, info
+        tagged[leg] = info[1]
+    med = {leg: statistics.median(v) for leg, v in us.items()}
+    print(json.dumps({"measurement": "kernel_bam_tags_floats", "what": "rd_bam_tag_splice_ex (RD_BAM_TAGS_FLOATS) on qs:f | rd_bam_tag_splice on qs:i, alternating",
+                      "read_len": length, "records": n, "tags": ["qs", "RG"], "tagged_bytes": tagged, "calls": calls, "us_per_call": {k: _us(v) for k, v in us.items()},
+                      "ratio_of_medians_f_over_i": round(med["qs_f"] / med["qs_i"], 4),
+                      "float_median_inside_int_spread": bool(us["qs_i"][0] <= med["qs_f"] <= us["qs_i"][-1])}), flush=True)
+
+
 def bench_kernel_bam_tags(calls):
     """rd_bam_tag_splice alone on a resident chunk of both shapes: 2^20 records of 100 bp (RG) and 8,192 of 10 kb (MM, ML)"""
     import numpy as np
@@ -497,11 +634,16 @@ def main():
                 import multiprocessing as mp
                 with mp.get_context("spawn").Pool(len(jobs)) as pool:          # (before anything initialises the GPU)
                     pool.map(_make_tagged, jobs)
+                    pool.map(_make_qs, [(d, n) for _, s, n in jobs if s == "short"])
             import ribodetector_amd  # noqa: F401
             for _, s, n in jobs:
                 bench_cli_bam_tags(d, s, n, a.calls)
+                if s == "short":
+                    bench_cli_bam_tag_floats(d, n, a.calls)
             if "kernel" in which:
                 bench_kernel_bam_tags(20)
+                bench_kernel_float_text(20)
+                bench_kernel_bam_tags_floats(20)
         finally:
             if not a.keep:
                 shutil.rmtree(d, ignore_errors=True)
