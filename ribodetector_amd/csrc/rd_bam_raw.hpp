@@ -25,6 +25,7 @@
 // same a record is clamped to [begin, end) when its size is taken, and no byte outside the window is read.
 #pragma once
 #include "rd_bam_index.hpp"
+#include "rd_scan.hpp"
 
 namespace {
 

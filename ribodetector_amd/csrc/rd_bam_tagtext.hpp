@@ -17,8 +17,8 @@
 //                              every lane of the wave stands again. Writes the record's tagged length (into out_start), the header
 //                              length, a flag (1: malformed tags - no comment; 2: a record that is none) and tag_bytes[tag][record];
 //                              counts the copied tags, the malformed records and the skipped float values per workgroup in LDS
-//   rd_bam_tt_sum / off_kernel the lengths -> out_start (exclusive scan in place, 256 records per workgroup, the workgroups' sums by
-//                              rd_gz_sel_base_kernel), the totals and the verdict into info
+//   rd_scan_* (rd_scan.hpp)    the lengths -> out_start (exclusive scan in place, all three passes: the count pass has L lanes per
+//                              record and no sum of its own), then TtVerdict: the totals and the verdict into info
 //   rd_bam_tt_write_kernel<L>  nothing on a fault. '@name', the comment, the rest of the record: a copy writes the 16-byte aligned
 //                              pieces of its OUTPUT range with one unaligned load and one aligned store each, lane j of the group the
 //                              j-th piece of a step, and the ragged ends byte by byte - pieces of neighbouring ranges never overlap.
@@ -27,7 +27,7 @@
 //                              shuffles are executed by all 64 lanes. Decimal digits are written per lane.
 #pragma once
 #include "rd_common.hpp"
-#include "rd_deflate.hpp"
+#include "rd_scan.hpp"
 #include "rd_bam_tags.hpp"
 #include "rd_float_text.hpp"
 
@@ -249,27 +249,16 @@ __global__ __launch_bounds__(TT_THREADS) void rd_bam_tt_count_kernel(const uint8
     if (threadIdx.x < TT_CNT && scnt[threadIdx.x]) atomicAdd(&cnt[threadIdx.x], (unsigned long long)scnt[threadIdx.x]);
 }
 
-// the sums of 256 lengths per workgroup (entries [0, n); the table has n + 1)
-__global__ __launch_bounds__(TT_THREADS) void rd_bam_tt_sum_kernel(const int64_t *__restrict__ out_len, int64_t n, int64_t *__restrict__ bsum) {
-    __shared__ int64_t sh[4];
-    const int64_t u = (int64_t)blockIdx.x * TT_THREADS + threadIdx.x;
-    int64_t total;
-    gz_block_scan(u < n ? out_len[u] : 0, sh, total);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-
-// lengths -> exclusive offsets in place (entry n = the total); info = {records, bytes, 0, fault, malformed records, float values
-// skipped, 0, 0, records per copied tag}. fault 2: a record that is none; fault 1: more bytes than out_cap
-__global__ __launch_bounds__(TT_THREADS) void rd_bam_tt_off_kernel(int64_t *__restrict__ out_start, int64_t n, const int64_t *__restrict__ bbase,
-                                                                  const int64_t *__restrict__ tot, const unsigned long long *__restrict__ cnt,
-                                                                  const int32_t *__restrict__ fault, int64_t out_cap, int64_t *__restrict__ info) {
-    __shared__ int64_t sh[4];
-    const int64_t u = (int64_t)blockIdx.x * TT_THREADS + threadIdx.x;
-    const int64_t v = u < n ? out_start[u] : 0;
-    int64_t total;
-    const int64_t o = bbase[blockIdx.x] + gz_block_scan(v, sh, total);
-    if (u <= n) out_start[u] = o;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
+// the verdict behind the scan of out_start: info = {records, bytes, 0, fault, malformed records, float values skipped, 0, 0, records
+// per copied tag}. fault 2: a record that is none; fault 1: more bytes than out_cap. tot: the int64[4] of rd_scan_base_kernel
+struct TtVerdict {
+    int64_t n;
+    const int64_t *tot;
+    const unsigned long long *cnt;
+    const int32_t *fault;
+    int64_t out_cap;
+    int64_t *info;
+    __device__ __forceinline__ void operator()() const {
         const int64_t bytes = tot[1];
         const int f = *fault != 0 ? 2 : bytes > out_cap ? 1 : 0;
         info[0] = f == 2 ? 0 : n;
@@ -281,7 +270,7 @@ __global__ __launch_bounds__(TT_THREADS) void rd_bam_tt_off_kernel(int64_t *__re
         info[6] = info[7] = 0;
         for (int j = 0; j < RD_BAM_TAGS_MAX; ++j) info[8 + j] = f == 2 ? 0 : (int64_t)cnt[2 + j];
     }
-}
+};
 
 template <int L, bool F>
 __global__ __launch_bounds__(TT_THREADS) void rd_bam_tt_write_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ rec_start,
@@ -404,10 +393,10 @@ void tagtext_launch(const uint8_t *text, int64_t text_bytes, const int64_t *rec_
                            p.val_len + (size_t)j * n_rec, p.val_type + (size_t)j * n_rec, st);
     hipLaunchKernelGGL((rd_bam_tt_count_kernel<L, F>), grid, dim3(TT_THREADS), 0, st, text, text_bytes, rec_start, raw, raw_bytes, raw_start, n_rec, (int)n_tags,
                        (const int64_t *)p.val_off, (const int32_t *)p.val_len, (const uint8_t *)p.val_type, p.tag_bytes, p.hdr, p.flags, out_start, p.cnt, p.fault);
-    hipLaunchKernelGGL(rd_bam_tt_sum_kernel, dim3(p.nb), dim3(TT_THREADS), 0, st, (const int64_t *)out_start, n_rec, p.bsum);
-    hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, p.bsum, p.nb, p.tot, (int64_t)INT64_MAX);
-    hipLaunchKernelGGL(rd_bam_tt_off_kernel, dim3(p.nb), dim3(TT_THREADS), 0, st, out_start, n_rec, (const int64_t *)p.bsum, (const int64_t *)p.tot,
-                       (const unsigned long long *)p.cnt, (const int32_t *)p.fault, cap, info);
+    hipLaunchKernelGGL((rd_scan_sum_kernel<8, ScanTab<1>>), dim3(p.nb), dim3(256), 0, st, ScanTab<1>{{out_start}}, n_rec, p.bsum);
+    scan_base(p.bsum, p.nb, p.tot, INT64_MAX, st);
+    hipLaunchKernelGGL((rd_scan_off_kernel<8, 1, ScanTab<1>, TtVerdict>), dim3(p.nb), dim3(256), 0, st, ScanTab<1>{{out_start}}, n_rec, ScanOut<1>{{out_start}, {p.bsum}},
+                       TtVerdict{n_rec, p.tot, p.cnt, p.fault, cap, info});
     hipLaunchKernelGGL((rd_bam_tt_write_kernel<L, F>), grid, dim3(TT_THREADS), 0, st, text, rec_start, raw, n_rec, (int)n_tags, names, (const int64_t *)p.val_off,
                        (const int32_t *)p.val_len, (const uint8_t *)p.val_type, (const int64_t *)p.tag_bytes, (const int64_t *)p.hdr, (const uint8_t *)p.flags,
                        (const int64_t *)out_start, out, (const int64_t *)info);

@@ -7,7 +7,7 @@
 // cores - 13-20 % of the device rate, flat in the GPU count. Here the chunk's records of one label become gzip members without
 // leaving the device; the host appends the compressed bytes to the file.
 //
-//   rd_gz_sel_* / rd_gz_pack_kernel   selected records -> one contiguous byte stream (scan of the selected lengths + coalesced copy)
+//   rd_scan_* / rd_gz_pack_kernel     selected records -> one contiguous byte stream (scan of the selected lengths, rd_scan.hpp, + coalesced copy)
 //   rd_gz_deflate_kernel              one workgroup per member of 65,280 input bytes (BGZF's block size: the file is valid BGZF -
 //                                     bgzip / htslib index it, this build's reader inflates its members in parallel):
 //        wave w owns part w of the member (4,080 bytes: a sixteenth) and its own hash table in LDS (seeded with the last 512 bytes of the
@@ -26,6 +26,7 @@
 // the lane-for-lane CPU model tools/gzdev_model.c against zlib level 5: 0.98 / 1.00 / 0.94 of its size on three FASTQ profiles (1.02-1.06 on files of reads that are all copies of ONE template).
 #pragma once
 #include "rd_common.hpp"
+#include "rd_scan.hpp"
 
 namespace {
 
@@ -55,85 +56,12 @@ __constant__ uint32_t GZ_X2N[32] = {0x40000000u, 0x20000000u, 0x08000000u, 0x008
 // ------------------------------------------------------------------------------------------------
 // selection: out_off[i] = bytes of the selected records before record i (record i is selected when labels[i] == label)
 // ------------------------------------------------------------------------------------------------
-constexpr int GZ_SCAN_ITEMS = 2048;   // records per workgroup (256 threads x 8)
-
-__device__ __forceinline__ int64_t gz_sel_len(const int64_t *rec_start, const int8_t *labels, int64_t i, int64_t n, int label) {
-    return (i < n && labels[i] == (int8_t)label) ? rec_start[i + 1] - rec_start[i] : 0;
-}
-
-__device__ __forceinline__ int64_t gz_block_scan(int64_t v, int64_t *sh, int64_t &total) {   // exclusive scan over the 256 threads
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int64_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int64_t t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) sh[wave] = inc;
-    __syncthreads();
-    int64_t base = 0;
-    for (int w = 0; w < wave; ++w) base += sh[w];
-    total = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return base + inc - v;
-}
-
-__global__ __launch_bounds__(256) void rd_gz_sel_sum_kernel(const int64_t *__restrict__ rec_start, const int8_t *__restrict__ labels,
-                                                           int64_t n, int label, int64_t *__restrict__ bsum) {
-    __shared__ int64_t sh[4];
-    const int64_t i0 = (int64_t)blockIdx.x * GZ_SCAN_ITEMS + threadIdx.x * 8;
-    int64_t s = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s += gz_sel_len(rec_start, labels, i0 + k, n, label);
-    int64_t total;
-    gz_block_scan(s, sh, total);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-
-// one workgroup: bsum[] -> exclusive bases in place; info = {compressed bytes (filled later), plain bytes, members}
-__global__ __launch_bounds__(256) void rd_gz_sel_base_kernel(int64_t *__restrict__ bsum, int nb, int64_t *__restrict__ info, int64_t text_bytes) {
-    __shared__ int64_t sh[4];
-    __shared__ int64_t run_s;
-    if (threadIdx.x == 0) run_s = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nb; b0 += 256) {
-        const int b = b0 + threadIdx.x;
-        const int64_t v = b < nb ? bsum[b] : 0;
-        int64_t total;
-        const int64_t ex = gz_block_scan(v, sh, total);
-        const int64_t run = run_s;
-        if (b < nb) bsum[b] = run + ex;
-        __syncthreads();
-        if (threadIdx.x == 0) run_s = run + total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        // info[3] != 0: the record table does not describe the text (selected bytes > text bytes: overlapping or stray records) - the
-        // workspace is sized by the text, so nothing is packed or compressed and the caller is told
-        const bool bad = run_s > text_bytes || run_s < 0;
-        info[0] = 0;
-        info[1] = bad ? 0 : run_s;
-        info[2] = bad ? 0 : (run_s + GZ_MEMBER - 1) / GZ_MEMBER;
-        info[3] = bad ? 1 : 0;
-    }
-}
-
-__global__ __launch_bounds__(256) void rd_gz_sel_off_kernel(const int64_t *__restrict__ rec_start, const int8_t *__restrict__ labels,
-                                                           int64_t n, int label, const int64_t *__restrict__ bbase,
-                                                           int64_t *__restrict__ out_off) {
-    __shared__ int64_t sh[4];
-    const int64_t i0 = (int64_t)blockIdx.x * GZ_SCAN_ITEMS + threadIdx.x * 8;
-    int64_t v[8], s = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { v[k] = gz_sel_len(rec_start, labels, i0 + k, n, label); s += v[k]; }
-    int64_t total;
-    int64_t run = bbase[blockIdx.x] + gz_block_scan(s, sh, total);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        if (i0 + k <= n) out_off[i0 + k] = run;   // (entry n = the total)
-        run += v[k];
-    }
-}
+struct GzSelLen {                       // the length of record i when it is selected, else 0 (rd_scan.hpp's len functor)
+    const int64_t *rec_start;
+    const int8_t *labels;
+    int label;
+    __device__ __forceinline__ int64_t operator()(int, int64_t i) const { return labels[i] == (int8_t)label ? rec_start[i + 1] - rec_start[i] : 0; }
+};
 
 // selected records -> plain[out_off[i] ...): a workgroup takes 256 consecutive records, whose output range is contiguous, and its
 // threads take 16-byte pieces of that range (a piece finds its record by bisection over the 257 staged offsets)

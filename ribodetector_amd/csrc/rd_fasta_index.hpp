@@ -23,6 +23,7 @@
 // with an empty header line (until then everything is carried).
 #pragma once
 #include "rd_fastq_index.hpp"
+#include "rd_scan.hpp"
 
 namespace {
 

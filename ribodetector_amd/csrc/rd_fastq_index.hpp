@@ -25,7 +25,6 @@
 // gather's copy; measured numbers in DESIGN.md.
 #pragma once
 #include "rd_common.hpp"
-#include "rd_deflate.hpp"
 
 namespace {
 

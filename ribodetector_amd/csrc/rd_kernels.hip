@@ -44,6 +44,7 @@
 #include "rd_lstm_t32.hpp"
 #include "rd_refine.hpp"
 #include "rd_encode.hpp"
+#include "rd_scan.hpp"
 #include "rd_deflate.hpp"
 #include "rd_inflate_dev.hpp"
 #include "rd_inflate_stream.hpp"
@@ -615,7 +616,7 @@ GzWs gz_ws(void *workspace, int64_t n, int64_t text_bytes) {
     GzWs p{};
     if (n < 0 || text_bytes < 0) return p;
     Carver c(workspace);
-    p.nb = (int)((n + 1 + GZ_SCAN_ITEMS - 1) / GZ_SCAN_ITEMS);
+    p.nb = scan_blocks(n);
     p.cap_members = (text_bytes + GZ_MEMBER - 1) / GZ_MEMBER;
     if (p.cap_members < 1) p.cap_members = 1;
     p.grid = (int)(p.cap_members < GZ_MAX_GRID ? p.cap_members : GZ_MAX_GRID);
@@ -648,9 +649,12 @@ int sel_scan_pack(const char *fn, const uint8_t *text, int64_t text_bytes, const
     if (((uintptr_t)workspace & 255) || ((uintptr_t)out & (out_align - 1)))
         RD_FAIL(RD_E_INVALID, "%s: workspace must be 256-byte aligned, out %u-byte aligned", fn, out_align);
     if (workspace_bytes < need) RD_FAIL(RD_E_WORKSPACE, "%s: workspace too small: %zu < %zu", fn, workspace_bytes, need);
-    hipLaunchKernelGGL(rd_gz_sel_sum_kernel, dim3(s.nb), dim3(256), 0, st, rec_start, labels, n, label, s.bsum);
-    hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, s.bsum, s.nb, info, limit);
-    hipLaunchKernelGGL(rd_gz_sel_off_kernel, dim3(s.nb), dim3(256), 0, st, rec_start, labels, n, label, s.bsum, s.out_off);
+    const GzSelLen len = {rec_start, labels, (int)label};
+    hipLaunchKernelGGL((rd_scan_sum_kernel<8, GzSelLen>), dim3(s.nb), dim3(256), 0, st, len, n, s.bsum);
+    // info[3] != 0: the record table does not describe the text (rd_gz_compress_selected's limit is the text's bytes: more selected
+    // bytes than that are overlapping or stray records) - the workspace is sized by the text, so nothing is packed or compressed
+    scan_base(s.bsum, s.nb, info, limit, st, GZ_MEMBER);
+    hipLaunchKernelGGL((rd_scan_off_kernel<8, 1, GzSelLen, ScanNoVerdict>), dim3(s.nb), dim3(256), 0, st, len, n, ScanOut<1>{{s.out_off}, {s.bsum}}, ScanNoVerdict{});
     hipLaunchKernelGGL(rd_gz_pack_kernel, dim3((unsigned)((n + GZ_PACK_RECS - 1) / GZ_PACK_RECS)), dim3(256), 0, st, text, rec_start, s.out_off, n, dst, info);
     RD_HIP(hipGetLastError());
     return RD_OK;
@@ -1052,7 +1056,7 @@ struct ReportWs {
 ReportWs report_ws(void *workspace, int64_t n) {
     ReportWs p;
     Carver c(workspace);
-    p.nb = (int)((n + 1 + GZ_SCAN_ITEMS - 1) / GZ_SCAN_ITEMS);
+    p.nb = scan_blocks(n);
     p.idlen = c.take<int32_t>((size_t)n);
     p.qs = c.take<uint64_t>((size_t)n);
     p.bsum = c.take<int64_t>((size_t)p.nb);
@@ -1089,8 +1093,9 @@ int rd_report_format(const uint8_t *text, int64_t text_bytes, const int64_t *rec
     if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "rd_report_format: workspace too small: %zu < %zu", workspace_bytes, p.total);
     RD_HIP(hipMemsetAsync(p.fault, 0, sizeof(int32_t), st));
     hipLaunchKernelGGL(rd_report_len_kernel, dim3(p.nb), dim3(256), 0, st, text, text_bytes, rec_start, n, logits_a, logits_b, labels, line_start, p.idlen, p.qs, p.bsum, p.fault);
-    hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, p.bsum, p.nb, info, (int64_t)(out_cap < (size_t)INT64_MAX ? out_cap : (size_t)INT64_MAX));
-    hipLaunchKernelGGL(rd_report_off_kernel, dim3(p.nb), dim3(256), 0, st, line_start, n, p.bsum, p.fault, info);
+    scan_base(p.bsum, p.nb, info, (int64_t)(out_cap < (size_t)INT64_MAX ? out_cap : (size_t)INT64_MAX), st);
+    hipLaunchKernelGGL((rd_scan_off_kernel<8, 1, ScanTab<1>, RpVerdict>), dim3(p.nb), dim3(256), 0, st, ScanTab<1>{{line_start}}, n, ScanOut<1>{{line_start}, {p.bsum}},
+                       RpVerdict{n, p.fault, info});
     hipLaunchKernelGGL(rd_report_write_kernel, dim3((unsigned)((n + RP_LINES - 1) / RP_LINES)), dim3(256), 0, st, text, rec_start, line_start, n, p.idlen, p.qs, labels,
                        logits_b ? 3 : 1, out, info);
     RD_HIP(hipGetLastError());
@@ -1223,7 +1228,7 @@ TagTextWs tagtext_ws(void *workspace, int64_t n, int32_t n_tags) {
     TagTextWs p;
     Carver c(workspace);
     const size_t cells = (size_t)n * (size_t)n_tags;
-    p.nb = (int)((n + 1 + TT_THREADS - 1) / TT_THREADS);
+    p.nb = scan_blocks(n);
     p.val_off = c.take<int64_t>(cells);
     p.val_len = c.take<int32_t>(cells);
     p.val_type = c.take<uint8_t>(cells);
@@ -1323,7 +1328,7 @@ struct WindowWs {
 WindowWs window_ws(void *workspace, int64_t n) {
     WindowWs p;
     Carver c(workspace);
-    p.nb = (int)((n + 1 + GZ_SCAN_ITEMS - 1) / GZ_SCAN_ITEMS);
+    p.nb = scan_blocks(n);
     p.bsum = c.take<int64_t>((size_t)p.nb);
     p.fault = c.take<int32_t>(1);
     p.total = c.off;
@@ -1360,9 +1365,9 @@ int rd_window_plan(const int32_t *seq_len, int64_t n, int32_t max_len, int64_t s
     if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "rd_window_plan: workspace too small: %zu < %zu", workspace_bytes, p.total);
     RD_HIP(hipMemsetAsync(p.fault, 0, sizeof(int32_t), st));
     hipLaunchKernelGGL(rd_window_count_kernel, dim3(p.nb), dim3(256), 0, st, seq_len, n, (int64_t)max_len, stride, (int64_t)max_windows, p.bsum, p.fault);
-    hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, p.bsum, p.nb, info, (int64_t)INT64_MAX);
-    hipLaunchKernelGGL(rd_window_off_kernel, dim3(p.nb), dim3(256), 0, st, seq_len, n, (int64_t)max_len, stride, (int64_t)max_windows, p.bsum, p.fault,
-                       win_first, info);
+    scan_base(p.bsum, p.nb, info, INT64_MAX, st);
+    hipLaunchKernelGGL((rd_scan_off_kernel<8, 1, WnLen, WnVerdict>), dim3(p.nb), dim3(256), 0, st, WnLen{seq_len, (int64_t)max_len, stride, (int64_t)max_windows}, n,
+                       ScanOut<1>{{win_first}, {p.bsum}}, WnVerdict{n, p.fault, info});
     RD_HIP(hipGetLastError());
     return RD_OK;
 }
@@ -1410,8 +1415,8 @@ constexpr size_t RG_LINE_SLACK = 8 + 5 * 256;     // entry `lines` of line_off, 
 RegionWs region_ws(void *workspace, int64_t n, int64_t units, size_t workspace_bytes) {
     RegionWs p;
     Carver c(workspace);
-    p.nb = (int)((units + 1 + RG_UNITS - 1) / RG_UNITS);
-    const size_t cap_units = (size_t)(2 * n + 1), cap_nb = (size_t)((2 * n + 1 + RG_UNITS - 1) / RG_UNITS);
+    p.nb = scan_blocks(units, 1);
+    const size_t cap_units = (size_t)(2 * n + 1), cap_nb = (size_t)scan_blocks(2 * n, 1);
     p.unit_bytes = c.take<int64_t>(cap_units);
     p.unit_lines = c.take<int64_t>(cap_units);
     p.idlen = c.take<int32_t>(cap_units);
@@ -1464,10 +1469,10 @@ int rd_region_format(const uint8_t *text_a, int64_t bytes_a, const int64_t *rec_
     RD_HIP(hipMemsetAsync(p.cnt, 0, (size_t)((char *)p.fault - (char *)p.cnt) + sizeof(int32_t), st));     // (the counters and the fault word)
     hipLaunchKernelGGL(rd_region_count_kernel, dim3(p.nb), dim3(256), 0, st, ma, mb, mates, rec_stride, n, (int64_t)max_len, p.unit_bytes, p.unit_lines, p.idlen,
                        p.bsum_bytes, p.bsum_lines, p.cnt, p.fault);
-    hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, p.bsum_bytes, p.nb, p.tot_bytes, (int64_t)INT64_MAX);
-    hipLaunchKernelGGL(rd_gz_sel_base_kernel, dim3(1), dim3(256), 0, st, p.bsum_lines, p.nb, p.tot_lines, (int64_t)INT64_MAX);
-    hipLaunchKernelGGL(rd_region_off_kernel, dim3(p.nb), dim3(256), 0, st, p.unit_bytes, p.unit_lines, units, p.bsum_bytes, p.bsum_lines, p.tot_bytes, p.tot_lines,
-                       p.cnt, p.fault, cap, p.line_cap, info);
+    scan_base(p.bsum_bytes, p.nb, p.tot_bytes, INT64_MAX, st);
+    scan_base(p.bsum_lines, p.nb, p.tot_lines, INT64_MAX, st);
+    hipLaunchKernelGGL((rd_scan_off_kernel<1, 2, ScanTab<2>, RgVerdict>), dim3(p.nb), dim3(256), 0, st, ScanTab<2>{{p.unit_bytes, p.unit_lines}}, units,
+                       ScanOut<2>{{p.unit_bytes, p.unit_lines}, {p.bsum_bytes, p.bsum_lines}}, RgVerdict{units, p.tot_bytes, p.tot_lines, p.cnt, p.fault, cap, p.line_cap, info});
     hipLaunchKernelGGL(rd_region_lines_kernel, dim3(p.nb), dim3(256), 0, st, ma, mb, mates, n, (int64_t)max_len, p.unit_bytes, p.unit_lines, p.idlen, info, p.line_cap,
                        p.line_off, p.line_unit, p.line_start, p.line_end, p.line_wq);
     const int64_t tiles = (p.line_cap + RG_LINES - 1) / RG_LINES;

@@ -13,13 +13,14 @@
 // loop of rd_window_fuse_kernel (W <= 4096): a unit of thousands of windows holds its wave as long as it does there, not longer, and
 // the usual chunk (W of 1..3 everywhere) is one coalesced pass over win_logits. What must not sit behind one lane is the text: a unit
 // of 4,096 alternating windows has 2,048 lines. So the line pass writes no text, only one 24-byte entry per region into a LINE TABLE
-// (there are at most (windows + units) / 2 regions, which sizes it), and the write pass is rd_report_write_kernel's scheme over that
-// table: a workgroup takes 256 consecutive LINES, whichever units they belong to - a contiguous output range - and every lane
-// assembles 16-byte pieces of it.
+// (there are at most (windows + units) / 2 regions, which sizes it), and the write pass is the report's tile writer (rp_write_tile)
+// over that table: a workgroup takes 256 consecutive LINES, whichever units they belong to - a contiguous output range - and every
+// lane assembles 16-byte pieces of it.
 //
-//   rd_region_count_kernel   one lane per unit: id length (the 16-byte header scan of the report), regions and exact line bytes of the
-//                            unit; the workgroup's sums of both (block sums for rd_gz_sel_base_kernel); the counters of info[4..8)
-//   rd_region_off_kernel     per unit byte offset and line index (exclusive scans in place), the totals and the verdict info[8]
+//   rd_region_count_kernel   one lane per unit: id length (rp_id_len), regions and exact line bytes of the unit; the workgroup's sums
+//                            of both (the sums pass of rd_scan.hpp); the counters of info[4..8)
+//   rd_scan_off_kernel<1, 2> per unit byte offset and line index (both tables scanned in place by one launch), then RgVerdict: the
+//                            totals and the verdict info[8]
 //   rd_region_lines_kernel   one lane per unit walks its windows again: one line-table entry per region
 //   rd_region_write_kernel   256 consecutive lines per workgroup -> text, in aligned 16-byte stores
 #pragma once
@@ -51,27 +52,6 @@ __device__ __forceinline__ uint32_t rg_pow10(int k) {
     uint32_t p = 1;
     for (int i = 0; i < k; ++i) p *= 10u;
     return p;
-}
-
-// the id of a record [a, b): its length, or -1 when the record is not one (outside the text, no '@' / '>', a header past its end)
-__device__ __forceinline__ int64_t rg_id_len(const uint8_t *__restrict__ text, int64_t text_bytes, int64_t a, int64_t b) {
-    if (!(a >= 0 && a < b && b <= text_bytes)) return -1;
-    if (text[a] != '@' && text[a] != '>') return -1;
-    int64_t p = a + 1;
-    for (; p + 16 <= b; p += 16) {               // 16 bytes per step while they lie inside the record
-        u32x4 v;
-        __builtin_memcpy(&v, text + p, 16);
-        int j = 16;
-#pragma unroll
-        for (int w = 3; w >= 0; --w)
-#pragma unroll
-            for (int c = 3; c >= 0; --c)
-                if (rp_ws((v[w] >> (8 * c)) & 0xffu)) j = 4 * w + c;
-        if (j < 16) return p + j - a - 1 > 0x7fffffffLL ? -1 : p + j - a - 1;
-    }
-    for (; p < b; ++p)
-        if (rp_ws(text[p])) return p - a - 1 > 0x7fffffffLL ? -1 : p - a - 1;
-    return -1;
 }
 
 // The walk over a unit's windows that the count pass and the line pass share: emit(start, end, windows, q) per region, in ascending
@@ -106,7 +86,7 @@ __device__ __forceinline__ const RgMate &rg_mate(const RgMate &ma, const RgMate 
     return m ? mb : ma;
 }
 
-// unit_bytes / unit_lines: what the unit's lines need; the off pass turns both into exclusive offsets in place. cnt[4]: regions of mate
+// unit_bytes / unit_lines: what the unit's lines need; the offsets pass turns both into exclusive offsets in place. cnt[4]: regions of mate
 // 1 / 2, reads of mate 1 / 2 with a region.
 __global__ __launch_bounds__(256) void rd_region_count_kernel(RgMate ma, RgMate mb, int mates, int64_t rec_stride, int64_t n, int64_t L,
                                                              int64_t *__restrict__ unit_bytes, int64_t *__restrict__ unit_lines,
@@ -124,7 +104,7 @@ __global__ __launch_bounds__(256) void rd_region_count_kernel(RgMate ma, RgMate 
         int64_t i;
         int m;
         const RgMate &t = rg_mate(ma, mb, mates, u, i, m);
-        const int64_t idl = rg_id_len(t.text, t.bytes, t.rec_start[i * rec_stride], t.rec_start[i * rec_stride + 1]);
+        const int64_t idl = rp_id_len(t.text, t.bytes, t.rec_start[i * rec_stride], t.rec_start[i * rec_stride + 1]);
         const int64_t len = t.seq_len[i], f = t.win_first[i], W = t.win_first[i + 1] - f;
         // (every entry in [0, total] and every step in 1..RD_WINDOW_MAX, total = entry n: no window outside win_logits is read; several
         // windows are those of a read longer than L, or the starts would be negative)
@@ -145,34 +125,23 @@ __global__ __launch_bounds__(256) void rd_region_count_kernel(RgMate ma, RgMate 
         unit_lines[u] = lines;
         idlen[u] = bad ? 0 : (int32_t)idl;
     }
-    int64_t total;
-    gz_block_scan(bytes, sh, total);
-    if (threadIdx.x == 0) bsum_bytes[blockIdx.x] = total;
-    gz_block_scan(lines, sh, total);
-    if (threadIdx.x == 0) bsum_lines[blockIdx.x] = total;
+    scan_store_sum(bytes, sh, bsum_bytes);
+    scan_store_sum(lines, sh, bsum_lines);
     if (threadIdx.x < 4 && scnt[threadIdx.x]) atomicAdd(&cnt[threadIdx.x], (unsigned long long)scnt[threadIdx.x]);
 }
 
-// unit_bytes / unit_lines -> exclusive offsets in place (entry `units` = the totals); info = {units, bytes, 0, fault, regions of mate 1,
-// of mate 2, reads of mate 1 with a region, of mate 2}. tot_bytes / tot_lines: the int64[4] that rd_gz_sel_base_kernel wrote ([1] = the
-// total). fault 2: a unit that is none, or more lines than the line table holds (windows that the workspace was not sized for);
-// fault 1: more bytes than out_cap, info[1] = the bytes needed. Either way the passes behind this one write nothing.
-__global__ __launch_bounds__(256) void rd_region_off_kernel(int64_t *__restrict__ unit_bytes, int64_t *__restrict__ unit_lines, int64_t units,
-                                                           const int64_t *__restrict__ bb_bytes, const int64_t *__restrict__ bb_lines,
-                                                           const int64_t *__restrict__ tot_bytes, const int64_t *__restrict__ tot_lines,
-                                                           const unsigned long long *__restrict__ cnt, const int32_t *__restrict__ fault,
-                                                           int64_t out_cap, int64_t line_cap, int64_t *__restrict__ info) {
-    __shared__ int64_t sh[4];
-    const int64_t u = (int64_t)blockIdx.x * RG_UNITS + threadIdx.x;
-    const int64_t vb = u < units ? unit_bytes[u] : 0, vl = u < units ? unit_lines[u] : 0;
-    int64_t total;
-    const int64_t ob = bb_bytes[blockIdx.x] + gz_block_scan(vb, sh, total);
-    const int64_t ol = bb_lines[blockIdx.x] + gz_block_scan(vl, sh, total);
-    if (u <= units) {
-        unit_bytes[u] = ob;
-        unit_lines[u] = ol;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
+// The verdict behind the offsets pass (unit_bytes / unit_lines -> exclusive offsets in place, entry `units` = the totals): info = {units,
+// bytes, 0, fault, regions of mate 1, of mate 2, reads of mate 1 with a region, of mate 2}. tot_bytes / tot_lines: the int64[4] that
+// rd_scan_base_kernel wrote ([1] = the total). fault 2: a unit that is none, or more lines than the line table holds (windows that the
+// workspace was not sized for); fault 1: more bytes than out_cap, info[1] = the bytes needed. Either way the passes behind write nothing.
+struct RgVerdict {
+    int64_t units;
+    const int64_t *tot_bytes, *tot_lines;
+    const unsigned long long *cnt;
+    const int32_t *fault;
+    int64_t out_cap, line_cap;
+    int64_t *info;
+    __device__ __forceinline__ void operator()() const {
         const int64_t bytes = tot_bytes[1], lines = tot_lines[1];
         const int f = (*fault != 0 || lines > line_cap) ? 2 : bytes > out_cap ? 1 : 0;
         info[0] = f ? 0 : units;
@@ -181,7 +150,7 @@ __global__ __launch_bounds__(256) void rd_region_off_kernel(int64_t *__restrict_
         info[3] = f;
         for (int k = 0; k < 4; ++k) info[4 + k] = f == 2 ? 0 : (int64_t)cnt[k];
     }
-}
+};
 
 // one line-table entry per region: where its line starts in the output, its unit, start, end, and windows << 16 | q
 __global__ __launch_bounds__(256) void rd_region_lines_kernel(RgMate ma, RgMate mb, int mates, int64_t n, int64_t L,
@@ -238,17 +207,11 @@ __device__ __forceinline__ uint32_t rg_byte(const uint8_t *__restrict__ src, int
             t -= 2;
         }
     }
-    const uint32_t v = wq & 0xffffu;               // p, as rp_byte prints it
-    if (t >= 6) return '\n';
-    if (t == 1) return '.';
-    if (v >= 10000u) return t == 0 ? '1' : '0';
-    if (t == 0) return '0';
-    const uint32_t div = t == 2 ? 1000u : t == 3 ? 100u : t == 4 ? 10u : 1u;
-    return '0' + (v / div) % 10u;
+    return t >= 6 ? '\n' : rp_prob_byte(wq & 0xffffu, t);
 }
 
 // A workgroup takes tiles of RG_LINES consecutive lines (a contiguous output range each), the tiles dealt round over the grid: the
-// number of lines is known on the device only. Within a tile: rd_report_write_kernel's scheme.
+// number of lines is known on the device only. Within a tile: rp_write_tile.
 __global__ __launch_bounds__(256) void rd_region_write_kernel(RgMate ma, RgMate mb, int mates, int64_t rec_stride, const int64_t *__restrict__ unit_line,
                                                              int64_t units, const int32_t *__restrict__ idlen, const int64_t *__restrict__ line_off,
                                                              const int32_t *__restrict__ line_unit, const int32_t *__restrict__ line_start,
@@ -278,41 +241,9 @@ __global__ __launch_bounds__(256) void rd_region_write_kernel(RgMate ma, RgMate 
             mt[k] = (uint8_t)(m + 1);
         }
         __syncthreads();
-        const int64_t ob = offs[0], oe = offs[nr];
-        for (int64_t o = (ob & ~(int64_t)15) + 16 * (int64_t)threadIdx.x; o < oe; o += 16 * 256) {
-            const int64_t a = o < ob ? ob : o;         // the piece is [a, e) (its neighbours in other tiles write the rest)
-            const int64_t e = o + 16 < oe ? o + 16 : oe;
-            int lo = 0, hi = nr;                        // the line that holds byte a (lines are never empty)
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (offs[mid] <= a) lo = mid; else hi = mid;
-            }
-            int r = lo;
-            const bool whole = a == o && e == o + 16;
-            if (whole && o + 16 <= offs[r] + idl[r]) {     // 16 bytes of one id: one unaligned load, one aligned store
-                u32x4 v;
-                __builtin_memcpy(&v, srcs[r] + (o - offs[r]), 16);
-                *reinterpret_cast<u32x4 *>(out + o) = v;
-                continue;
-            }
-            u32x4 v = {0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int b = 0; b < 16; ++b) {
-                const int64_t p = o + b;
-                if (p >= a && p < e) {
-                    while (offs[r + 1] <= p) ++r;
-                    const uint32_t c = rg_byte(srcs[r], idl[r], ss[r], es[r], wqs[r], mt[r], p - offs[r]);
-                    v[b >> 2] |= c << (8 * (b & 3));
-                }
-            }
-            if (whole) {
-                *reinterpret_cast<u32x4 *>(out + o) = v;
-            } else {
-#pragma unroll
-                for (int b = 0; b < 16; ++b)
-                    if (o + b >= a && o + b < e) out[o + b] = (uint8_t)(v[b >> 2] >> (8 * (b & 3)));
-            }
-        }
+        rp_write_tile(offs, nr, out,
+                      [&](int r, int64_t j) { return j + 16 <= idl[r] ? srcs[r] + j : nullptr; },
+                      [&](int r, int64_t j) { return rg_byte(srcs[r], idl[r], ss[r], es[r], wqs[r], mt[r], j); });
     }
 }
 

@@ -1,5 +1,5 @@
 // rd_windows.hpp - reads longer than max_len classified over several windows of max_len bases (`--windows`), on the device (rd_window_* kernels)
-// Part of the single translation unit rd_kernels.hip (included from there, after rd_deflate.hpp, whose scan it reuses).
+// Part of the single translation unit rd_kernels.hip (included from there, after rd_scan.hpp, whose scan it uses).
 //
 // The window rule (one definition: wn_count / wn_start here, ribodetector_amd/windows.py in numpy, README "Windows"): a read of len bases
 // with L = max_len, S = stride, K = max_windows has W = 1 window when len <= L, else W = min(K, ceil((len - L) / S) + 1). W == 1: the
@@ -8,16 +8,15 @@
 // recomputes what the plan pass counted. A window is one more entry of a (seq_off, seq_len) table over the same text: rd_classify takes
 // the window table as it takes a read table, and no byte of text is read here.
 //
-//   rd_window_count_kernel   one thread per 8 reads: W per read, the workgroup's sum (the block sums of rd_gz_sel_*, which
-//                            rd_gz_sel_base_kernel turns into bases); a seq_len < 0 sets the fault word
-//   rd_window_off_kernel     W per read again -> win_first (exclusive scan, entry n = the total); the verdict info[4]
+//   rd_window_count_kernel   one thread per 8 reads: W per read, the workgroup's sum (the sums pass of rd_scan.hpp, whose base and
+//                            offsets passes make win_first of them: WnLen, WnVerdict); a seq_len < 0 sets the fault word
 //   rd_window_fill_kernel    one thread per read: its W table entries from win_first[i] on (W == 1 everywhere: entry i, the stores of a
 //                            wave are contiguous). Entries outside [0, total) are not written, whatever win_first says.
 //   rd_window_fuse_kernel    one thread per read: its windows' logits in window order -> the read's logits (and label). The order of
 //                            the fp32 sum is part of the result (mean), so there is no reduction across lanes.
 #pragma once
 #include "rd_common.hpp"
-#include "rd_deflate.hpp"
+#include "rd_scan.hpp"
 
 namespace {
 
@@ -45,33 +44,26 @@ __global__ __launch_bounds__(256) void rd_window_count_kernel(const int32_t *__r
             s += wn_count(len, L, S, K);
         }
     if (bad) atomicOr(fault, 1);
-    int64_t total;
-    gz_block_scan(s, sh, total);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+    scan_store_sum(s, sh, bsum);
 }
 
-__global__ __launch_bounds__(256) void rd_window_off_kernel(const int32_t *__restrict__ seq_len, int64_t n, int64_t L, int64_t S, int64_t K,
-                                                           const int64_t *__restrict__ bbase, const int32_t *__restrict__ fault,
-                                                           int64_t *__restrict__ win_first, int64_t *__restrict__ info) {
-    __shared__ int64_t sh[4];
-    const int64_t i0 = (int64_t)blockIdx.x * GZ_SCAN_ITEMS + threadIdx.x * 8;
-    int64_t v[8], s = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { v[k] = i0 + k < n ? wn_count(seq_len[i0 + k], L, S, K) : 0; s += v[k]; }
-    int64_t total;
-    int64_t run = bbase[blockIdx.x] + gz_block_scan(s, sh, total);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        if (i0 + k <= n) win_first[i0 + k] = run;         // (entry n = the total)
-        run += v[k];
-    }
-    // info = {reads, windows, 0, fault}: the base kernel has set info[1] = the total (and info[3] = 0: its limit is INT64_MAX)
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
+// the offsets pass (rd_scan_off_kernel) counts W per read again, then: info = {reads, windows, 0, fault} - the base kernel has set
+// info[1] = the total (and info[3] = 0: its limit is INT64_MAX)
+struct WnLen {
+    const int32_t *seq_len;
+    int64_t L, S, K;
+    __device__ __forceinline__ int64_t operator()(int, int64_t i) const { return wn_count(seq_len[i], L, S, K); }
+};
+struct WnVerdict {
+    int64_t n;
+    const int32_t *fault;
+    int64_t *info;
+    __device__ __forceinline__ void operator()() const {
         info[0] = n;
         info[2] = 0;
         if (*fault) info[3] = 1;
     }
-}
+};
 
 __global__ __launch_bounds__(256) void rd_window_fill_kernel(const int64_t *__restrict__ seq_off, const int32_t *__restrict__ seq_len,
                                                             const int64_t *__restrict__ win_first, int64_t n, int64_t L, int64_t S, int64_t K,

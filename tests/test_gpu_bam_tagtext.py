@@ -114,7 +114,7 @@ def test_splice_on_the_hand_built_cases(lanes, mapping):
 
 
 @pytest.mark.parametrize("mapping", LANES)
-@pytest.mark.parametrize("n_rec", [1, 63, 64, 65, 257, 3000])
+@pytest.mark.parametrize("n_rec", [1, 63, 64, 65, 257, 2047, 2048, 2049, 3000])      # (2,048 records per workgroup of the scan)
 def test_splice_record_counts(lanes, mapping, n_rec):
     lanes(mapping)
     base, lst = TC.random_records(11, 97)

@@ -66,30 +66,30 @@ def _device_report(recs, la, lb, labels):
 def test_format_kernel_against_python(fasta, paired):
     import torch
     from ribodetector_amd.gz import DeviceGzip
-    n = 12500                                                  # x 4 cases = 50k records
-    rng = np.random.default_rng(5 + 2 * fasta + paired)
-    recs = _records(n, 11 + 2 * fasta + paired, fasta=fasta)
-    la = _logits(n, rng)
-    lb = _logits(n, rng) if paired else None
-    labels = rng.integers(-1 if paired else 0, 2, n)
-    rep, out, ls, info, t, rs = _device_report(recs, la, lb, labels)
-    assert int(info[3]) == 0 and int(info[0]) == n
-    nb = int(info[1])
-    got = out[:nb].cpu().numpy().tobytes()
-    want = H.format_lines(recs, labels, la, lb)
-    _, g = H.parse(b"#\n" + got)
-    _, w = H.parse(b"#\n" + want)
-    assert len(g) == len(w) == n
-    assert [r[:2] for r in g] == [r[:2] for r in w]              # ids and labels byte for byte
-    dq = np.abs(np.array([r[2] for r in g]) - np.array([r[2] for r in w]))
-    assert dq.max() <= 1
-    starts = ls.cpu().numpy()
-    lens = np.array([len(x) + 1 for x in got.split(b"\n")[:-1]])
-    assert starts[0] == 0 and (np.diff(starts) == lens).all() and starts[-1] == nb
-    # the line starts are a record table of the report text: the device gzip deflates all of it
-    comp, ginfo = DeviceGzip("cuda:0").compress_selected(out, ls, rep.zeros(n), 0)
-    torch.cuda.synchronize()
-    assert gzip.decompress(comp[: int(ginfo[0])].cpu().numpy().tobytes()) == got
+    for n in (12500, 255, 256, 257):                           # x 4 cases = 50k records; then one tile of the write pass: a line short, full, a line more
+        rng = np.random.default_rng(5 + 2 * fasta + paired)
+        recs = _records(n, 11 + 2 * fasta + paired, fasta=fasta)
+        la = _logits(n, rng)
+        lb = _logits(n, rng) if paired else None
+        labels = rng.integers(-1 if paired else 0, 2, n)
+        rep, out, ls, info, t, rs = _device_report(recs, la, lb, labels)
+        assert int(info[3]) == 0 and int(info[0]) == n, n
+        nb = int(info[1])
+        got = out[:nb].cpu().numpy().tobytes()
+        want = H.format_lines(recs, labels, la, lb)
+        _, g = H.parse(b"#\n" + got)
+        _, w = H.parse(b"#\n" + want)
+        assert len(g) == len(w) == n, n
+        assert [r[:2] for r in g] == [r[:2] for r in w], n           # ids and labels byte for byte
+        dq = np.abs(np.array([r[2] for r in g]) - np.array([r[2] for r in w]))
+        assert dq.max() <= 1, n
+        starts = ls.cpu().numpy()
+        lens = np.array([len(x) + 1 for x in got.split(b"\n")[:-1]])
+        assert starts[0] == 0 and (np.diff(starts) == lens).all() and starts[-1] == nb, n
+        # the line starts are a record table of the report text: the device gzip deflates all of it
+        comp, ginfo = DeviceGzip("cuda:0").compress_selected(out, ls, rep.zeros(n), 0)
+        torch.cuda.synchronize()
+        assert gzip.decompress(comp[: int(ginfo[0])].cpu().numpy().tobytes()) == got, n
 
 
 def test_format_kernel_faults():

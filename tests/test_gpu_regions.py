@@ -171,21 +171,26 @@ def test_format_against_the_reference(n, layout):
 
 
 def test_every_id_length_and_terminator():
-    """ids of 0..40 and 300 bytes, each ended by each of the six id terminators; one window per read, all rRNA"""
-    rng = np.random.default_rng(11)
-    lens_of_id = list(range(0, 41)) + [300]
-    ids, terms = [], []
-    for k in lens_of_id:
-        for t in TERMS:
-            ids.append(bytes(rng.integers(48, 123, k).astype(np.uint8)))
-            terms.append(t)
-    n = len(ids)
-    m = {"ids": ids, "lens": rng.integers(1, 101, n).astype(np.int64), "first": np.arange(n + 1, dtype=np.int64),
-         "wl": np.stack([np.zeros(n), np.full(n, 3.0)], axis=1).astype(np.float32)}
-    recs = [_record(rid, t) for rid, t in zip(ids, terms)]
-    rs = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum([len(r) for r in recs], dtype=np.int64)])
-    want = _check([m], [(b"".join(recs), rs, 0)], 100)
-    assert want.count(b"\n") == n and want.startswith(b"\t0\t")
+    """ids of 0..40 and 300 bytes, each ended by each of the six id terminators; one window per read, all rRNA: 252 lines, and the
+    same with 3, 4 and 5 reads more - one tile of the write pass a line short, full, and a line more"""
+    for more in (0, 3, 4, 5):
+        rng = np.random.default_rng(11)
+        lens_of_id = list(range(0, 41)) + [300]
+        ids, terms = [], []
+        for k in lens_of_id:
+            for t in TERMS:
+                ids.append(bytes(rng.integers(48, 123, k).astype(np.uint8)))
+                terms.append(t)
+        for k in range(more):
+            ids.append(b"more%d" % k)
+            terms.append(TERMS[k])
+        n = len(ids)
+        m = {"ids": ids, "lens": rng.integers(1, 101, n).astype(np.int64), "first": np.arange(n + 1, dtype=np.int64),
+             "wl": np.stack([np.zeros(n), np.full(n, 3.0)], axis=1).astype(np.float32)}
+        recs = [_record(rid, t) for rid, t in zip(ids, terms)]
+        rs = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum([len(r) for r in recs], dtype=np.int64)])
+        want = _check([m], [(b"".join(recs), rs, 0)], 100)
+        assert want.count(b"\n") == n == 252 + more and want.startswith(b"\t0\t"), n
 
 
 def test_one_unit_of_4096_alternating_windows_and_starts_of_every_width():

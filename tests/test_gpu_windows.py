@@ -61,7 +61,7 @@ def _lengths(n, seed, L=100):
     return offs, lens
 
 
-@pytest.mark.parametrize("n", [0, 1, 2047, 2048, 2049, (1 << 17) + 3])
+@pytest.mark.parametrize("n", [0, 1, 2047, 2048, 2049, (1 << 17) + 3, 256 * 2048 + 1])      # (the last: 257 scan blocks, a second trip of the base pass)
 def test_plan_and_fill_against_the_reference(n):
     for L, S, K in ((100, 100, 32), (100, 37, 4096)) + (((4, 1, 5),) if n <= 2049 else ()):
         offs, lens = _lengths(n, 1000 + n, L)

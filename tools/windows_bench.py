@@ -12,7 +12,9 @@ the median rate and the lowest and highest of its calls.
           us per call and the bytes each moves; one chunk of 100 bp reads (W = 1) and one of 300 bp reads (W = 3)
 --keep DIR: leave the inputs in DIR (and reuse them when they are there), e.g. for a profiler run of one with-flag call:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o x -- python tools/windows_bench.py --keep DIR --profile_leg
---trace OUT then prints the rd_window_* kernels' times from OUT's kernel trace, and the run's kernel time in all.
+--trace OUT then prints the rd_window_* kernels' times from OUT's kernel trace, and the run's kernel time in all. The plan's offsets
+pass is the shared scan's instantiation over the window rule (csrc/rd_scan.hpp); it is listed as rd_window_off_kernel, the name it
+had as a kernel of its own in the lines already under profiles/. The plan's base pass (rd_scan_base_kernel) was never listed.
 """
 import argparse
 import csv
@@ -38,6 +40,8 @@ def trace_times(root):
                 total += us
                 if "rd_window_" in r["Kernel_Name"]:
                     out.setdefault("rd_window_" + r["Kernel_Name"].split("rd_window_")[1].split("(")[0], []).append(us)
+                elif "rd_scan_off_kernel" in r["Kernel_Name"] and "WnLen" in r["Kernel_Name"]:
+                    out.setdefault("rd_window_off_kernel", []).append(us)
     return out, total
 
 
