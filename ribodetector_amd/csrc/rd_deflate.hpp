@@ -11,12 +11,17 @@
 //   rd_gz_deflate_kernel              one workgroup per member of 65,280 input bytes (BGZF's block size: the file is valid BGZF -
 //                                     bgzip / htslib index it, this build's reader inflates its members in parallel):
 //        wave w owns part w of the member (4,080 bytes: a sixteenth) and its own hash table in LDS (seeded with the last 512 bytes of the
-//        part before; 256 buckets of the 8 nearest earlier positions with
-//        the same 8-byte hash); a STRIP of 64 consecutive positions is handled at once, one per lane: hash, the bucket's 8 candidates
-//        (positions before the strip) and distance 1 (runs) compared over the first 16 bytes; then the 64 positions are inserted; then
+//        part before; 512 buckets of 4 ways: the 4 nearest earlier positions with
+//        the same 8-byte hash); a STRIP of 64 consecutive positions is handled at once, one per lane: hash, the bucket's 4 candidates
+//        (positions before the strip) and distance 1 (runs) compared over the first 16 bytes - the longest wins, the nearest on ties,
+//        the run when it is as long, and only then is the length cut at the part's end; then the 64 positions are inserted: per bucket
+//        the occupants move one way down ONCE and one lane's position takes way 0 - WHICH of the strip's lanes that share a bucket
+//        wins the store is unspecified, and the losers' positions are never inserted; then
 //        the strip's parse is resolved from the ballot of match lanes (lazy rule: a match shorter than 16 yields to a longer one at
-//        the next position), and only the CHOSEN matches are measured exactly - by the whole wave, 8 lanes per candidate, 32 bytes
-//        per candidate and round; tokens go to a scratch in HBM, symbol counts to per-wave LDS histograms;
+//        the next lane of the strip; the strip's last lane looks at nothing), and only the CHOSEN matches are measured exactly - by
+//        the whole wave, 16 lanes per way, each comparing 4 bytes: 64 bytes per way and round; tokens go to a scratch in HBM, symbol
+//        counts to per-wave LDS histograms;
+//        (tests/gz_model.py states these rules in plain Python; tests/test_gpu_gz_model.py holds the kernel to them token for token)
 //        ONE dynamic-Huffman block per member: lengths by two-queue merge over the rank-sorted used symbols, limited to 15 bits the
 //        way zlib's gen_bitlen does it, canonical codes; code lengths sent without the run-length symbols (+0.2 %); every wave emits
 //        its part's tokens with a prefix sum of bit lengths and LDS atomic-or; stored block if that is smaller; CRC-32 of the

@@ -14,6 +14,14 @@
 //             literal when the next position holds a longer one), matches may run over the following strips;
 //   one dynamic-Huffman block per member (stored blocks if that is not smaller), codes limited to 15 bits the way zlib does it.
 //
+// Two known differences from the kernel (tests/gz_model.py is the model the kernel is tested against; tests/test_gz_model_host.py
+// holds its token and match counts to this tool's):
+//   * the block header here sends the code lengths with the run-length symbols 16-18; the kernel sends them one by one, so this
+//     tool's sizes are about 30 bytes per member below the kernel's;
+//   * the highest lane wins an insert here; the kernel leaves open which lane of a strip wins a bucket they share.
+// (Near a part's end the kernel also picks among lengths that are not yet cut at the end, this tool among cut ones: the distance of a
+// match within the last 15 positions of a part can differ, its length cannot.)
+//
 // build: gcc -O2 -o /tmp/gzdev_model tools/gzdev_model.c -lz        run: /tmp/gzdev_model file.fastq [more files]
 #include <stdint.h>
 #include <stdio.h>
