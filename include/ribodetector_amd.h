@@ -394,6 +394,43 @@ RD_API size_t rd_select_workspace_bytes(int64_t n);
 RD_API int rd_select_pack(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int8_t *labels, int64_t n, int32_t label, uint8_t *out,
                    size_t out_cap, int64_t *info, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The records of a chunk partitioned by KEY (outputs per read group, an extension): ONE call writes, for every key k in 0 .. K - 1, the
+ * records that carry it - in input order, the same bytes rd_select_pack / rd_gz_compress_selected write for them - as one contiguous
+ * run of `out`, the runs in key order. The number of launches does not depend on K. text / text_bytes / rec_start as rd_select_pack;
+ * keys [dev] int32[n]: -1 = no run takes the record. 1 <= K <= RD_GROUP_KEYS_MAX.
+ * rd_group_keys: the keys of a run that splits every class's file by the read group of MATE 1. rows [dev] int32 as rd_bam_group_rows
+ *   writes them (0 <= G <= RD_SPLIT_GROUPS_MAX declared groups; rows G, G + 1 and G + 2 - no tag, an undeclared value, malformed tags -
+ *   share member G of a family); unit u = record first + stride * u of that table, as in rd_bam_group_accumulate; labels [dev] int8[n]
+ *   in {-1, 0, 1}; class_slot [host] int32[3]: the index among this mate's families of the file set of class label + 1, -1 = the
+ *   class is not written. key = class_slot[label + 1] * (G + 1) + min(row, G), or -1. mate = -1: keys [dev] int32[n], a key per unit;
+ *   mate = 0 / 1: keys [dev] int32[2n] over the records of an interleaved chunk, keys[2u + mate] = the key and the other mate's entry =
+ *   -1 (the analogue of RD_LABEL_SKIP). info [dev] int64[4]: info[0] != 0 = a label outside -1..1 (bit 0) or a row outside 0..G + 2
+ *   (bit 1): such units get -1 and the keys are not to be used; info[1] = n.
+ * rd_group_pack: out [dev, 16-byte aligned]; every run STARTS on a multiple of 16 bytes. key_tab [dev] int64[K][4] = {offset of the
+ *   run in out, bytes, records, 0}. info [dev] int64[4]: info[0] = records with a key, info[1] = the bytes of `out` in use (the end of
+ *   the last run that holds a byte), info[3] = fault bits - 1: a key outside -1..K - 1, 2: the record table does not describe the text
+ *   (an entry outside it, descending entries, or more bytes in the keyed records than text_bytes), 4: info[1] > out_cap. On any fault
+ *   nothing is written or nothing in out is to be trusted; on fault 4 alone info[1] and key_tab still say what was needed.
+ * rd_gz_compress_grouped: the same partition, every run a sequence of complete BGZF members of at most 65,280 input bytes; no member
+ *   holds bytes of two keys. out [dev, 256-byte aligned] is compact and in key order: one copy to the host serves every file.
+ *   key_tab[k] = {offset of the key's first member in out, compressed bytes, records, members}, members = ceil(text bytes of k /
+ *   65,280) - 0 for a key without bytes. info[0] = compressed bytes, info[1] = uncompressed bytes, info[2] = members, info[3] as
+ *   above (4: info[0] > out_cap, out is incomplete). out_cap >= rd_gz_grouped_out_bound(text_bytes, K) is always enough.
+ * workspace [dev, 256-byte aligned] of rd_group_workspace_bytes(n, text_bytes, K, gz) bytes (gz != 0: rd_gz_compress_grouped's; 0:
+ * bad arguments). Its largest piece under gz is the padded stream in front of the deflate, in which every key's run starts a member:
+ * text_bytes + 65,280 * min(K, n) bytes at most, and 65,536 bytes of member slot per 65,280 of them. The counters of the partition are
+ * 32-bit words in LDS up to K = 4,096 and words in the workspace beyond. n == 0: info and key_tab are zeroed. Asynchronous on `stream`. */
+#define RD_SPLIT_GROUPS_MAX 1024
+#define RD_GROUP_KEYS_MAX 16384
+RD_API int rd_group_keys(const int32_t *rows, int64_t first, int64_t stride, int32_t mate, const int8_t *labels, int64_t n, const int32_t *class_slot,
+                         int32_t G, int32_t *keys, int64_t *info, void *stream);
+RD_API size_t rd_group_workspace_bytes(int64_t n, int64_t text_bytes, int32_t K, int32_t gz);
+RD_API size_t rd_gz_grouped_out_bound(int64_t text_bytes, int32_t K);
+RD_API int rd_group_pack(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int32_t *keys, int64_t n, int32_t K, uint8_t *out,
+                         size_t out_cap, int64_t *key_tab, int64_t *info, void *workspace, size_t workspace_bytes, void *stream);
+RD_API int rd_gz_compress_grouped(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int32_t *keys, int64_t n, int32_t K, uint8_t *out,
+                                  size_t out_cap, int64_t *key_tab, int64_t *info, void *workspace, size_t workspace_bytes, void *stream);
+
 /* The per-read report of a chunk (the CLI's --read_report) as ONE contiguous text in `out` [dev, 16-byte aligned]: line i, in input order,
  * is `<id>\t<label>\t<p>\n` (logits_b NULL: single-end) or `<id>\t<label>\t<p_a>\t<p_b>\t<p_pair>\n` (pairs). id = the bytes of record i's
  * header after its leading '@' / '>' up to the first of {space, \t, \r, \n, \v, \f} (may be empty); label = "rRNA" / "nonrRNA" /

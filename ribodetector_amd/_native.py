@@ -34,6 +34,7 @@ SYMBOLS = [
     "rd_bam_tag_splice_workspace_bytes", "rd_bam_tag_splice", "rd_bam_tag_splice_ex", "rd_float_text",
     "rd_window_workspace_bytes", "rd_window_plan", "rd_window_fill", "rd_window_fuse",
     "rd_region_workspace_bytes", "rd_region_format",
+    "rd_group_keys", "rd_group_workspace_bytes", "rd_gz_grouped_out_bound", "rd_group_pack", "rd_gz_compress_grouped",
 ]
 WINDOW_MAX = 4096       # include/ribodetector_amd.h RD_WINDOW_MAX: the most windows a read can have
 BAM_SEGMENT = 32768     # RD_BAM_SEGMENT: bytes per segment of the BAM framing (csrc/rd_bam_index.hpp)
@@ -44,6 +45,8 @@ GROUPS_MAX = 65536      # RD_GROUPS_MAX: the most read groups a dictionary of rd
 BAM_TAGS_MAX = 16       # RD_BAM_TAGS_MAX: the most tags rd_bam_tag_splice copies into the header lines
 BAM_TAGS_FLOATS = 1     # RD_BAM_TAGS_FLOATS: the flag of rd_bam_tag_splice_ex that formats f and B:f values
 FLOAT_TEXT_SLOT = 16    # bytes per value in the text rd_float_text writes
+SPLIT_GROUPS_MAX = 1024     # RD_SPLIT_GROUPS_MAX: the most declared read groups a run splits its outputs by (--split_groups)
+GROUP_KEYS_MAX = 16384      # RD_GROUP_KEYS_MAX: the most keys of rd_group_pack / rd_gz_compress_grouped
 LABEL_SKIP = 2         # include/ribodetector_amd.h RD_LABEL_SKIP: the record label that no output file selects
 
 
@@ -158,6 +161,13 @@ def lib():
     L.rd_region_workspace_bytes.argtypes = [i64, i64]
     L.rd_region_workspace_bytes.restype = sz
     L.rd_region_format.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, i64, i32, vp, sz, vp, vp, sz, vp]
+    L.rd_group_keys.argtypes = [vp, i64, i64, i32, vp, i64, C.POINTER(i32), i32, vp, vp, vp]
+    L.rd_group_workspace_bytes.argtypes = [i64, i64, i32, i32]
+    L.rd_group_workspace_bytes.restype = sz
+    L.rd_gz_grouped_out_bound.argtypes = [i64, i32]
+    L.rd_gz_grouped_out_bound.restype = sz
+    L.rd_group_pack.argtypes = [vp, i64, vp, vp, i64, i32, vp, sz, vp, vp, vp, sz, vp]
+    L.rd_gz_compress_grouped.argtypes = [vp, i64, vp, vp, i64, i32, vp, sz, vp, vp, vp, sz, vp]
     L.rd_stream_create.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(vp)]
     L.rd_stream_destroy.argtypes = [vp]
     L.rd_copy_bytes.argtypes = [vp, vp, i64, i32, vp]

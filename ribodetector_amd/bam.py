@@ -37,6 +37,7 @@ out and counted, or, with floats=True (--bam_tag_floats), written as float_g say
 csrc/rd_float_text.hpp, C ABI rd_float_text / rd_bam_tag_splice_ex). A record whose listed tags cannot be walked, or hold a byte that
 would break a FASTQ header line, gets no comment.
 """
+import os
 import struct
 import zlib
 
@@ -629,3 +630,32 @@ def group_row(data, val_off, val_len, val_type, ids):
         if bytes(rid) == value:
             return j
     return G + 1
+
+
+# ---- outputs per read group (detect.py --split_groups): the names of a family's files --------------------------------------------------
+SPLIT_GROUPS_MAX = N.SPLIT_GROUPS_MAX      # RD_SPLIT_GROUPS_MAX: the most declared groups a run splits its outputs by
+UNASSIGNED = None                          # the row id of a family's last member: no RG tag, an undeclared value, malformed tags
+_ESC_KEEP = frozenset(b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789._+=@,-")
+
+
+def esc(rid):
+    """a read-group id as part of a file name: the bytes A-Z a-z 0-9 . _ + = @ , - stay, every other byte - '%' included - becomes
+    %XX in upper-case hex. Injective; the result holds no '/'."""
+    return "".join(chr(b) if b in _ESC_KEEP else "%%%02X" % b for b in bytes(rid))
+
+
+def split_name(path, row_id):
+    """the name of the member of `path`'s family for the declared id `row_id` (bytes), or for the unassigned records (UNASSIGNED): the
+    marker '.rg-<esc(id)>' / '.unassigned' goes in front of the first '.' of the basename that is not its first byte, or behind the
+    name when there is no such dot: non.fq.gz -> non.rg-lib7.fq.gz, non.unassigned.fq.gz. The 'rg-' keeps declared ids apart from
+    'unassigned'."""
+    head, base = os.path.split(path)
+    marker = ".unassigned" if row_id is UNASSIGNED else ".rg-" + esc(row_id)
+    dot = base.find(".", 1)
+    base = base + marker if dot < 0 else base[:dot] + marker + base[dot:]
+    return os.path.join(head, base)
+
+
+def split_paths(path, ids):
+    """the G + 1 names of `path`'s family: a member per declared id, in the order of `ids`, and the unassigned member last"""
+    return [split_name(path, rid) for rid in ids] + [split_name(path, UNASSIGNED)]

@@ -492,16 +492,41 @@ __device__ void gz_huff(GzSmem &S, uint32_t *freq, uint8_t *lens, uint16_t *code
 }
 
 
-// plain: the selected records of the chunk as one stream (info[1] bytes); member m = bytes [65280 m, ...). toks: 65,280 words of
-// scratch per workgroup. slots: GZ_SLOT bytes per member; msize[m] = the member's size.
-__global__ __launch_bounds__(GZ_THREADS) void rd_gz_deflate_kernel(const uint8_t *__restrict__ plain, const int64_t *__restrict__ info,
+// How many members a stream has and how long each is (the deflate kernel's length provider): member m always STARTS at plain +
+// 65280 m. GzStreamLen: one stream of info[1] bytes, every member but the last is full. GzTableLen: info[2] members whose lengths
+// stand in a table - the keys of rd_gz_compress_grouped (rd_group_pack.hpp), each of which ends in a short member.
+struct GzStreamLen {
+    const int64_t *info;
+    struct View {
+        int64_t total;
+        __device__ __forceinline__ int64_t members() const { return (total + GZ_MEMBER - 1) / GZ_MEMBER; }
+        __device__ __forceinline__ int len(int64_t m) const { return (int)(total - m * GZ_MEMBER < GZ_MEMBER ? total - m * GZ_MEMBER : GZ_MEMBER); }
+    };
+    __device__ __forceinline__ View view() const { return View{info[1]}; }
+};
+struct GzTableLen {
+    const int64_t *info;
+    const uint32_t *mlen;
+    struct View {
+        int64_t nmem;
+        const uint32_t *mlen;
+        __device__ __forceinline__ int64_t members() const { return nmem; }
+        __device__ __forceinline__ int len(int64_t m) const { return __builtin_amdgcn_readfirstlane((int)mlen[m]); }   // (m is uniform)
+    };
+    __device__ __forceinline__ View view() const { return View{info[2], mlen}; }
+};
+
+// plain: the selected records of the chunk as one stream; member m = bytes [65280 m, ...) of it, ml.len(m) of them. toks: 65,280
+// words of scratch per workgroup. slots: GZ_SLOT bytes per member; msize[m] = the member's size.
+template <class MemberLen>
+__global__ __launch_bounds__(GZ_THREADS) void rd_gz_deflate_kernel(const uint8_t *__restrict__ plain, const MemberLen ml,
                                                            uint32_t *__restrict__ toks, uint8_t *__restrict__ slots,
                                                            uint32_t *__restrict__ msize) {
     __shared__ GzSmem S;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int64_t total = info[1];
-    const int64_t nmem = (total + GZ_MEMBER - 1) / GZ_MEMBER;
+    const typename MemberLen::View mv = ml.view();
+    const int64_t nmem = mv.members();
     {   // tables, once per workgroup
         if (tid < 256) {
             uint32_t c = (uint32_t)tid;
@@ -515,7 +540,7 @@ __global__ __launch_bounds__(GZ_THREADS) void rd_gz_deflate_kernel(const uint8_t
     const uint32_t x8n_full = tid >= 64 && crc_b0 < GZ_MEMBER ? gz_x8n((uint32_t)(GZ_MEMBER - (crc_b0 + GZ_CRCB < GZ_MEMBER ? crc_b0 + GZ_CRCB : GZ_MEMBER))) : 0u;
     uint32_t *mytoks = toks + (size_t)blockIdx.x * GZ_MEMBER;
     for (int64_t m = blockIdx.x; m < nmem; m += gridDim.x) {
-        const int len = (int)(total - m * GZ_MEMBER < GZ_MEMBER ? total - m * GZ_MEMBER : GZ_MEMBER);
+        const int len = mv.len(m);
         __syncthreads();
 #ifdef RD_DIAG
         unsigned long long stamp_ = clock64();

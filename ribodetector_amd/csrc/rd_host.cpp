@@ -235,7 +235,7 @@ struct rd_writer {
     bool gz;
     int threads;
     std::vector<uint8_t> pending;   // gz only: selected record bytes not yet compressed
-    std::vector<void *> comp;       // gz only: one libdeflate compressor per worker slot (empty: zlib)
+    std::vector<void *> comp;       // gz only: one libdeflate compressor per worker slot, made on the first flush (empty: zlib, or no flush yet)
     bool bgzf = false;              // members written by rd_writer_write_members (BGZF blocks made on the GPU)
     bool eof_marker = true;         // ... then the file ends with BGZF's empty block (rd_writer_set_eof_marker)
     bool bam = false;               // a BAM output (.bam / .ubam): gzip mode whose every member is a BGZF block, the end-of-file block always
@@ -386,6 +386,10 @@ int gz_flush(rd_writer *w, size_t upto) {
     std::condition_variable cv;
     size_t next = 0;
     const size_t nthreads = std::min<size_t>((size_t)std::max(1, w->threads), nblk);
+    // the compressors are made here, on the first flush of the host deflate, not when the file is opened: a writer that only ever
+    // appends members made on the device (hundreds of them in a run with a file per read group) holds none
+    if (w->comp.empty() && libdeflate().ok)
+        for (int k = 0; k < w->threads; ++k) w->comp.push_back(libdeflate().alloc(5));   // reference: compresslevel=5
     std::vector<std::thread> th;
     for (size_t t = 0; t < nthreads; ++t) {
         void *comp = t < w->comp.size() ? w->comp[t] : nullptr;
@@ -1050,8 +1054,6 @@ int rd_writer_open(const char *path, rd_writer **out) {
         delete w;
         RDH_FAIL("cannot open %s for writing", path);
     }
-    if (w->gz && libdeflate().ok)
-        for (int k = 0; k < w->threads; ++k) w->comp.push_back(libdeflate().alloc(5));   // reference: compresslevel=5
     *out = w;
     return 0;
 }

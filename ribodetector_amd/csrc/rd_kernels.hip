@@ -25,6 +25,7 @@
 //   rd_encode_* / rd_pack_onehot       standalone encoder kernels (reference tensor layouts), HBM-bound
 //   rd_pair_fuse_kernel, rd_count_kernel
 //   rd_gz_*                            records of one label -> gzip (BGZF) members on the device (rd_deflate.hpp)
+//   rd_group_* / rd_gz_compress_grouped the records partitioned by key: a run of text or of members per key (rd_group_pack.hpp)
 //   rd_fq_* / rd_fa_*                  FASTQ records framed, FASTA batches re-written and indexed in HBM (rd_fastq_index.hpp, rd_fasta_index.hpp)
 //   rd_report_*                        per-read report lines (id, label, probabilities) of a chunk (rd_report.hpp)
 //   rd_pair_*                          the mates of an interleaved chunk: pair table, mates' sequence tables, mate check (rd_pairs.hpp)
@@ -60,6 +61,7 @@
 #include "rd_bam_tagtext.hpp"
 #include "rd_windows.hpp"
 #include "rd_regions.hpp"
+#include "rd_group_pack.hpp"
 
 // ================================================================================================
 // C ABI
@@ -686,7 +688,7 @@ int rd_gz_compress_selected(const uint8_t *text, int64_t text_bytes, const int64
     const int rc = sel_scan_pack("rd_gz_compress_selected", text, text_bytes, rec_start, labels, n, label, out, 256, info, workspace, workspace_bytes,
                                  p.total, p, p.plain, text_bytes, st);
     if (rc || n == 0) return rc;
-    hipLaunchKernelGGL(rd_gz_deflate_kernel, dim3(p.grid), dim3(GZ_THREADS), 0, st, p.plain, info, p.toks, p.slots, p.msize);
+    hipLaunchKernelGGL(rd_gz_deflate_kernel<GzStreamLen>, dim3(p.grid), dim3(GZ_THREADS), 0, st, p.plain, GzStreamLen{info}, p.toks, p.slots, p.msize);
     hipLaunchKernelGGL(rd_gz_moff_kernel, dim3(1), dim3(256), 0, st, p.msize, p.moff, info);
     hipLaunchKernelGGL(rd_gz_compact_kernel, dim3(p.grid), dim3(256), 0, st, p.slots, p.msize, p.moff, info, out, (int64_t)out_cap);
     RD_HIP(hipGetLastError());
@@ -704,6 +706,159 @@ int rd_select_pack(const uint8_t *text, int64_t text_bytes, const int64_t *rec_s
     const int64_t limit = text_bytes < (int64_t)out_cap ? text_bytes : (int64_t)out_cap;   // more selected bytes than text, or than `out` holds
     return sel_scan_pack("rd_select_pack", text, text_bytes, rec_start, labels, n, label, out, 16, info, workspace, workspace_bytes, p.sel_total, p, out, limit,
                          (hipStream_t)stream);
+}
+
+// ---- the records of a chunk partitioned by key: a run of text or of gzip members per key (rd_group_pack.hpp) -----------------------
+namespace {
+// the workspace of rd_group_pack (gz = false) and rd_gz_compress_grouped; bad arguments give an empty layout, total = 0
+struct GpWs {
+    GpParts parts;
+    int64_t entries;        // K * parts: the (key, part) counters
+    int nb_pos, nb_len;     // scan blocks over the counters, over the records
+    int64_t cap_members;    // members of the padded stream at most
+    int grid;               // workgroups of the deflate kernel
+    int64_t *head;          // [0..3] the counters' scan, [4..7] the lengths' scan, [8] the fault flag of the count pass
+    uint32_t *cnt, *gcur, *toks, *msize, *mlen;
+    int64_t *pos, *bsum_pos, *L, *bsum_len, *shift, *moff;
+    int32_t *perm;
+    uint8_t *plain, *slots;
+    size_t total;
+};
+GpWs gp_ws(void *workspace, int64_t n, int64_t text_bytes, int64_t K, bool gz) {
+    GpWs p{};
+    if (n < 0 || n > 0x7fffffffLL || text_bytes < 0 || K < 1 || K > RD_GROUP_KEYS_MAX) return p;
+    Carver c(workspace);
+    int64_t nb = (n + GP_PART_MIN - 1) / GP_PART_MIN;
+    nb = nb < 1 ? 1 : nb > GP_MAX_PARTS ? GP_MAX_PARTS : nb;
+    p.parts = GpParts{(int)nb, (n + nb - 1) / nb};
+    p.entries = K * nb;
+    p.nb_pos = scan_blocks(p.entries);
+    p.nb_len = scan_blocks(n);
+    p.head = c.take<int64_t>(16);
+    p.cnt = c.take<uint32_t>((size_t)p.entries);
+    p.gcur = c.take<uint32_t>(K > GP_LDS_KEYS ? (size_t)p.entries : 0);
+    p.pos = c.take<int64_t>((size_t)p.entries + 1);
+    p.bsum_pos = c.take<int64_t>((size_t)p.nb_pos);
+    p.perm = c.take<int32_t>((size_t)n);
+    p.L = c.take<int64_t>((size_t)n + 1);
+    p.bsum_len = c.take<int64_t>((size_t)p.nb_len);
+    p.shift = c.take<int64_t>((size_t)K);
+    if (gz) {   // the padded stream: every key's run starts a member, so it holds text_bytes + 65,280 * min(K, n) bytes at most
+        p.cap_members = text_bytes / GZ_MEMBER + (K < n ? K : n) + 1;
+        p.grid = (int)(p.cap_members < GZ_MAX_GRID ? p.cap_members : GZ_MAX_GRID);
+        p.plain = c.take<uint8_t>((size_t)p.cap_members * GZ_MEMBER + 256);
+        p.toks = c.take<uint32_t>((size_t)p.grid * GZ_MEMBER);
+        p.slots = c.take<uint8_t>((size_t)p.cap_members * GZ_SLOT);
+        p.msize = c.take<uint32_t>((size_t)p.cap_members);
+        p.moff = c.take<int64_t>((size_t)p.cap_members);
+        p.mlen = c.take<uint32_t>((size_t)p.cap_members);
+    }
+    p.total = c.off;
+    return p;
+}
+
+// What rd_group_pack and rd_gz_compress_grouped (`fn`) share: the argument checks, the n == 0 path, the partition, the length scan,
+// the keys' table and the pack into `dst`. The caller goes on only when n > 0.
+int group_scan_pack(bool gz, const char *fn, const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int32_t *keys, int64_t n, int32_t K,
+                    const uint8_t *out, size_t out_cap, unsigned out_align, int64_t *key_tab, int64_t *info, void *workspace, size_t workspace_bytes,
+                    const GpWs &p, uint8_t *dst, hipStream_t st) {
+    if (n < 0 || n > 0x7fffffffLL || text_bytes < 0) RD_FAIL(RD_E_INVALID, "%s: bad n or text_bytes", fn);
+    if (K < 1 || K > RD_GROUP_KEYS_MAX) RD_FAIL(RD_E_INVALID, "%s: K = %d is outside 1..%d", fn, K, RD_GROUP_KEYS_MAX);
+    if (!info || !key_tab) RD_FAIL(RD_E_INVALID, "%s: null info or key_tab", fn);
+    if (n == 0) {
+        RD_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int64_t), st));
+        RD_HIP(hipMemsetAsync(key_tab, 0, (size_t)K * 4 * sizeof(int64_t), st));
+        return RD_OK;
+    }
+    if ((!text && text_bytes > 0) || !rec_start || !keys || !out || !workspace) RD_FAIL(RD_E_INVALID, "%s: null pointer", fn);
+    if (((uintptr_t)workspace & 255) || ((uintptr_t)out & (out_align - 1)))
+        RD_FAIL(RD_E_INVALID, "%s: workspace must be 256-byte aligned, out %u-byte aligned", fn, out_align);
+    if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "%s: workspace too small: %zu < %zu", fn, workspace_bytes, p.total);
+    const bool lds = K <= GP_LDS_KEYS;
+    uint32_t *flag = reinterpret_cast<uint32_t *>(p.head + 8);
+    int64_t *pinfo = p.head, *linfo = p.head + 4;
+    RD_HIP(hipMemsetAsync(p.head, 0, 16 * sizeof(int64_t), st));
+    if (!lds) RD_HIP(hipMemsetAsync(p.gcur, 0, (size_t)p.entries * sizeof(uint32_t), st));
+    if (lds)
+        hipLaunchKernelGGL(rd_gp_count_kernel<true>, dim3(p.parts.nb), dim3(64), 0, st, keys, rec_start, n, text_bytes, (int)K, p.parts, p.cnt, p.gcur, flag);
+    else
+        hipLaunchKernelGGL(rd_gp_count_kernel<false>, dim3(p.parts.nb), dim3(64), 0, st, keys, rec_start, n, text_bytes, (int)K, p.parts, p.cnt, p.gcur, flag);
+    const GpCntLen clen = {p.cnt};
+    hipLaunchKernelGGL((rd_scan_sum_kernel<8, GpCntLen>), dim3(p.nb_pos), dim3(256), 0, st, clen, p.entries, p.bsum_pos);
+    scan_base(p.bsum_pos, p.nb_pos, pinfo, n, st);
+    hipLaunchKernelGGL((rd_scan_off_kernel<8, 1, GpCntLen, ScanNoVerdict>), dim3(p.nb_pos), dim3(256), 0, st, clen, p.entries, ScanOut<1>{{p.pos}, {p.bsum_pos}}, ScanNoVerdict{});
+    if (lds)
+        hipLaunchKernelGGL(rd_gp_scatter_kernel<true>, dim3(p.parts.nb), dim3(64), 0, st, keys, n, (int)K, p.parts, p.pos, p.gcur, flag, p.perm);
+    else
+        hipLaunchKernelGGL(rd_gp_scatter_kernel<false>, dim3(p.parts.nb), dim3(64), 0, st, keys, n, (int)K, p.parts, p.pos, p.gcur, flag, p.perm);
+    // more bytes in the keyed records than in the text: overlapping records - the table does not describe the text (linfo[3])
+    const GpPermLen plen = {p.perm, rec_start, p.pos + p.entries, flag};
+    hipLaunchKernelGGL((rd_scan_sum_kernel<8, GpPermLen>), dim3(p.nb_len), dim3(256), 0, st, plen, n, p.bsum_len);
+    scan_base(p.bsum_len, p.nb_len, linfo, text_bytes, st);
+    hipLaunchKernelGGL((rd_scan_off_kernel<8, 1, GpPermLen, ScanNoVerdict>), dim3(p.nb_len), dim3(256), 0, st, plen, n, ScanOut<1>{{p.L}, {p.bsum_len}}, ScanNoVerdict{});
+    if (gz) {
+        hipLaunchKernelGGL(rd_gp_keytab_kernel<true>, dim3(1), dim3(256), 0, st, p.pos, p.L, (int)K, p.parts.nb, flag, linfo, (int64_t)out_cap, p.shift, key_tab, info);
+        hipLaunchKernelGGL(rd_gp_mlen_kernel, dim3((unsigned)(K < 1024 ? K : 1024)), dim3(256), 0, st, key_tab, (int)K, p.mlen, info);
+    } else {
+        hipLaunchKernelGGL(rd_gp_keytab_kernel<false>, dim3(1), dim3(256), 0, st, p.pos, p.L, (int)K, p.parts.nb, flag, linfo, (int64_t)out_cap, p.shift, key_tab, info);
+    }
+    hipLaunchKernelGGL(rd_gp_pack_kernel, dim3((unsigned)((n + GZ_PACK_RECS - 1) / GZ_PACK_RECS)), dim3(256), 0, st, text, rec_start, keys, p.perm, p.L, p.shift,
+                       p.pos + p.entries, dst, info);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+}  // namespace
+
+int rd_group_keys(const int32_t *rows, int64_t first, int64_t stride, int32_t mate, const int8_t *labels, int64_t n, const int32_t *class_slot, int32_t G,
+                  int32_t *keys, int64_t *info, void *stream) {
+    if (n < 0 || n > 0x3fffffffLL || G < 0 || G > RD_SPLIT_GROUPS_MAX) RD_FAIL(RD_E_INVALID, "rd_group_keys: bad n or G");
+    if (first < 0 || stride < 1) RD_FAIL(RD_E_INVALID, "rd_group_keys: bad first / stride");
+    if (mate < -1 || mate > 1) RD_FAIL(RD_E_INVALID, "rd_group_keys: mate must be -1 (a key per unit), 0 or 1; got %d", mate);
+    if (!class_slot || !info) RD_FAIL(RD_E_INVALID, "rd_group_keys: null class_slot or info");
+    GpSlots slots;
+    for (int c = 0; c < 3; ++c) {
+        if (class_slot[c] < -1 || class_slot[c] > 2) RD_FAIL(RD_E_INVALID, "rd_group_keys: class_slot[%d] = %d is outside -1..2", c, class_slot[c]);
+        slots.s[c] = class_slot[c];
+    }
+    RD_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int64_t), (hipStream_t)stream));
+    if (n == 0) return RD_OK;
+    if (!rows || !labels || !keys) RD_FAIL(RD_E_INVALID, "rd_group_keys: null pointer");
+    hipLaunchKernelGGL(rd_group_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rows, first, stride, (int)mate, labels, n, slots,
+                       (int)G, keys, info);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+size_t rd_group_workspace_bytes(int64_t n, int64_t text_bytes, int32_t K, int32_t gz) {
+    return gp_ws(nullptr, n, text_bytes, K, gz != 0).total;
+}
+
+size_t rd_gz_grouped_out_bound(int64_t text_bytes, int32_t K) {
+    if (text_bytes < 0 || K < 1 || K > RD_GROUP_KEYS_MAX) return 0;
+    const int64_t members = text_bytes / GZ_MEMBER + K;     // every key may end in a short member
+    return (size_t)members * (GZ_HDR + 5 + GZ_TRL) + (size_t)text_bytes;   // every member as a stored block
+}
+
+int rd_group_pack(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int32_t *keys, int64_t n, int32_t K, uint8_t *out, size_t out_cap,
+                  int64_t *key_tab, int64_t *info, void *workspace, size_t workspace_bytes, void *stream) {
+    const GpWs p = gp_ws(workspace, n, text_bytes, K, false);
+    return group_scan_pack(false, "rd_group_pack", text, text_bytes, rec_start, keys, n, K, out, out_cap, 16, key_tab, info, workspace, workspace_bytes, p, out,
+                                  (hipStream_t)stream);
+}
+
+int rd_gz_compress_grouped(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int32_t *keys, int64_t n, int32_t K, uint8_t *out,
+                           size_t out_cap, int64_t *key_tab, int64_t *info, void *workspace, size_t workspace_bytes, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const GpWs p = gp_ws(workspace, n, text_bytes, K, true);
+    const int rc = group_scan_pack(true, "rd_gz_compress_grouped", text, text_bytes, rec_start, keys, n, K, out, out_cap, 256, key_tab, info, workspace,
+                                         workspace_bytes, p, p.plain, st);
+    if (rc || n == 0) return rc;
+    hipLaunchKernelGGL(rd_gz_deflate_kernel<GzTableLen>, dim3(p.grid), dim3(GZ_THREADS), 0, st, p.plain, GzTableLen{info, p.mlen}, p.toks, p.slots, p.msize);
+    hipLaunchKernelGGL(rd_gz_moff_kernel, dim3(1), dim3(256), 0, st, p.msize, p.moff, info);
+    hipLaunchKernelGGL(rd_gz_compact_kernel, dim3(p.grid), dim3(256), 0, st, p.slots, p.msize, p.moff, info, out, (int64_t)out_cap);
+    hipLaunchKernelGGL(rd_gp_keytab_gz_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, p.moff, (int)K, (int64_t)out_cap, key_tab, info);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
 }
 
 int rd_gz_inflate_members(const uint8_t *comp, int64_t comp_bytes, const rd_gz_member *members, int64_t n, uint8_t *text, int64_t text_bytes,

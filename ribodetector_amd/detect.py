@@ -40,6 +40,9 @@ rd_bam_raw_gather, csrc/rd_bam_raw.hpp), and the output kernels select from THAT
 header of its input, the selected records byte for byte, BGZF members. Classification, report, summary and regions see the FASTQ view.
 --read_groups (an extension, BAM input, with --summary): the chunks carry the same raw view, and every chunk's units are counted per
 read group on the post stream (groups.py: rd_bam_tag_find / rd_bam_group_rows / rd_bam_group_accumulate); the summary gains "read_groups".
+--split_groups (an extension, BAM input, one rank): every output file is a family of files, one per read group and one `unassigned`
+(bam.split_paths); a chunk's records are partitioned by (class, group) key and deflated in ONE device call per mate (gz.DeviceGroupSelect:
+rd_group_keys / rd_group_pack / rd_gz_compress_grouped), and the mate's writer appends every key's run to its file.
 --bam_tags LIST (an extension, BAM input, FASTQ outputs): the chunks carry the raw view, and every chunk gets one more view, the TAGGED
 text - its FASTQ text with the listed tags of every record behind the read name (bamtags.py: rd_bam_tag_splice, csrc/rd_bam_tagtext.hpp;
 bam.tag_comment has the rule). It depends on the chunk alone, so it is made on the copy stream when the chunk is submitted; the output
@@ -158,6 +161,30 @@ class Piece(NamedTuple):
         return (None, 0) if self.fallback is None else self.fallback.take()
 
 
+class GroupPiece(NamedTuple):
+    """Piece's sibling under --split_groups: the bytes that the family files of ONE mate get from the GPU for one chunk, from one grouped
+    call (gz.DeviceGroupSelect). buf holds every key's run, key_tab (pinned int64[K, 4]) says where: key s * (G + 1) + g is member g of
+    the family of class labels[s]. info / kinfo: pinned copies of the int64[4] of the grouped call and of rd_group_keys."""
+    buf: torch.Tensor
+    info: torch.Tensor
+    key_tab: torch.Tensor
+    kinfo: torch.Tensor
+    gz: bool
+    labels: tuple
+
+    def size(self):
+        """the bytes made; raises when the keys or the partition found the chunk's tables wrong"""
+        if int(self.kinfo[0]):
+            raise RuntimeError("device group keys: a label or a read-group row of the chunk is outside its range (flags %d)" % int(self.kinfo[0]))
+        if int(self.info[3]):
+            raise RuntimeError("device group %s: the chunk's keys or record table do not describe its text, or the output did not fit (fault %d)"
+                               % ("gzip" if self.gz else "pack", int(self.info[3])))
+        return int(self.info[0 if self.gz else 1])
+
+
+SPLIT = "groups"            # pieces[(mate, SPLIT)]: the GroupPieces of a mate's family files
+
+
 class MateMismatch(RuntimeError):
     """--interleaved: two consecutive records whose ids are not those of mates (the chunks in front of them have been written)"""
 
@@ -205,7 +232,19 @@ class _MateWriter:
         (event to wait for or None, write)"""
         chunk, labels, pieces = item
         jobs, slot = [], 0
+        for gp in pieces.get((self.e, SPLIT)) or ():      # --split_groups: one fetch per grouped call, an append per key with bytes
+            nb, tab = gp.size(), gp.key_tab.numpy()
+            self.pred._split_counted(self.e, gp.labels, tab[:, 2])
+            if nb:
+                (buf, done), slot = self._fetch(k, slot, gp.buf, nb), slot + 1
+                fams = dict(self.files)
+                handles = [fams[(self.e, lab, g)] for lab in gp.labels for g in range(len(tab) // len(gp.labels))]
+                for kk in np.flatnonzero(tab[:, 1]):
+                    fh = handles[kk]
+                    jobs.append((done, functools.partial(fh.write_members if gp.gz else fh.write_text, buf.data_ptr() + int(tab[kk, 0]), int(tab[kk, 1]))))
         for key, fh in self.files:
+            if len(key) == 3:           # (a family member: served above)
+                continue
             for piece in pieces.get(key) or (None,):
                 p, nb = (None, 0) if piece is None else piece.take()
                 if p is None:           # nothing from the GPU, or too much for its buffer: the host writes the records of this label
@@ -271,6 +310,8 @@ class Predictor:
         self.mate_check = not getattr(args, 'no_mate_check', False)
         self.bam_output = bool(getattr(args, 'bam_output', False))       # BAM outputs: the selected records as they stand in the input
         self.read_groups = bool(getattr(args, 'read_groups', False))     # --summary gains the counters per BAM read group
+        self.split_groups = bool(getattr(args, 'split_groups', False))   # every output file becomes a family: a file per BAM read group
+        self._split = self._split_ids = None     # ... gz.DeviceGroupSelect (run_with_chunks), the declared ids in row order (detect)
         self.bam_shard = bool(getattr(args, 'bam_shard', False))         # BAM input under several ranks: the sharded parse (data_loader/bam_shard.py)
         self._groups = None                      # ... groups.DeviceGroups (run_with_chunks)
         self.bam_tags = _tagmod.parse_list(self.bam_tags_arg) if self.bam_tags_arg is not None else None     # ... the listed names (2 bytes each)
@@ -574,7 +615,8 @@ class Predictor:
                                                want_labels=outs[k][1] is not None, only_multi=True)
             labels = module_arch.pair_fuse(outs[0][0], outs[1][0], self.args.ensure) if self.is_paired else outs[0][1].view(torch.int8)
             tk.labels, tk.host = labels, None if self.gathers_labels else _pinned(labels)
-            tk.pieces = self._select_chunk(chunks, dev_in, labels, lo, hi, on_dev, ring, pairs, tagged)
+            rows1 = self._group_rows(chunks[0]) if self._split is not None else None     # mate 1's rows, once: the split and --read_groups
+            tk.pieces = self._select_chunk(chunks, dev_in, labels, lo, hi, on_dev, ring, pairs, tagged, rows1)
             if self._report is not None:
                 tk.pieces[REPORT] = self._report_chunk(chunks, dev_in, outs, labels, lo, hi, ring, pairs)
             if self._regions:
@@ -586,7 +628,7 @@ class Predictor:
                                                  outs[1][0] if self.is_paired else None, labels.view(torch.int8)))
                 tk.checks["summary"] = functools.partial(self._check_counted, "summary: the chunk's sequence tables or labels", info)
             if self._groups is not None:            # --read_groups: the same units per read group, over the chunks' raw records
-                info = _pinned(self._groups.add(chunks, labels.view(torch.int8), self.interleaved))
+                info = _pinned(self._groups.add(chunks, labels.view(torch.int8), self.interleaved, rows_a=rows1))
                 tk.checks["groups"] = functools.partial(self._check_counted, "read groups: the chunk's labels or group rows", info)
             if self.gathers_labels:                 # label gather (1 B per read) queued behind the kernels, collected later
                 _, tk.finish = rdist.gather_labels(labels, n, dst=0, bounds=bounds, async_op=True)
@@ -595,7 +637,7 @@ class Predictor:
         # what the ticket only keeps alive: the tensors of dev_in (of pairs, of the tagged views; --read_groups: the raw views) were
         # allocated on the copy stream and must not return to that stream's pool while other streams read them - and the deferred
         # float64 pass reads the bases until the post-pass has run
-        tk.keep = (dev_in, outs, plans, pairs, tagged, [c.raw for c in chunks] if self._groups is not None else None)
+        tk.keep = (dev_in, outs, plans, pairs, tagged, [c.raw for c in chunks] if self._groups is not None or self._split is not None else None)
         return tk
 
     def _tag_chunks(self, chunks, on_dev):
@@ -614,12 +656,51 @@ class Predictor:
                 out.append((text, out_start))
         return out
 
-    def _select_chunk(self, chunks, dev_in, labels, lo, hi, on_dev, ring, pairs=None, tagged=None):
+    def _group_rows(self, chunk):
+        """the read-group rows of every raw record of mate 1's chunk (rd_bam_tag_find / rd_bam_group_rows over DeviceChunk.raw)"""
+        if chunk.raw is None:
+            raise RuntimeError("--split_groups: the chunk carries no raw records (BAM input is device ingest only)")
+        raw, rs = chunk.raw
+        return self._split_dict.rows(raw, *_grpmod.tag_find(raw, rs, int(rs.numel()) - 1, _grpmod.TAG))
+
+    def _select_split(self, chunks, dev_in, labels, lo, hi, ring, pairs, tagged, rows):
+        """--split_groups: {(mate, SPLIT): [GroupPiece]} - ONE grouped call per mate (two when a mate's files are part .gz, part
+        plain), over the same three sources as _select_chunk, instead of a call per (mate, label)"""
+        pieces, n, G, lab8 = {}, hi - lo, len(self._split_ids), labels.view(torch.int8)
+        for e, plan in self._split_plan.items():
+            f, pair_table = e if pairs is None else 0, None
+            if self.bam_output:
+                source = chunks[f].raw
+            elif tagged is not None:
+                source = tagged[f]
+            else:
+                source, pair_table = self._fastq_view(chunks, dev_in, e, lo, hi, pairs)
+            text, table, _ = record_view(source, n, lab8, e, pairs is not None, len(self.output), pair_table, lambda lab, m: None)
+            stride = 1 if pairs is None else 2                      # unit u's row is mate 1's: record u, or record 2 u of an interleaved chunk
+            mate = e if pairs is not None and len(self.output) == 2 else -1
+            for gz, slots, labs in plan:
+                keys, kinfo = self._split.keys(rows, lab8, slots, G, 0, stride, mate, slot=(e, gz, ring))
+                call = self._split.compress_grouped if gz else self._split.pack_grouped
+                out, tab, info = call(text, table, keys, len(labs) * (G + 1), slot=(e, gz, ring))
+                pieces.setdefault((e, SPLIT), []).append(GroupPiece(out, _pinned(info), _pinned(tab), _pinned(kinfo), gz, labs))
+        return pieces
+
+    def _split_counted(self, e, labs, records):
+        """the records per key of one grouped call, added to the run's counters (mate e's writer thread)"""
+        G1 = len(self._split_ids) + 1
+        for s, lab in enumerate(labs):
+            self._split_recs[(e, lab)] += records[s * G1:(s + 1) * G1]
+
+    def _select_chunk(self, chunks, dev_in, labels, lo, hi, on_dev, ring, pairs=None, tagged=None, rows1=None):
         """{(mate, label): [Piece]}: the label files whose records of this chunk are selected on the device, on the post stream beside
         the next chunk's recurrences, so that only the selected bytes travel to the host. A chunk whose text lives on the device: every
         file's, deflated (.gz outputs: BGZF members, csrc/rd_deflate.hpp) or packed into one text (rd_select_pack). Otherwise the .gz
         outputs' only - under the label gather: of this rank's shard (reference: gzip.open(..., compresslevel=5) on the host,
         detect.py:729-741). Every rank takes the same decision (the chunks of a shared decode are the same chunks)."""
+        if self._split is not None:
+            if not on_dev:
+                raise RuntimeError("--split_groups: the chunk's text is not on the device (BAM input is device ingest only)")
+            return self._select_split(chunks, dev_in, labels, lo, hi, ring, pairs, tagged, rows1)
         if on_dev:
             files = self._out_files
         elif self._gz_files and all(c.tensors is not None and len(c.tensors) > 3 and c.verbatim for c in chunks):
@@ -788,7 +869,7 @@ class Predictor:
                 if arena is None and self._device_parse(path):
                     st = self.ingest.setdefault(os.path.basename(str(path)), {"path": "device"})
                     stream = dr.get_seq_chunks_device(path, chunk_size=chunk_reads, byte_range=byte_range, first_chunk=first, schedule=schedule,
-                                                      device=self.device, stats=st, keep_raw=self.bam_output or self.read_groups or self.bam_tags is not None,
+                                                      device=self.device, stats=st, keep_raw=self.bam_output or self.read_groups or self.split_groups or self.bam_tags is not None,
                                                       rank=self.rank if self.sharded_parse else None)
                 # one plain input file: its parser thread was the slowest stage of the pipeline - two readers over byte segments,
                 # small first chunks (mate files keep one reader each and exact chunk sizes: their chunks must pair up)
@@ -1028,6 +1109,8 @@ class Predictor:
                 self.logger.info(_tagmod.log_line(self.bam_tags, self._tag_total))
         if self.interleaved:
             fx.check_even_records(self._records_seen)
+        if self._split is not None:
+            self._split_total = self._finish_split(sum(1 for key, _, _ in files if len(key) == 3))
         mates = range(2 if self.is_paired else 1)
         if self._windows is not None:              # every rank classified the windows of its own shard / byte range
             total = self._sum_ranks(self._win_classified, self.multi)
@@ -1045,6 +1128,22 @@ class Predictor:
                     " + ".join(str(x) for x in self._reg_total[1])))
         if self._summary is not None:
             self._write_summary()
+
+    def _finish_split(self, n_files):
+        """--split_groups, at the end of a run that went well: the records every family received, summed over the chunks, against the
+        run's own counts per class - a file of a mate gets one record per unit of its class -; the log line; the summary's object"""
+        want = {0: self.num_nonrrna, 1: self.num_rrna, -1: self.num_unknown}
+        for (e, lab), recs in sorted(self._split_recs.items()):
+            if int(recs.sum()) != want[lab]:
+                raise RuntimeError("--split_groups: the files of mate {} for label {} received {} records, the run counted {} units".format(
+                    e + 1, lab, int(recs.sum()), want[lab]))
+        G = len(self._split_ids)
+        # units by class in the unassigned member (mate 1's files; None: the run writes no file for the class)
+        un = {name: (int(self._split_recs[(0, lab)][G]) if (0, lab) in self._split_recs else None)
+              for name, lab in (("unclassified", -1), ("nonrRNA", 0), ("rRNA", 1))}
+        self.logger.info('Split outputs: {} read groups + unassigned, {} files; {} reads unassigned'.format(
+            G, n_files, sum(v for v in un.values() if v is not None)))
+        return {"groups": G, "files": n_files, "unassigned": un}
 
     def _write_summary(self):
         """--summary, at the end of a run that went well (every output file is closed): the ranks' counters summed, checked against
@@ -1077,6 +1176,8 @@ class Predictor:
             rg = doc["read_groups"] = _grpmod.to_json(gacc, grp.groups, bool(self.is_paired), input=self.input[0])
         if self._tags is not None:
             doc["bam_tags"] = _tagmod.to_json(self.bam_tags, self._tag_total, floats=self.bam_tag_floats)
+        if self._split is not None:
+            doc["split_groups"] = self._split_total
         _summod.write_json(path, doc)
         frac = doc["reads"]["rRNA_fraction"]
         self.logger.info('rRNA fraction: {} (summary: {})'.format("n/a" if frac is None else "%.6f" % frac, path))
@@ -1180,10 +1281,14 @@ class Predictor:
         log = self.logger.info if self.rank == 0 else (lambda *a, **k: None)
 
         def open_(label, paths):               # one file per mate: keys (mate, label); the report's is REPORT
-            for e, path in enumerate(paths):
+            split = self._split_ids is not None and label in (0, 1, -1)       # --split_groups: a family of files per label file
+            members = [(e, g, m) for e, path in enumerate(paths) for g, m in enumerate(_bammod.split_paths(path, self._split_ids))] if split \
+                else [(e, None, path) for e, path in enumerate(paths)]
+            for e, g, path in members:
                 if self.sharded_parse:
                     self._part_files.append(part_path(path, self.rank))
-                files.append(((e, label), path, fx.open_for_write(self._part_files[-1] if self.sharded_parse else path)))
+                files.append(((e, label) if g is None else (e, label, g), path,
+                              fx.open_for_write(self._part_files[-1] if self.sharded_parse else path)))
                 if self.sharded_parse:         # parts are joined later: the joined file gets ONE BGZF end-of-file block, at its end
                     files[-1][2].set_eof_marker(False)
                 # a BAM output starts with the header of its mate's input, byte for byte (the sharded parse: rank 0's part comes first)
@@ -1237,6 +1342,26 @@ class Predictor:
         self._summary = _summod.DeviceSummary(self.device) if self.summary_path else None
         # --read_groups: the same units per read group of mate 1's BAM, one more int64 array that every chunk adds to
         self._groups = _grpmod.DeviceGroups(self.device, _bammod.header(self.input[0])) if self.read_groups else None
+        # --split_groups: per mate the grouped calls of its family files - (gzip?, class_slot, labels in slot order) - and the counters
+        if self._split_ids is not None:
+            G, gzset = len(self._split_ids), set(self.gz_output_files(self.output, self.rrna, self.is_paired, self.args.ensure))
+            if gzset and not self.gzip_on_device:
+                raise RuntimeError("--split_groups: compressed family files are deflated on the device only (kernel.gzip / RD_DEVICE_GZIP = host)")
+            self._split = _gzmod.DeviceGroupSelect(self.device)
+            self._split_dict = self._groups.dict if self._groups is not None else _grpmod.Dictionary(self.device, self._split_ids)
+            self._split_plan, self._split_recs = {}, {}
+            for e in sorted({key[0] for key in out_files}):
+                labs_e = [key[1] for key in out_files if key[0] == e and key[2] == 0]
+                self._split_plan[e] = []
+                for gz in (True, False):
+                    labs = tuple(lab for lab in labs_e if ((e, lab) in gzset) == gz)
+                    if labs:
+                        slots = [-1, -1, -1]
+                        for k, lab in enumerate(labs):
+                            slots[lab + 1] = k
+                        self._split_plan[e].append((gz, slots, labs))
+                for lab in labs_e:
+                    self._split_recs[(e, lab)] = np.zeros(G + 1, dtype=np.int64)
         # --bam_tags: the tagged view of every chunk, and the counters of the tags copied, per input file
         self._tags = [_tagmod.DeviceBamTags(self.device, self.bam_tags, floats=self.bam_tag_floats) for _ in self.input] if self.bam_tags is not None else None
         self._win_classified = [0, 0]
@@ -1333,6 +1458,8 @@ class Predictor:
         check_summary(self.summary_path, self.output, self.rrna, self.is_paired, self.args.ensure, self.report_path, self.bam_output)
         check_read_groups(self.read_groups, self.summary_path, self.input, self.bam_shard)
         check_bam_tags(self.bam_tags_arg, self.input, self.bam_output, floats=self.bam_tag_floats)
+        self._split_ids = check_split_groups(self.split_groups, self.input, self.output, self.rrna, self.args.ensure, self.report_path,
+                                             self.summary_path, self.regions_path, self.bam_output, self.interleaved)
         self._windows = check_windows(self.args)
         check_regions(self.regions_path, self._windows is not None, self.output, self.rrna, self.is_paired, self.args.ensure,
                       self.report_path, self.summary_path, self.bam_output)
@@ -1531,6 +1658,73 @@ def check_read_groups(read_groups, summary, inputs, bam_shard=False):
     return _grpmod.check_groups(header)
 
 
+SPLIT_FD_MARGIN = 64        # open files a run needs besides its outputs: inputs, libraries, the device, pipes
+
+
+def split_families(output, rrna, paired_out, ensure, bam_output=False):
+    """[(label, [path per mate])] of the output files of a run in the order _open_outputs opens them: -r, -o, and under -e both with
+    pairs the unclassified files"""
+    fams = ([(1, list(rrna))] if rrna else []) + [(0, list(output or []))]
+    if paired_out and ensure == 'both':
+        fams.append((-1, [unclassified_path(o, bam_output) for o in output or []]))
+    return fams
+
+
+def check_split_groups(split_groups, inputs, output, rrna, ensure, read_report=None, summary=None, regions=None, bam_output=False, interleaved=False):
+    """--split_groups: the rules that hold before anything touches a device; returns the declared ids in the order of the device's
+    rows (bam.sorted_ids), or None without the flag. Every output file becomes bam.split_paths(path, ids)."""
+    if not split_groups:
+        return None
+    late = " (checked before anything touches a device)"
+
+    def fmt(path):
+        try:
+            return fx.get_seq_format(path)
+        except ValueError:
+            return None
+    if not inputs or any(fmt(p) != "bam" for p in inputs):
+        raise RuntimeError("--split_groups writes one set of files per RG tag of BAM records: every -i file must end with .bam or .ubam, got {}{}".format(
+            ", ".join(str(p) for p in inputs or []), late))
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("--split_groups under several ranks is not implemented: run on one rank" + late)
+    try:
+        header = _bammod.header(inputs[0])
+    except (OSError, ValueError) as e:
+        raise RuntimeError("--split_groups: cannot read the header of {}: {}{}".format(inputs[0], e, late))
+    try:
+        groups = _bammod.read_groups(header)
+    except ValueError as e:
+        raise RuntimeError("--split_groups: {}{}".format(e, late))
+    if len(groups) > _bammod.SPLIT_GROUPS_MAX:
+        raise RuntimeError("--split_groups: the header declares {} read groups, more than {}{}".format(len(groups), _bammod.SPLIT_GROUPS_MAX, late))
+    ids, _ = _bammod.sorted_ids([g[0] for g in groups])
+    paired_out = len(inputs) == 2 or interleaved
+    names = {}
+    for what, path in (("--read_report", read_report), ("--summary", summary), ("--regions", regions)):
+        if path:
+            names.setdefault(os.path.abspath(path), []).append(what)
+    n_files = 0
+    for label, paths in split_families(output, rrna, paired_out, ensure, bam_output):
+        for path in paths:
+            if path.endswith('gz') and os.environ.get("RD_DEVICE_GZIP") == "host":
+                raise RuntimeError("--split_groups: the members of {} are deflated on the device only: it cannot run with RD_DEVICE_GZIP=host "
+                                   "(a host writer per file would hold a set of compressors per file){}".format(path, late))
+            for member in _bammod.split_paths(path, ids):
+                if len(os.fsencode(os.path.basename(member))) > 255:
+                    raise RuntimeError("--split_groups: the file name {} is longer than 255 bytes{}".format(os.path.basename(member), late))
+                names.setdefault(os.path.abspath(member), []).append(member)
+                n_files += 1
+    for key, who in names.items():
+        if len(who) > 1:
+            raise RuntimeError("--split_groups: two files of the run have the same name {}: {}{}".format(key, " and ".join(who), late))
+    import resource
+    soft = resource.getrlimit(resource.RLIMIT_NOFILE)[0]
+    if soft != resource.RLIM_INFINITY and n_files + SPLIT_FD_MARGIN > soft:
+        raise RuntimeError("--split_groups: the run writes {} files and needs {} open files, the limit is {}: raise it with ulimit -n{}".format(
+            n_files, n_files + SPLIT_FD_MARGIN, soft, late))
+    return ids
+
+
 def check_windows(args):
     """--windows and its settings, checked before anything touches a device: None without the flag, else {"stride" (None = -l),
     "max_per_read", "fuse"}. RuntimeError for a setting without --windows, a stride outside 1..2^31-1 or more than 4096 (or fewer than
@@ -1644,6 +1838,13 @@ none: give label based on the mean probability of read pair.
                            'mate 1\'s group), and for the records without RG, with an RG that no @RG line declares, and with malformed\n'
                            'tags. Counted on the GPU over the records as they stand in the input, which the run then keeps in GPU\n'
                            'memory next to the FASTQ text (about 0.75 of its bytes more).')
+    args.add_argument('--split_groups', action='store_true',
+                      help='(extension) BAM input, one rank: every output file becomes a family of files, one per @RG line of the header of\n'
+                           'the first -i file and one for the rest: non.fq.gz -> non.rg-<id>.fq.gz ... and non.unassigned.fq.gz (bytes of an\n'
+                           'id outside A-Z a-z 0-9 . _ + = @ , - are written %%XX). A read or pair goes to the member of MATE 1\'s RG:Z tag;\n'
+                           'no RG, an undeclared value and malformed tags go to unassigned. Inside every file the records are in input\n'
+                           'order and are the bytes the unsplit run writes. Every member is always written. Partitioned and deflated\n'
+                           'on the GPU in one call per mate and chunk; the run keeps the records as they stand in the input in GPU memory.')
     args.add_argument('--bam_shard', action='store_true',
                       help='(extension) BAM input under several ranks (torch.distributed.run): every rank inflates, frames, classifies and\n'
                            'writes its own share of the records, like the ranks of a BGZF FASTQ run. The shares begin at record starts\n'
@@ -1672,6 +1873,9 @@ def main(argv=None, log_level=None):
     config = ConfigParser.from_json(config_file)
     check_windows(args)                          # (before the model is loaded: nothing has touched a device yet)
     check_regions(args.regions, args.windows)    # (args is the parser's own Namespace: every option is there)
+    # (in front of check_bam: several ranks are refused for the split as such, with or without --bam_shard)
+    check_split_groups(args.split_groups, args.input, args.output, args.rrna, args.ensure, args.read_report, args.summary, args.regions,
+                       args.bam_output, args.interleaved)
     check_bam(args.input, args.output, args.rrna, args.bam_output, args.bam_shard, args.interleaved)
     check_read_groups(args.read_groups, args.summary, args.input, args.bam_shard)
     check_bam_tags(args.bam_tags, args.input, args.bam_output, floats=args.bam_tag_floats)

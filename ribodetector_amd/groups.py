@@ -121,17 +121,18 @@ class DeviceGroups:
     def rows(self, raw, raw_start, n_rec):
         return self.dict.rows(raw, *tag_find(raw, raw_start, n_rec, TAG))
 
-    def add(self, chunks, labels, interleaved=False):
+    def add(self, chunks, labels, interleaved=False, rows_a=None):
+        """rows_a: the rows of mate 1's chunk where the caller has them already (rows(*chunks[0].raw, records))"""
         n = int(labels.numel())
         views = []
-        for c in chunks:
+        for k, c in enumerate(chunks):
             if c.raw is None:
                 raise RuntimeError("DeviceGroups.add: the chunk carries no raw records (the reader must run with keep_raw)")
             raw, rs = c.raw
             n_rec = int(rs.numel()) - 1
             if n_rec < (2 * n if interleaved else n):
                 raise RuntimeError("DeviceGroups.add: the chunk holds %d raw records for %d units" % (n_rec, n))
-            views.append((raw, rs, self.rows(raw, rs, n_rec)))
+            views.append((raw, rs, rows_a if k == 0 and rows_a is not None else self.rows(raw, rs, n_rec)))
         if interleaved:
             a, b = views[0] + (0, 2), views[0] + (1, 2)
         else:

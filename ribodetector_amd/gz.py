@@ -123,6 +123,62 @@ class DeviceSelect:
         return out, info
 
 
+class DeviceGroupSelect:
+    """The records of a chunk partitioned by key (C ABI rd_group_keys / rd_group_pack / rd_gz_compress_grouped, csrc/rd_group_pack.hpp):
+    ONE call per mate and chunk writes the records of every key 0 .. K - 1, in input order, as a run of text (pack_grouped) or of BGZF
+    members (compress_grouped) per key, the runs in key order. keys(rows, labels, class_slot, G, ...) makes the int32 keys of a run
+    that splits every class's file by read group. Both return (out, key_tab, info): out a device uint8 buffer owned by this object
+    until the next call with the same `slot` - a ring slot per (mate, ring) -, key_tab int64[K, 4] and info int64[4] on the device
+    (include/ribodetector_amd.h has the columns). Buffers grow on demand. Asynchronous on the current stream."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._ws = None
+        self._out = {}
+        self._keys = {}
+
+    def keys(self, rows, labels, class_slot, G, first=0, stride=1, mate=-1, slot=0):
+        n = int(labels.numel())
+        if rows.dtype != torch.int32 or not rows.is_contiguous() or (n and rows.numel() < first + stride * (n - 1) + 1):
+            raise TypeError("DeviceGroupSelect.keys: rows must be a contiguous int32 tensor that holds entry first + stride * (n - 1)")
+        if labels.dtype not in (torch.int8, torch.uint8) or not labels.is_contiguous():
+            raise TypeError("DeviceGroupSelect.keys: labels must be a contiguous int8 / uint8 tensor")
+        m = n if mate < 0 else 2 * n
+        out = _grown(self._keys, (slot, mate), m, lambda: torch.empty(max(m, 2048), dtype=torch.int32, device=self.device))
+        info = torch.empty(4, dtype=torch.int64, device=self.device)
+        slots = (C.c_int32 * 3)(*[int(x) for x in class_slot])
+        with torch.cuda.device(self.device):
+            N.check(N.lib().rd_group_keys(N.ptr(rows), int(first), int(stride), int(mate), N.ptr(labels), n, slots, int(G), N.ptr(out), N.ptr(info),
+                                          N.stream_ptr(self.device)), "rd_group_keys")
+        return out[:m], info
+
+    def _call(self, fn, gz, text, rec_start, keys, K, slot, cap):
+        lib = N.lib()
+        n, tb = int(keys.numel()), int(text.numel())
+        _check_tables(fn, text, rec_start, "n", n)
+        if keys.dtype != torch.int32 or not keys.is_contiguous() or text.dtype != torch.uint8:
+            raise TypeError("%s: keys must be a contiguous int32 tensor and text uint8" % fn)
+        need = int(lib.rd_group_workspace_bytes(n, tb, int(K), gz))
+        if need == 0:
+            raise ValueError("%s: n = %d, K = %d: outside what the device call takes (K <= %d)" % (fn, n, K, N.GROUP_KEYS_MAX))
+        ws = _grown(self, "_ws", need, lambda: torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=self.device))
+        out = _grown(self._out, slot, cap, lambda: torch.empty(cap, dtype=torch.uint8, device=self.device))
+        key_tab = torch.empty((int(K), 4), dtype=torch.int64, device=self.device)
+        info = torch.empty(4, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(getattr(lib, fn)(N.ptr(text), tb, N.ptr(rec_start), N.ptr(keys), n, int(K), N.ptr(out), out.numel(), N.ptr(key_tab), N.ptr(info),
+                                     N.ptr(ws), ws.numel(), N.stream_ptr(self.device)), fn)
+        return out, key_tab, info
+
+    def pack_grouped(self, text, rec_start, keys, K, slot=0):
+        """every run starts on a multiple of 16 bytes: the text and 16 bytes per key always hold them"""
+        return self._call("rd_group_pack", 0, text, rec_start, keys, K, slot, int(text.numel()) + 16 * int(K) + 256)
+
+    def compress_grouped(self, text, rec_start, keys, K, slot=0):
+        return self._call("rd_gz_compress_grouped", 1, text, rec_start, keys, K, slot,
+                          max(int(N.lib().rd_gz_grouped_out_bound(int(text.numel()), int(K))), 256))
+
+
 class DevicePairSplit:
     """Paired-end reads from ONE interleaved chunk (C ABI rd_pair_split / rd_pair_expand_labels, csrc/rd_pairs.hpp): records 2k and
     2k + 1 of the chunk's 2n records are the mates of pair k. split(text, rec_start, seq_off, seq_len, n_pairs) returns (pair_start
