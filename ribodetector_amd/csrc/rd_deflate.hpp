@@ -7,7 +7,7 @@
 // cores - 13-20 % of the device rate, flat in the GPU count. Here the chunk's records of one label become gzip members without
 // leaving the device; the host appends the compressed bytes to the file.
 //
-//   rd_scan_* / rd_gz_pack_kernel     selected records -> one contiguous byte stream (scan of the selected lengths, rd_scan.hpp, + coalesced copy)
+//   rd_scan_* / rd_pack_kernel        selected records -> one contiguous byte stream (scan of the selected lengths, rd_scan.hpp, + coalesced copy)
 //   rd_gz_deflate_kernel              one workgroup per member of 65,280 input bytes (BGZF's block size: the file is valid BGZF -
 //                                     bgzip / htslib index it, this build's reader inflates its members in parallel):
 //        wave w owns part w of the member (4,080 bytes: a sixteenth) and its own hash table in LDS (seeded with the last 512 bytes of the
@@ -68,41 +68,72 @@ struct GzSelLen {                       // the length of record i when it is sel
     __device__ __forceinline__ int64_t operator()(int, int64_t i) const { return labels[i] == (int8_t)label ? rec_start[i + 1] - rec_start[i] : 0; }
 };
 
-// selected records -> plain[out_off[i] ...): a workgroup takes 256 consecutive records, whose output range is contiguous, and its
-// threads take 16-byte pieces of that range (a piece finds its record by bisection over the 257 staged offsets)
+// ------------------------------------------------------------------------------------------------
+// the pack: place j -> dst[begin(j) ...), for both callers (the places of a selection, or of rd_group_pack.hpp's permuted order)
+// ------------------------------------------------------------------------------------------------
+// A workgroup takes 256 consecutive places, whose destinations ascend, and its threads take the 16-byte pieces of [first begin, last
+// end): a piece finds its record by bisection over the staged begins; a piece inside one record is one unaligned 16-byte load and one
+// aligned store, any other a byte loop. WHICH places there are says a provider (as GzSelLen says which lengths):
+//   places()            how many
+//   src(j), begin(j)    where place j's bytes start in the text, and in dst
+//   len(j)              their number - asked only where GAPS says that a gap may lie between two consecutive places (a piece in a gap
+//                       writes nothing); without gaps place j ends where place j + 1 begins, and begin(places()) is the end of the last
 constexpr int GZ_PACK_RECS = 256;
-__global__ __launch_bounds__(256) void rd_gz_pack_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ rec_start,
-                                                        const int64_t *__restrict__ out_off, int64_t n, uint8_t *__restrict__ plain,
-                                                        const int64_t *__restrict__ info) {
-    __shared__ int64_t offs[GZ_PACK_RECS + 1];
-    __shared__ int64_t srcs[GZ_PACK_RECS];
+struct GzSelPlaces {                    // the records of a selection: record j -> out_off[j], the scan of the selected lengths
+    static constexpr bool GAPS = false;
+    const int64_t *rec_start, *out_off;
+    int64_t n;
+    __device__ __forceinline__ int64_t places() const { return n; }
+    __device__ __forceinline__ int64_t src(int64_t j) const { return rec_start[j]; }
+    __device__ __forceinline__ int64_t begin(int64_t j) const { return out_off[j]; }
+};
+template <bool GAPS>
+struct GzPackStage {                    // begin, source and - with gaps - end of a workgroup's places, in LDS
+    int64_t begs[GZ_PACK_RECS + (GAPS ? 0 : 1)], ends[GAPS ? GZ_PACK_RECS : 0], srcs[GZ_PACK_RECS];
+    __device__ __forceinline__ int64_t end(int r) const { return GAPS ? ends[r] : begs[r + 1]; }
+};
+
+template <class Places>
+__global__ __launch_bounds__(256) void rd_pack_kernel(const uint8_t *__restrict__ text, const Places pl, uint8_t *__restrict__ dst,
+                                                     const int64_t *__restrict__ info) {
+    constexpr bool GAPS = Places::GAPS;
+    __shared__ GzPackStage<GAPS> S;
     if (info[3]) return;
+    const int64_t M = pl.places();
     const int64_t r0 = (int64_t)blockIdx.x * GZ_PACK_RECS;
-    const int nr = (int)(n - r0 < GZ_PACK_RECS ? n - r0 : GZ_PACK_RECS);
-    for (int k = threadIdx.x; k <= nr; k += 256) offs[k] = out_off[r0 + k];
-    for (int k = threadIdx.x; k < nr; k += 256) srcs[k] = rec_start[r0 + k];
+    if (r0 >= M) return;
+    const int nr = (int)(M - r0 < GZ_PACK_RECS ? M - r0 : GZ_PACK_RECS);
+    if ((int)threadIdx.x < nr) {
+        const int64_t j = r0 + threadIdx.x, b = pl.begin(j);
+        S.begs[threadIdx.x] = b;
+        S.srcs[threadIdx.x] = pl.src(j);
+        if constexpr (GAPS) S.ends[threadIdx.x] = b + pl.len(j);
+    }
+    if (!GAPS && threadIdx.x == 255) S.begs[nr] = pl.begin(r0 + nr);
     __syncthreads();
-    const int64_t ob = offs[0], oe = offs[nr];
+    const int64_t ob = S.begs[0], oe = S.end(nr - 1);
     for (int64_t o = (ob & ~(int64_t)15) + 16 * (int64_t)threadIdx.x; o < oe; o += 16 * 256) {
         int64_t a = o < ob ? ob : o;                    // the piece is [a, e) (its neighbours in other workgroups write the rest)
         const int64_t e = o + 16 < oe ? o + 16 : oe;
-        int lo = 0, hi = nr;                            // largest r with offs[r] <= a (records of zero length share an offset:
-        while (hi - lo > 1) {                           // the LAST of them is the one that holds byte a)
+        int lo = 0, hi = nr;                            // largest r with begs[r] <= a (records of zero length share a begin: the
+        while (hi - lo > 1) {                           // LAST of them is the one that can hold byte a)
             const int mid = (lo + hi) >> 1;
-            if (offs[mid] <= a) lo = mid; else hi = mid;
+            if (S.begs[mid] <= a) lo = mid; else hi = mid;
         }
         int r = lo;
-        if (a == o && e == o + 16 && offs[r + 1] >= e) {   // a whole piece from one record: one unaligned 16-byte load, one aligned store
+        if (a == o && e == o + 16 && S.end(r) >= e) {   // a whole piece from one record: one unaligned 16-byte load, one aligned store
             u32x4 v;
-            __builtin_memcpy(&v, text + srcs[r] + (a - offs[r]), 16);
-            *reinterpret_cast<u32x4 *>(plain + o) = v;
+            __builtin_memcpy(&v, text + S.srcs[r] + (a - S.begs[r]), 16);
+            *reinterpret_cast<u32x4 *>(dst + o) = v;
             continue;
         }
         while (a < e) {
-            while (offs[r + 1] <= a) ++r;
-            const int64_t stop = offs[r + 1] < e ? offs[r + 1] : e;
-            const uint8_t *src = text + srcs[r] + (a - offs[r]);
-            for (; a < stop; ++a) plain[a] = *src++;
+            while ((!GAPS || r < nr) && S.end(r) <= a) ++r;
+            if (GAPS && r == nr) break;
+            if (GAPS && S.begs[r] > a) { a = S.begs[r]; continue; }     // (a gap between two keys' runs)
+            const int64_t stop = S.end(r) < e ? S.end(r) : e;
+            const uint8_t *src = text + S.srcs[r] + (a - S.begs[r]);
+            for (; a < stop; ++a) dst[a] = *src++;
         }
     }
 }

@@ -20,8 +20,8 @@
 //                          (text) or of the member size (gzip: member m of the padded stream is still plain + 65,280 m, and only
 //                          its LENGTH comes from the per-member table written here)
 //   rd_gp_mlen_kernel      gzip: the per-member lengths from the keys' table, a thread per member
-//   rd_gp_pack_kernel      256 consecutive records of the permuted order per workgroup, 16-byte pieces by bisection over the staged
-//                          destinations (rd_gz_pack_kernel's scheme; the records are read through the permutation)
+//   rd_pack_kernel<GpPermPlaces>   the pack kernel of rd_deflate.hpp over the places of the permuted order: 256 consecutive places per
+//                          workgroup, 16-byte pieces by bisection over the staged destinations, nothing written into the gaps between runs
 //   rd_gz_deflate_kernel<GzTableLen>, rd_gz_moff_kernel, rd_gz_compact_kernel   the members, as in rd_gz_compress_selected: the
 //                          compact stream is in key order already; rd_gp_keytab_gz_kernel turns member offsets into the keys' table
 #pragma once
@@ -232,53 +232,18 @@ __global__ __launch_bounds__(256) void rd_gp_keytab_gz_kernel(const int64_t *__r
 // ------------------------------------------------------------------------------------------------
 // the pack: place j of the permuted order -> dst[L[j] + shift[key] ...)
 // ------------------------------------------------------------------------------------------------
-// A workgroup takes 256 consecutive places; their destinations ascend, with a gap where the key changes (up to the next multiple of
-// 16, or of the member size). Its threads take the 16-byte pieces of [first begin, last end): a piece finds its record by bisection
-// over the staged begins; a piece that lies in a gap writes nothing.
-__global__ __launch_bounds__(256) void rd_gp_pack_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ rec_start,
-                                                        const int32_t *__restrict__ keys, const int32_t *__restrict__ perm,
-                                                        const int64_t *__restrict__ L, const int64_t *__restrict__ shift,
-                                                        const int64_t *__restrict__ placed, uint8_t *__restrict__ dst,
-                                                        const int64_t *__restrict__ info) {
-    __shared__ int64_t begs[GZ_PACK_RECS], ends[GZ_PACK_RECS], srcs[GZ_PACK_RECS];
-    if (info[3]) return;
-    const int64_t M = *placed;
-    const int64_t r0 = (int64_t)blockIdx.x * GZ_PACK_RECS;
-    if (r0 >= M) return;
-    const int nr = (int)(M - r0 < GZ_PACK_RECS ? M - r0 : GZ_PACK_RECS);
-    if ((int)threadIdx.x < nr) {
-        const int64_t j = r0 + threadIdx.x, p = perm[j];
-        const int64_t s = rec_start[p], b = L[j] + shift[keys[p]];
-        begs[threadIdx.x] = b;
-        ends[threadIdx.x] = b + (rec_start[p + 1] - s);
-        srcs[threadIdx.x] = s;
-    }
-    __syncthreads();
-    const int64_t ob = begs[0], oe = ends[nr - 1];
-    for (int64_t o = (ob & ~(int64_t)15) + 16 * (int64_t)threadIdx.x; o < oe; o += 16 * 256) {
-        int64_t a = o < ob ? ob : o;                    // the piece is [a, e) (its neighbours in other workgroups write the rest)
-        const int64_t e = o + 16 < oe ? o + 16 : oe;
-        int lo = 0, hi = nr;                            // largest r with begs[r] <= a (records of zero length share a begin: the
-        while (hi - lo > 1) {                           // LAST of them is the one that can hold byte a)
-            const int mid = (lo + hi) >> 1;
-            if (begs[mid] <= a) lo = mid; else hi = mid;
-        }
-        int r = lo;
-        if (a == o && e == o + 16 && ends[r] >= e) {    // a whole piece from one record: one unaligned 16-byte load, one aligned store
-            u32x4 v;
-            __builtin_memcpy(&v, text + srcs[r] + (a - begs[r]), 16);
-            *reinterpret_cast<u32x4 *>(dst + o) = v;
-            continue;
-        }
-        while (a < e) {
-            while (r < nr && ends[r] <= a) ++r;
-            if (r == nr) break;
-            if (begs[r] > a) { a = begs[r]; continue; } // (a gap between two keys' runs)
-            const int64_t stop = ends[r] < e ? ends[r] : e;
-            const uint8_t *src = text + srcs[r] + (a - begs[r]);
-            for (; a < stop; ++a) dst[a] = *src++;
-        }
-    }
-}
+// rd_pack_kernel's places (rd_deflate.hpp): the records that have a key, read through the permutation. Their destinations ascend, with
+// a gap where the key changes (up to the next multiple of 16, or of the member size).
+struct GpPermPlaces {
+    static constexpr bool GAPS = true;
+    const int64_t *rec_start;
+    const int32_t *keys, *perm;
+    const int64_t *L, *shift;
+    const int64_t *placed;              // pos[K * parts]: the records that have a key
+    __device__ __forceinline__ int64_t places() const { return *placed; }
+    __device__ __forceinline__ int64_t src(int64_t j) const { return rec_start[perm[j]]; }
+    __device__ __forceinline__ int64_t begin(int64_t j) const { return L[j] + shift[keys[perm[j]]]; }
+    __device__ __forceinline__ int64_t len(int64_t j) const { return rec_start[perm[j] + 1] - rec_start[perm[j]]; }
+};
 
 }  // namespace

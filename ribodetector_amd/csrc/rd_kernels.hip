@@ -603,15 +603,59 @@ int rd_pack_onehot(const uint8_t *arena, const int64_t *seq_off, const int32_t *
 
 // ---- device-side gzip of the label-partitioned records (rd_deflate.hpp) ------------------------------------------------------------
 namespace {
+// the member stage of both gzip entry points: the stream to deflate (member m starts at plain + 65,280 m), the token scratch of the
+// deflate kernel's workgroups, a slot and a size per member, the members' offsets in `out`
+struct GzMembers {
+    int64_t cap_members;    // members the stream can have at most
+    int grid;               // workgroups of the deflate kernel
+    uint8_t *plain, *slots;
+    uint32_t *toks, *msize;
+    int64_t *moff;
+};
+GzMembers gz_members(Carver &c, int64_t cap_members) {
+    GzMembers m{cap_members, (int)(cap_members < GZ_MAX_GRID ? cap_members : GZ_MAX_GRID)};
+    m.plain = c.take<uint8_t>((size_t)cap_members * GZ_MEMBER + 256);
+    m.toks = c.take<uint32_t>((size_t)m.grid * GZ_MEMBER);
+    m.slots = c.take<uint8_t>((size_t)cap_members * GZ_SLOT);
+    m.msize = c.take<uint32_t>((size_t)cap_members);
+    m.moff = c.take<int64_t>((size_t)cap_members);
+    return m;
+}
+// the members of m.plain (their lengths: ml) deflated, and compacted into `out`; info = (compressed bytes, text bytes, members, fault)
+extern "C++" template <class MemberLen>      // (inside the C ABI's extern "C": a template needs C++ linkage)
+void gz_deflate_members(const GzMembers &m, const MemberLen ml, int64_t *info, uint8_t *out, size_t out_cap, hipStream_t st) {
+    hipLaunchKernelGGL(rd_gz_deflate_kernel<MemberLen>, dim3(m.grid), dim3(GZ_THREADS), 0, st, m.plain, ml, m.toks, m.slots, m.msize);
+    hipLaunchKernelGGL(rd_gz_moff_kernel, dim3(1), dim3(256), 0, st, m.msize, m.moff, info);
+    hipLaunchKernelGGL(rd_gz_compact_kernel, dim3(m.grid), dim3(256), 0, st, m.slots, m.msize, m.moff, info, out, (int64_t)out_cap);
+}
+
+// What the four pack entry points (`fn`) refuse, and their n == 0 answer (info zeroed; the grouped ones - key_tab's K rows belong to
+// them - zero the keys' table too). `sel`: the labels or the keys; `need`: the bytes of the caller's workspace; `out` must be
+// out_align-byte aligned. The caller goes on only when this returned RD_OK and n > 0.
+int pack_check(const char *fn, bool grouped, const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const void *sel, int64_t n, int32_t label_or_K,
+               const uint8_t *out, unsigned out_align, int64_t *key_tab, int64_t *info, const void *workspace, size_t workspace_bytes, size_t need, hipStream_t st) {
+    if (n < 0 || n > 0x7fffffffLL || text_bytes < 0) RD_FAIL(RD_E_INVALID, "%s: bad n or text_bytes", fn);
+    if (grouped && (label_or_K < 1 || label_or_K > RD_GROUP_KEYS_MAX)) RD_FAIL(RD_E_INVALID, "%s: K = %d is outside 1..%d", fn, label_or_K, RD_GROUP_KEYS_MAX);
+    if (!info || (grouped && !key_tab)) RD_FAIL(RD_E_INVALID, grouped ? "%s: null info or key_tab" : "%s: null info", fn);
+    if (!grouped && (label_or_K < -128 || label_or_K > 127)) RD_FAIL(RD_E_INVALID, "%s: label %d is not an int8 value", fn, label_or_K);
+    if (n == 0) {
+        RD_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int64_t), st));
+        if (grouped) RD_HIP(hipMemsetAsync(key_tab, 0, (size_t)label_or_K * 4 * sizeof(int64_t), st));
+        return RD_OK;
+    }
+    if ((!text && text_bytes > 0) || !rec_start || !sel || !out || !workspace) RD_FAIL(RD_E_INVALID, "%s: null pointer", fn);
+    if (((uintptr_t)workspace & 255) || ((uintptr_t)out & (out_align - 1)))
+        RD_FAIL(RD_E_INVALID, "%s: workspace must be 256-byte aligned, out %u-byte aligned", fn, out_align);
+    if (workspace_bytes < need) RD_FAIL(RD_E_WORKSPACE, "%s: workspace too small: %zu < %zu", fn, workspace_bytes, need);
+    return RD_OK;
+}
+
 // the workspace of rd_gz_compress_selected; its head, the selection scan's part, is all of rd_select_pack's. Sizes that the entry
 // points refuse (n < 0, text_bytes < 0) give an empty layout: total = 0, what the *_workspace_bytes functions answer to them
 struct GzWs {
     int nb;                 // scan blocks
-    int64_t cap_members;    // members the chunk can have at most (every record selected)
-    int grid;               // workgroups of the deflate kernel
-    int64_t *out_off, *bsum, *moff;
-    uint8_t *plain, *slots;
-    uint32_t *toks, *msize;
+    int64_t *out_off, *bsum;
+    GzMembers m;            // at most (text_bytes + 65,279) / 65,280 members: every record selected
     size_t sel_total, total;    // sel_total: the bytes of out_off + bsum, the selection scan's part
 };
 GzWs gz_ws(void *workspace, int64_t n, int64_t text_bytes) {
@@ -619,45 +663,30 @@ GzWs gz_ws(void *workspace, int64_t n, int64_t text_bytes) {
     if (n < 0 || text_bytes < 0) return p;
     Carver c(workspace);
     p.nb = scan_blocks(n);
-    p.cap_members = (text_bytes + GZ_MEMBER - 1) / GZ_MEMBER;
-    if (p.cap_members < 1) p.cap_members = 1;
-    p.grid = (int)(p.cap_members < GZ_MAX_GRID ? p.cap_members : GZ_MAX_GRID);
     p.out_off = c.take<int64_t>((size_t)(n + 1));
     p.bsum = c.take<int64_t>((size_t)p.nb);
     p.sel_total = c.off;
-    p.plain = c.take<uint8_t>((size_t)p.cap_members * GZ_MEMBER + 256);
-    p.toks = c.take<uint32_t>((size_t)p.grid * GZ_MEMBER);
-    p.slots = c.take<uint8_t>((size_t)p.cap_members * GZ_SLOT);
-    p.msize = c.take<uint32_t>((size_t)p.cap_members);
-    p.moff = c.take<int64_t>((size_t)p.cap_members);
+    const int64_t cap_members = (text_bytes + GZ_MEMBER - 1) / GZ_MEMBER;
+    p.m = gz_members(c, cap_members < 1 ? 1 : cap_members);
     p.total = c.off;
     return p;
 }
 
-// What rd_gz_compress_selected and rd_select_pack (`fn`) share: the argument checks, the n == 0 path, and the selection scan that
-// packs the selected records into `dst` (more selected bytes than `limit`: info[3] = 1, nothing packed). `need` = the bytes of the
-// caller's workspace, `out` must be out_align-byte aligned. The caller goes on only when n > 0.
+// What rd_gz_compress_selected and rd_select_pack (`fn`) share: pack_check, and the selection scan that packs the selected records
+// into `dst` (more selected bytes than `limit`: info[3] = 1, nothing packed). The caller goes on only when n > 0.
 int sel_scan_pack(const char *fn, const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int8_t *labels, int64_t n, int32_t label,
                   const uint8_t *out, unsigned out_align, int64_t *info, const void *workspace, size_t workspace_bytes, size_t need, const GzWs &s,
                   uint8_t *dst, int64_t limit, hipStream_t st) {
-    if (n < 0 || n > 0x7fffffffLL || text_bytes < 0) RD_FAIL(RD_E_INVALID, "%s: bad n or text_bytes", fn);
-    if (!info) RD_FAIL(RD_E_INVALID, "%s: null info", fn);
-    if (label < -128 || label > 127) RD_FAIL(RD_E_INVALID, "%s: label %d is not an int8 value", fn, label);
-    if (n == 0) {
-        RD_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int64_t), st));
-        return RD_OK;
-    }
-    if ((!text && text_bytes > 0) || !rec_start || !labels || !out || !workspace) RD_FAIL(RD_E_INVALID, "%s: null pointer", fn);
-    if (((uintptr_t)workspace & 255) || ((uintptr_t)out & (out_align - 1)))
-        RD_FAIL(RD_E_INVALID, "%s: workspace must be 256-byte aligned, out %u-byte aligned", fn, out_align);
-    if (workspace_bytes < need) RD_FAIL(RD_E_WORKSPACE, "%s: workspace too small: %zu < %zu", fn, workspace_bytes, need);
+    const int rc = pack_check(fn, false, text, text_bytes, rec_start, labels, n, label, out, out_align, nullptr, info, workspace, workspace_bytes, need, st);
+    if (rc || n == 0) return rc;
     const GzSelLen len = {rec_start, labels, (int)label};
     hipLaunchKernelGGL((rd_scan_sum_kernel<8, GzSelLen>), dim3(s.nb), dim3(256), 0, st, len, n, s.bsum);
     // info[3] != 0: the record table does not describe the text (rd_gz_compress_selected's limit is the text's bytes: more selected
     // bytes than that are overlapping or stray records) - the workspace is sized by the text, so nothing is packed or compressed
     scan_base(s.bsum, s.nb, info, limit, st, GZ_MEMBER);
     hipLaunchKernelGGL((rd_scan_off_kernel<8, 1, GzSelLen, ScanNoVerdict>), dim3(s.nb), dim3(256), 0, st, len, n, ScanOut<1>{{s.out_off}, {s.bsum}}, ScanNoVerdict{});
-    hipLaunchKernelGGL(rd_gz_pack_kernel, dim3((unsigned)((n + GZ_PACK_RECS - 1) / GZ_PACK_RECS)), dim3(256), 0, st, text, rec_start, s.out_off, n, dst, info);
+    hipLaunchKernelGGL(rd_pack_kernel<GzSelPlaces>, dim3((unsigned)((n + GZ_PACK_RECS - 1) / GZ_PACK_RECS)), dim3(256), 0, st, text,
+                       GzSelPlaces{rec_start, s.out_off, n}, dst, info);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }
@@ -686,11 +715,9 @@ int rd_gz_compress_selected(const uint8_t *text, int64_t text_bytes, const int64
     hipStream_t st = (hipStream_t)stream;
     const GzWs p = gz_ws(workspace, n, text_bytes);
     const int rc = sel_scan_pack("rd_gz_compress_selected", text, text_bytes, rec_start, labels, n, label, out, 256, info, workspace, workspace_bytes,
-                                 p.total, p, p.plain, text_bytes, st);
+                                 p.total, p, p.m.plain, text_bytes, st);
     if (rc || n == 0) return rc;
-    hipLaunchKernelGGL(rd_gz_deflate_kernel<GzStreamLen>, dim3(p.grid), dim3(GZ_THREADS), 0, st, p.plain, GzStreamLen{info}, p.toks, p.slots, p.msize);
-    hipLaunchKernelGGL(rd_gz_moff_kernel, dim3(1), dim3(256), 0, st, p.msize, p.moff, info);
-    hipLaunchKernelGGL(rd_gz_compact_kernel, dim3(p.grid), dim3(256), 0, st, p.slots, p.msize, p.moff, info, out, (int64_t)out_cap);
+    gz_deflate_members(p.m, GzStreamLen{info}, info, out, out_cap, st);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }
@@ -715,13 +742,11 @@ struct GpWs {
     GpParts parts;
     int64_t entries;        // K * parts: the (key, part) counters
     int nb_pos, nb_len;     // scan blocks over the counters, over the records
-    int64_t cap_members;    // members of the padded stream at most
-    int grid;               // workgroups of the deflate kernel
     int64_t *head;          // [0..3] the counters' scan, [4..7] the lengths' scan, [8] the fault flag of the count pass
-    uint32_t *cnt, *gcur, *toks, *msize, *mlen;
-    int64_t *pos, *bsum_pos, *L, *bsum_len, *shift, *moff;
+    uint32_t *cnt, *gcur, *mlen;
+    int64_t *pos, *bsum_pos, *L, *bsum_len, *shift;
     int32_t *perm;
-    uint8_t *plain, *slots;
+    GzMembers m;            // gz: the padded stream's members, and mlen: their lengths
     size_t total;
 };
 GpWs gp_ws(void *workspace, int64_t n, int64_t text_bytes, int64_t K, bool gz) {
@@ -744,36 +769,20 @@ GpWs gp_ws(void *workspace, int64_t n, int64_t text_bytes, int64_t K, bool gz) {
     p.bsum_len = c.take<int64_t>((size_t)p.nb_len);
     p.shift = c.take<int64_t>((size_t)K);
     if (gz) {   // the padded stream: every key's run starts a member, so it holds text_bytes + 65,280 * min(K, n) bytes at most
-        p.cap_members = text_bytes / GZ_MEMBER + (K < n ? K : n) + 1;
-        p.grid = (int)(p.cap_members < GZ_MAX_GRID ? p.cap_members : GZ_MAX_GRID);
-        p.plain = c.take<uint8_t>((size_t)p.cap_members * GZ_MEMBER + 256);
-        p.toks = c.take<uint32_t>((size_t)p.grid * GZ_MEMBER);
-        p.slots = c.take<uint8_t>((size_t)p.cap_members * GZ_SLOT);
-        p.msize = c.take<uint32_t>((size_t)p.cap_members);
-        p.moff = c.take<int64_t>((size_t)p.cap_members);
-        p.mlen = c.take<uint32_t>((size_t)p.cap_members);
+        p.m = gz_members(c, text_bytes / GZ_MEMBER + (K < n ? K : n) + 1);
+        p.mlen = c.take<uint32_t>((size_t)p.m.cap_members);
     }
     p.total = c.off;
     return p;
 }
 
-// What rd_group_pack and rd_gz_compress_grouped (`fn`) share: the argument checks, the n == 0 path, the partition, the length scan,
-// the keys' table and the pack into `dst`. The caller goes on only when n > 0.
+// What rd_group_pack and rd_gz_compress_grouped (`fn`) share: pack_check, the partition, the length scan, the keys' table and the
+// pack into `dst`. The caller goes on only when n > 0.
 int group_scan_pack(bool gz, const char *fn, const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int32_t *keys, int64_t n, int32_t K,
                     const uint8_t *out, size_t out_cap, unsigned out_align, int64_t *key_tab, int64_t *info, void *workspace, size_t workspace_bytes,
                     const GpWs &p, uint8_t *dst, hipStream_t st) {
-    if (n < 0 || n > 0x7fffffffLL || text_bytes < 0) RD_FAIL(RD_E_INVALID, "%s: bad n or text_bytes", fn);
-    if (K < 1 || K > RD_GROUP_KEYS_MAX) RD_FAIL(RD_E_INVALID, "%s: K = %d is outside 1..%d", fn, K, RD_GROUP_KEYS_MAX);
-    if (!info || !key_tab) RD_FAIL(RD_E_INVALID, "%s: null info or key_tab", fn);
-    if (n == 0) {
-        RD_HIP(hipMemsetAsync(info, 0, 4 * sizeof(int64_t), st));
-        RD_HIP(hipMemsetAsync(key_tab, 0, (size_t)K * 4 * sizeof(int64_t), st));
-        return RD_OK;
-    }
-    if ((!text && text_bytes > 0) || !rec_start || !keys || !out || !workspace) RD_FAIL(RD_E_INVALID, "%s: null pointer", fn);
-    if (((uintptr_t)workspace & 255) || ((uintptr_t)out & (out_align - 1)))
-        RD_FAIL(RD_E_INVALID, "%s: workspace must be 256-byte aligned, out %u-byte aligned", fn, out_align);
-    if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "%s: workspace too small: %zu < %zu", fn, workspace_bytes, p.total);
+    const int rc = pack_check(fn, true, text, text_bytes, rec_start, keys, n, K, out, out_align, key_tab, info, workspace, workspace_bytes, p.total, st);
+    if (rc || n == 0) return rc;
     const bool lds = K <= GP_LDS_KEYS;
     uint32_t *flag = reinterpret_cast<uint32_t *>(p.head + 8);
     int64_t *pinfo = p.head, *linfo = p.head + 4;
@@ -802,8 +811,8 @@ int group_scan_pack(bool gz, const char *fn, const uint8_t *text, int64_t text_b
     } else {
         hipLaunchKernelGGL(rd_gp_keytab_kernel<false>, dim3(1), dim3(256), 0, st, p.pos, p.L, (int)K, p.parts.nb, flag, linfo, (int64_t)out_cap, p.shift, key_tab, info);
     }
-    hipLaunchKernelGGL(rd_gp_pack_kernel, dim3((unsigned)((n + GZ_PACK_RECS - 1) / GZ_PACK_RECS)), dim3(256), 0, st, text, rec_start, keys, p.perm, p.L, p.shift,
-                       p.pos + p.entries, dst, info);
+    hipLaunchKernelGGL(rd_pack_kernel<GpPermPlaces>, dim3((unsigned)((n + GZ_PACK_RECS - 1) / GZ_PACK_RECS)), dim3(256), 0, st, text,
+                       GpPermPlaces{rec_start, keys, p.perm, p.L, p.shift, p.pos + p.entries}, dst, info);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }
@@ -851,12 +860,10 @@ int rd_gz_compress_grouped(const uint8_t *text, int64_t text_bytes, const int64_
     hipStream_t st = (hipStream_t)stream;
     const GpWs p = gp_ws(workspace, n, text_bytes, K, true);
     const int rc = group_scan_pack(true, "rd_gz_compress_grouped", text, text_bytes, rec_start, keys, n, K, out, out_cap, 256, key_tab, info, workspace,
-                                         workspace_bytes, p, p.plain, st);
+                                         workspace_bytes, p, p.m.plain, st);
     if (rc || n == 0) return rc;
-    hipLaunchKernelGGL(rd_gz_deflate_kernel<GzTableLen>, dim3(p.grid), dim3(GZ_THREADS), 0, st, p.plain, GzTableLen{info, p.mlen}, p.toks, p.slots, p.msize);
-    hipLaunchKernelGGL(rd_gz_moff_kernel, dim3(1), dim3(256), 0, st, p.msize, p.moff, info);
-    hipLaunchKernelGGL(rd_gz_compact_kernel, dim3(p.grid), dim3(256), 0, st, p.slots, p.msize, p.moff, info, out, (int64_t)out_cap);
-    hipLaunchKernelGGL(rd_gp_keytab_gz_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, p.moff, (int)K, (int64_t)out_cap, key_tab, info);
+    gz_deflate_members(p.m, GzTableLen{info, p.mlen}, info, out, out_cap, st);
+    hipLaunchKernelGGL(rd_gp_keytab_gz_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, p.m.moff, (int)K, (int64_t)out_cap, key_tab, info);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }

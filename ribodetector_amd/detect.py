@@ -119,7 +119,8 @@ def _pinned(t):
 
 def record_view(source, n, labels, e, interleaved=False, outs=2, pair_table=None, expand=None):
     """(text, record table, selecting labels) of mate e's records, as DeviceGzip.compress_selected and DeviceSelect.pack_selected take
-    them - the one place that knows the three layouts. source: (text, record table) of this rank's n units; labels: the unit labels.
+    them - the one place that knows the three layouts. source: (text, record table) of this rank's n units; labels: the unit labels
+    (None: the caller selects by key - gz.DeviceGroupSelect - and gets no labels, none are expanded).
       two input files: record k of mate e's source is unit k;
       interleaved, one output: pair k is records 2 k and 2 k + 1, so the table is every second entry - pair_table where the source
         has that table already (rd_pair_split wrote it), else a copy of the entries;
@@ -130,59 +131,59 @@ def record_view(source, n, labels, e, interleaved=False, outs=2, pair_table=None
         return text, table, labels
     if outs == 1:
         return text, table[0:2 * n + 1:2].contiguous() if pair_table is None else pair_table, labels
-    return text, table, expand(labels, e)
+    return text, table, None if labels is None else expand(labels, e)
 
 
 class Piece(NamedTuple):
-    """Bytes that one output file gets from the GPU for one chunk (one piece per rank under the label gather). info: pinned copy of
-    the int64[4] that the kernel which made buf wrote ([0] = gzip bytes, [1] = text bytes: gz.DeviceGzip / DeviceSelect /
-    DeviceReport), or None when all of buf counts (bytes gathered from the ranks); text: text or gzip members; fault: pinned info
-    whose [3] != 0 says that the chunk's record table did not describe its text to `what`; fallback: what the file gets when the bytes
-    exceed buf (text that did not compress into the reserved half): None = the host writes the chunk's selected records."""
+    """Bytes that the GPU left for output files for one chunk (one piece per rank under the label gather). info: pinned copy of the
+    int64[4] that the kernel which made buf wrote ([0] = gzip bytes, [1] = text bytes: gz.DeviceGzip / DeviceSelect / DeviceReport /
+    DeviceGroupSelect), or None when all of buf counts (bytes gathered from the ranks); text: text or gzip members.
+      A label piece is one run of bytes for ONE file, the key it stands under in Ticket.pieces. fault: pinned info whose [3] != 0 says
+    that the chunk's record table did not describe its text to `what`; fallback: what the file gets when the bytes exceed buf (text
+    that did not compress into the reserved half): None = the host writes the chunk's selected records.
+      A grouped piece (--split_groups; key_tab is not None) holds the runs of ONE mate's family files from one grouped call: key_tab
+    (pinned int64[K, 4]) says where - key s * (G + 1) + g is member g of the family of class labels[s] -, kinfo is the pinned int64[4]
+    of rd_group_keys. It has no fallback: check_split_groups refuses the runs that would need one."""
     buf: torch.Tensor
     info: Optional[torch.Tensor]
     text: bool
     fault: Optional[torch.Tensor] = None
     what: str = "gzip"
     fallback: Optional["Piece"] = None
+    key_tab: Optional[torch.Tensor] = None
+    kinfo: Optional[torch.Tensor] = None
+    labels: tuple = ()
 
     def size(self):
-        """the bytes made, whether or not they fit buf; raises when the kernel found the record table wrong"""
-        if self.fault is not None and int(self.fault[3]):
+        """the bytes made, whether or not they fit buf; raises when the kernel found the chunk's tables wrong"""
+        if self.key_tab is not None:
+            if int(self.kinfo[0]):
+                raise RuntimeError("device group keys: a label or a read-group row of the chunk is outside its range (flags %d)" % int(self.kinfo[0]))
+            if int(self.info[3]):
+                raise RuntimeError("device group %s: the chunk's keys or record table do not describe its text, or the output did not fit (fault %d)"
+                                   % ("pack" if self.text else "gzip", int(self.info[3])))
+        elif self.fault is not None and int(self.fault[3]):
             raise RuntimeError("device %s: the chunk's record table does not describe its text" % self.what)
         return int(self.buf.numel()) if self.info is None else int(self.info[1 if self.text else 0])
 
     def take(self):
-        """(piece, bytes) that the file gets: this piece, or its fallback when the bytes do not fit buf; (None, 0) = the host writes
+        """(piece, bytes) that the files get: this piece, or its fallback when the bytes do not fit buf; (None, 0) = the host writes
         the chunk's selected records"""
         nb = self.size()
-        if nb <= self.buf.numel():
+        if nb <= self.buf.numel() or self.key_tab is not None:
             return self, nb
         return (None, 0) if self.fallback is None else self.fallback.take()
 
-
-class GroupPiece(NamedTuple):
-    """Piece's sibling under --split_groups: the bytes that the family files of ONE mate get from the GPU for one chunk, from one grouped
-    call (gz.DeviceGroupSelect). buf holds every key's run, key_tab (pinned int64[K, 4]) says where: key s * (G + 1) + g is member g of
-    the family of class labels[s]. info / kinfo: pinned copies of the int64[4] of the grouped call and of rd_group_keys."""
-    buf: torch.Tensor
-    info: torch.Tensor
-    key_tab: torch.Tensor
-    kinfo: torch.Tensor
-    gz: bool
-    labels: tuple
-
-    def size(self):
-        """the bytes made; raises when the keys or the partition found the chunk's tables wrong"""
-        if int(self.kinfo[0]):
-            raise RuntimeError("device group keys: a label or a read-group row of the chunk is outside its range (flags %d)" % int(self.kinfo[0]))
-        if int(self.info[3]):
-            raise RuntimeError("device group %s: the chunk's keys or record table do not describe its text, or the output did not fit (fault %d)"
-                               % ("gzip" if self.gz else "pack", int(self.info[3])))
-        return int(self.info[0 if self.gz else 1])
+    def runs(self, key, nb):
+        """[(file key, offset in buf, bytes)] of the nb bytes that size() told, for a piece that stands under `key`"""
+        if self.key_tab is None:
+            return [(key, 0, nb)]
+        tab = self.key_tab.numpy()
+        G1 = len(tab) // len(self.labels)
+        return [((key[0], self.labels[k // G1], k % G1), int(tab[k, 0]), int(tab[k, 1])) for k in np.flatnonzero(tab[:, 1])]
 
 
-SPLIT = "groups"            # pieces[(mate, SPLIT)]: the GroupPieces of a mate's family files
+SPLIT = "groups"            # pieces[(mate, SPLIT)]: the grouped pieces of a mate's family files
 
 
 class MateMismatch(RuntimeError):
@@ -197,7 +198,8 @@ class _MateWriter:
 
     def __init__(self, pred, e, files, errors):
         self.pred, self.e, self.files, self.errors = pred, e, files, errors     # files: [((mate, label), handle)] of mate e in file order
-        self.q = queue.Queue(maxsize=2)      # items (chunk of this mate, labels, {(mate, label): [Piece]}); None ends
+        self.keys, self.handles = self._file_index(e, files)
+        self.q = queue.Queue(maxsize=2)      # items (chunk of this mate, labels, Ticket.pieces); None ends
         self.stream, self.stages = _gzmod.acquire_stream(pred.device), [[], []]
         self.thread = pred._spawn(self._run)
 
@@ -227,33 +229,34 @@ class _MateWriter:
         finally:
             self.pred.thread_cpu_s["writer:%d" % self.e] = round(time.thread_time(), 4)
 
+    @staticmethod
+    def _file_index(e, files):
+        """(the keys under which an item's pieces for mate e's files stand, in job order; {file key: handle}). The family members
+        (keys of three) share the grouped pieces under (e, SPLIT); every other file has its own key."""
+        own = [key for key, _ in files if len(key) != 3]
+        return ([(e, SPLIT)] if len(own) < len(files) else []) + own, dict(files)
+
     def _issue(self, item, k):
-        """queue the D2H of everything the item's files take from the GPU into stage set k; returns the writes in file order, as
-        (event to wait for or None, write)"""
+        """queue the D2H of everything the item's files take from the GPU into stage set k; returns the writes - those of any one file
+        in input order -, as (event to wait for or None, write)"""
         chunk, labels, pieces = item
         jobs, slot = [], 0
-        for gp in pieces.get((self.e, SPLIT)) or ():      # --split_groups: one fetch per grouped call, an append per key with bytes
-            nb, tab = gp.size(), gp.key_tab.numpy()
-            self.pred._split_counted(self.e, gp.labels, tab[:, 2])
-            if nb:
-                (buf, done), slot = self._fetch(k, slot, gp.buf, nb), slot + 1
-                fams = dict(self.files)
-                handles = [fams[(self.e, lab, g)] for lab in gp.labels for g in range(len(tab) // len(gp.labels))]
-                for kk in np.flatnonzero(tab[:, 1]):
-                    fh = handles[kk]
-                    jobs.append((done, functools.partial(fh.write_members if gp.gz else fh.write_text, buf.data_ptr() + int(tab[kk, 0]), int(tab[kk, 1]))))
-        for key, fh in self.files:
-            if len(key) == 3:           # (a family member: served above)
-                continue
-            for piece in pieces.get(key) or (None,):
+        for key in self.keys:
+            # (a file without a piece: the host writes the records of its label; family members only ever get what the grouped pieces hold)
+            for piece in pieces.get(key) or (() if key[1] == SPLIT else (None,)):
                 p, nb = (None, 0) if piece is None else piece.take()
                 if p is None:           # nothing from the GPU, or too much for its buffer: the host writes the records of this label
-                    jobs.append((None, functools.partial(fh.write_selected, chunk, labels, key[1])))
-                elif nb:
+                    jobs.append((None, functools.partial(self.handles[key].write_selected, chunk, labels, key[1])))
+                    continue
+                if p.key_tab is not None:
+                    self.pred._split_counted(self.e, p.labels, p.key_tab.numpy()[:, 2])
+                if nb:
                     buf, done = p.buf, None
                     if buf.is_cuda:
                         (buf, done), slot = self._fetch(k, slot, buf, nb), slot + 1
-                    jobs.append((done, functools.partial(fh.write_text if p.text else fh.write_members, buf.data_ptr(), nb)))
+                    for fkey, off, n in p.runs(key, nb):
+                        fh = self.handles[fkey]
+                        jobs.append((done, functools.partial(fh.write_text if p.text else fh.write_members, buf.data_ptr() + off, n)))
         return jobs
 
     def _fetch(self, k, slot, src, nb):
@@ -663,26 +666,34 @@ class Predictor:
         raw, rs = chunk.raw
         return self._split_dict.rows(raw, *_grpmod.tag_find(raw, rs, int(rs.numel()) - 1, _grpmod.TAG))
 
+    def _output_view(self, chunks, dev_in, labels, e, lo, hi, ring, pairs, tagged):
+        """(text, record table, selecting labels) of mate e's records for the output files - the one place that chooses their source:
+        the records as they stand in the input under --bam_output (DeviceChunk.raw), else the text with the tags behind the read
+        names under --bam_tags, else the FASTQ view; record_view knows the layouts. labels None (--split_groups selects by key):
+        no selecting labels, none expanded."""
+        f, pair_table = e if pairs is None else 0, None
+        if self.bam_output:
+            source = chunks[f].raw
+        elif tagged is not None:
+            source = tagged[f]
+        else:
+            source, pair_table = self._fastq_view(chunks, dev_in, e, lo, hi, pairs)
+        return record_view(source, hi - lo, labels, e, pairs is not None, len(self.output), pair_table,
+                           None if pairs is None else functools.partial(self._pairs.expand, slot=ring))
+
     def _select_split(self, chunks, dev_in, labels, lo, hi, ring, pairs, tagged, rows):
-        """--split_groups: {(mate, SPLIT): [GroupPiece]} - ONE grouped call per mate (two when a mate's files are part .gz, part
-        plain), over the same three sources as _select_chunk, instead of a call per (mate, label)"""
-        pieces, n, G, lab8 = {}, hi - lo, len(self._split_ids), labels.view(torch.int8)
+        """--split_groups: {(mate, SPLIT): [grouped Piece]} - ONE grouped call per mate (two when a mate's files are part .gz, part
+        plain) instead of a call per (mate, label)"""
+        pieces, G, lab8 = {}, len(self._split_ids), labels.view(torch.int8)
         for e, plan in self._split_plan.items():
-            f, pair_table = e if pairs is None else 0, None
-            if self.bam_output:
-                source = chunks[f].raw
-            elif tagged is not None:
-                source = tagged[f]
-            else:
-                source, pair_table = self._fastq_view(chunks, dev_in, e, lo, hi, pairs)
-            text, table, _ = record_view(source, n, lab8, e, pairs is not None, len(self.output), pair_table, lambda lab, m: None)
+            text, table, _ = self._output_view(chunks, dev_in, None, e, lo, hi, ring, pairs, tagged)
             stride = 1 if pairs is None else 2                      # unit u's row is mate 1's: record u, or record 2 u of an interleaved chunk
             mate = e if pairs is not None and len(self.output) == 2 else -1
             for gz, slots, labs in plan:
                 keys, kinfo = self._split.keys(rows, lab8, slots, G, 0, stride, mate, slot=(e, gz, ring))
                 call = self._split.compress_grouped if gz else self._split.pack_grouped
                 out, tab, info = call(text, table, keys, len(labs) * (G + 1), slot=(e, gz, ring))
-                pieces.setdefault((e, SPLIT), []).append(GroupPiece(out, _pinned(info), _pinned(tab), _pinned(kinfo), gz, labs))
+                pieces.setdefault((e, SPLIT), []).append(Piece(out, _pinned(info), not gz, key_tab=_pinned(tab), kinfo=_pinned(kinfo), labels=labs))
         return pieces
 
     def _split_counted(self, e, labs, records):
@@ -713,16 +724,8 @@ class Predictor:
         pieces = {}
         views = {}                                  # mate -> (text, record table, labels) that select the records of its files
         for e, lab in files:
-            if e not in views:                      # the source is chosen once per chunk and mate; record_view knows the layouts
-                f, pair_table = e if pairs is None else 0, None
-                if self.bam_output:                 # the records as they stand in the input (DeviceChunk.raw), selected like the text's
-                    source = chunks[f].raw
-                elif tagged is not None:            # --bam_tags: the text with the tags behind the read names, selected like the text
-                    source = tagged[f]
-                else:
-                    source, pair_table = self._fastq_view(chunks, dev_in, e, lo, hi, pairs)
-                views[e] = record_view(source, hi - lo, labels.view(torch.int8), e, pairs is not None, len(self.output), pair_table,
-                                       None if pairs is None else functools.partial(self._pairs.expand, slot=ring))
+            if e not in views:                      # once per chunk and mate
+                views[e] = self._output_view(chunks, dev_in, labels.view(torch.int8), e, lo, hi, ring, pairs, tagged)
             text, rs, sel = views[e]
             gz = (e, lab) in self._gz_files
             if gz:

@@ -69,61 +69,60 @@ def eof_block():
     return bytes(buf)
 
 
-class DeviceGzip:
+class _DeviceOut:
+    """What DeviceGzip, DeviceSelect and DeviceGroupSelect share: one grow-only workspace, a ring of grow-only output buffers (one per
+    `slot`, owned by this object until the next call with the same slot) and the call itself - the four C entry points take
+    (text, bytes, rec_start, labels or keys, n, label or K, out, capacity, [key_tab,] info, workspace, bytes, stream)."""
+    WS_MIN = 1 << 20        # the workspace's first size, at least
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._ws = None
+        self._out = {}
+
+    def _run(self, fn, text, rec_start, sel, label_or_k, need, slot, cap, alloc=None, keyed=False):
+        """fn over the n = sel.numel() records: `need` bytes of workspace, an output buffer of at least `cap` bytes (made with `alloc`
+        bytes: cap when None) in ring slot `slot`. Returns (out, info), or (out, key_tab, info) with the int64[K, 4] table when keyed."""
+        n, tb = int(sel.numel()), int(text.numel())
+        ws = _grown(self, "_ws", need, lambda: torch.empty(max(need, self.WS_MIN), dtype=torch.uint8, device=self.device))
+        out = _grown(self._out, slot, cap, lambda: torch.empty(cap if alloc is None else alloc, dtype=torch.uint8, device=self.device))
+        tab = [torch.empty((int(label_or_k), 4), dtype=torch.int64, device=self.device)] if keyed else []
+        info = torch.empty(4, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(getattr(N.lib(), fn)(N.ptr(text), tb, N.ptr(rec_start), N.ptr(sel), n, int(label_or_k), N.ptr(out), out.numel(), *[N.ptr(t) for t in tab],
+                                         N.ptr(info), N.ptr(ws), ws.numel(), N.stream_ptr(self.device)), fn)
+        return (out, *tab, info)
+
+
+class DeviceGzip(_DeviceOut):
     """compress_selected(text, rec_start, labels, label): the records i of the chunk with labels[i] == label, in input order, as
     gzip members. text uint8[*], rec_start int64[n+1], labels int8[n] (or uint8) - all on the device. Returns (out, info): out is a
     device uint8 buffer owned by this object until the next call with the same `slot`, info a device int64[4] tensor = (compressed
     bytes, uncompressed bytes, members, 0). Asynchronous on the current stream."""
 
-    def __init__(self, device):
-        self.device = torch.device(device)
-        self._ws = None
-        self._out = {}
-
     def compress_selected(self, text, rec_start, labels, label, slot=0, out_frac=1.0):
         lib = N.lib()
-        n = int(labels.numel())
-        tb = int(text.numel())
+        n, tb = int(labels.numel()), int(text.numel())
         _check_tables("compress_selected", text, rec_start, "n", n, labels)
-        need = int(lib.rd_gz_workspace_bytes(n, tb))
-        ws = _grown(self, "_ws", need, lambda: torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=self.device))
         # out_frac < 1: a smaller output buffer than the worst case (every member stored). FASTQ shrinks 4-6x, so half the bound is
         # plenty; if a chunk does not fit (info[0] > out.numel()) the stream in `out` is incomplete and the caller falls back
         cap = max(int(int(lib.rd_gz_out_bound(tb)) * float(out_frac)) + (1 << 20), 256) if out_frac < 1.0 else max(int(lib.rd_gz_out_bound(tb)), 256)
-        out = _grown(self._out, slot, cap, lambda: torch.empty(cap, dtype=torch.uint8, device=self.device))
-        info = torch.empty(4, dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            N.check(lib.rd_gz_compress_selected(N.ptr(text), tb, N.ptr(rec_start), N.ptr(labels), n, int(label), N.ptr(out), out.numel(),
-                                                N.ptr(info), N.ptr(ws), ws.numel(), N.stream_ptr(self.device)),
-                    "rd_gz_compress_selected")
-        return out, info
+        return self._run("rd_gz_compress_selected", text, rec_start, labels, label, int(lib.rd_gz_workspace_bytes(n, tb)), slot, cap)
 
 
-class DeviceSelect:
+class DeviceSelect(_DeviceOut):
     """pack_selected(text, rec_start, labels, label): the records with labels[i] == label as ONE contiguous text on the device, in input
     order (C ABI rd_select_pack) - the plain-output counterpart of DeviceGzip for chunks whose text lives in HBM
     (data_loader/device_reader.py). Returns (out, info): info int64[4] on the device, info[1] = bytes, info[3] != 0 = bad record table."""
-
-    def __init__(self, device):
-        self.device = torch.device(device)
-        self._ws = None
-        self._out = {}
+    WS_MIN = 1 << 16
 
     def pack_selected(self, text, rec_start, labels, label, slot=0):
-        lib = N.lib()
         n, tb = int(labels.numel()), int(text.numel())
         _check_tables("pack_selected", text, rec_start, "n", n, labels)
-        need = int(lib.rd_select_workspace_bytes(n))
-        ws = _grown(self, "_ws", need, lambda: torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=self.device))
-        out = _grown(self._out, slot, tb + 16, lambda: torch.empty(tb + 256, dtype=torch.uint8, device=self.device))
-        info = torch.empty(4, dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            N.check(lib.rd_select_pack(N.ptr(text), tb, N.ptr(rec_start), N.ptr(labels), n, int(label), N.ptr(out), out.numel(), N.ptr(info),
-                                       N.ptr(ws), ws.numel(), N.stream_ptr(self.device)), "rd_select_pack")
-        return out, info
+        return self._run("rd_select_pack", text, rec_start, labels, label, int(N.lib().rd_select_workspace_bytes(n)), slot, tb + 16, tb + 256)
 
 
-class DeviceGroupSelect:
+class DeviceGroupSelect(_DeviceOut):
     """The records of a chunk partitioned by key (C ABI rd_group_keys / rd_group_pack / rd_gz_compress_grouped, csrc/rd_group_pack.hpp):
     ONE call per mate and chunk writes the records of every key 0 .. K - 1, in input order, as a run of text (pack_grouped) or of BGZF
     members (compress_grouped) per key, the runs in key order. keys(rows, labels, class_slot, G, ...) makes the int32 keys of a run
@@ -132,9 +131,7 @@ class DeviceGroupSelect:
     (include/ribodetector_amd.h has the columns). Buffers grow on demand. Asynchronous on the current stream."""
 
     def __init__(self, device):
-        self.device = torch.device(device)
-        self._ws = None
-        self._out = {}
+        super().__init__(device)
         self._keys = {}
 
     def keys(self, rows, labels, class_slot, G, first=0, stride=1, mate=-1, slot=0):
@@ -153,22 +150,14 @@ class DeviceGroupSelect:
         return out[:m], info
 
     def _call(self, fn, gz, text, rec_start, keys, K, slot, cap):
-        lib = N.lib()
         n, tb = int(keys.numel()), int(text.numel())
         _check_tables(fn, text, rec_start, "n", n)
         if keys.dtype != torch.int32 or not keys.is_contiguous() or text.dtype != torch.uint8:
             raise TypeError("%s: keys must be a contiguous int32 tensor and text uint8" % fn)
-        need = int(lib.rd_group_workspace_bytes(n, tb, int(K), gz))
+        need = int(N.lib().rd_group_workspace_bytes(n, tb, int(K), gz))
         if need == 0:
             raise ValueError("%s: n = %d, K = %d: outside what the device call takes (K <= %d)" % (fn, n, K, N.GROUP_KEYS_MAX))
-        ws = _grown(self, "_ws", need, lambda: torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=self.device))
-        out = _grown(self._out, slot, cap, lambda: torch.empty(cap, dtype=torch.uint8, device=self.device))
-        key_tab = torch.empty((int(K), 4), dtype=torch.int64, device=self.device)
-        info = torch.empty(4, dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            N.check(getattr(lib, fn)(N.ptr(text), tb, N.ptr(rec_start), N.ptr(keys), n, int(K), N.ptr(out), out.numel(), N.ptr(key_tab), N.ptr(info),
-                                     N.ptr(ws), ws.numel(), N.stream_ptr(self.device)), fn)
-        return out, key_tab, info
+        return self._run(fn, text, rec_start, keys, K, need, slot, cap, keyed=True)
 
     def pack_grouped(self, text, rec_start, keys, K, slot=0):
         """every run starts on a multiple of 16 bytes: the text and 16 bytes per key always hold them"""

@@ -11,7 +11,9 @@ CHECK_ORDER = ("totals", "pairs", "summary", "groups", "regions")
 class Ticket:
     """One submitted chunk. n: its units (reads or pairs); bounds: the ranks' shard bounds (label gather) or None; labels: the unit
     labels on the device; host: their pinned copy (None under the label gather, whose `finish` returns the gathered labels); done: the
-    event behind everything the chunk enqueued; pieces: {(mate, label): [Piece]}; chunk: mate 1's chunk. checks: name (one of
+    event behind everything the chunk enqueued; pieces: {key: [detect.Piece]} - key (mate, label): the label pieces of that file (one, or
+    one per rank behind the label gather), detect.REPORT / detect.REGIONS: those of the two text files, (mate, detect.SPLIT): the
+    grouped pieces of the mate's family files under --split_groups (one per grouped call); chunk: mate 1's chunk. checks: name (one of
     CHECK_ORDER) -> callable that reads, once `done` has passed, the verdict a side product's kernel wrote into pinned memory, and
     raises on a fault. keep: what is only kept alive until the ticket goes."""
     n: int

@@ -241,3 +241,41 @@ def test_faults_are_reported_not_taken():
     assert rc == 0 and inf[3] == 0
     rc, inf, tb_ = call("rd_gz_compress_grouped", cap=1024)      # (the compressed size is not the same from call to call: far too small)
     assert rc == 0 and inf[0] > 1024 and inf[3] == 4
+
+
+@pytest.mark.parametrize("n,chosen", [(1024, list(range(300, 311)) + [1023]), (257, [256])])
+def test_workgroups_of_the_pack_with_nothing_to_write(n, chosen):
+    """whole blocks of 256 records of which none is selected (a workgroup of the selection pack whose output range is empty, workgroups
+    of the grouped pack behind the last place), a last block that holds one place; records of 0 .. 40 bytes, so that most pieces of
+    16 bytes span several records. Labels 1 (a few records), 5 (none) and 0 (all the others), through all four entry points."""
+    from ribodetector_amd.gz import DeviceGroupSelect, DeviceGzip, DeviceSelect
+    rng = np.random.default_rng(n)
+    recs = [bytes(rng.integers(33, 127, int(L), dtype=np.uint8)) for L in rng.integers(0, 41, n)]
+    assert min(map(len, recs)) == 0 and any(0 < len(r) < 16 for r in recs)
+    text, rs = _tables(recs)
+    labels = np.zeros(n, dtype=np.int8)
+    labels[chosen] = 1
+    t, r, lab = _dev(text), _dev(rs), _dev(labels)
+    sel, gz, gs = DeviceSelect(DEV), DeviceGzip(DEV), DeviceGroupSelect(DEV)
+    for label in (1, 5, 0):
+        picked = np.flatnonzero(labels == label)
+        want = b"".join(recs[i] for i in picked)
+        members = -(-len(want) // MEMBER)
+        out, info = sel.pack_selected(t, r, lab, label)
+        gout, ginfo = gz.compress_selected(t, r, lab, label)
+        keys = _dev(np.where(labels == label, 0, -1).astype(np.int32))
+        kout, ktab, kinfo = gs.pack_grouped(t, r, keys, 1, slot="text")
+        zout, ztab, zinfo = gs.compress_grouped(t, r, keys, 1, slot="gz")
+        torch.cuda.synchronize()
+        info = info.cpu().tolist()
+        assert (info[1], info[3]) == (len(want), 0) and out[:len(want)].cpu().numpy().tobytes() == want, (label, info)
+        ginfo = ginfo.cpu().tolist()
+        assert ginfo[1:] == [len(want), members, 0], (label, ginfo)
+        bodies = _members(gout[:ginfo[0]].cpu().numpy().tobytes())
+        assert len(bodies) == members and b"".join(bodies) == want, label
+        assert ktab.cpu().tolist() == [[0, len(want), len(picked), 0]] and kinfo.cpu().tolist() == [len(picked), len(want), 0, 0], label
+        assert kout[:len(want)].cpu().numpy().tobytes() == want, label
+        ztab, zinfo = ztab.cpu().tolist(), zinfo.cpu().tolist()
+        assert ztab == [[0, zinfo[0], len(picked), members]] and zinfo[1:] == [len(want), members, 0], (label, ztab, zinfo)
+        bodies = _members(zout[:zinfo[0]].cpu().numpy().tobytes())
+        assert len(bodies) == members and b"".join(bodies) == want, label
