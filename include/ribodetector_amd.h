@@ -566,6 +566,33 @@ RD_API int rd_bam_tag_splice_ex(const uint8_t *text, int64_t text_bytes, const i
                                 int64_t *out_start, int64_t *info, void *workspace, size_t workspace_bytes, uint32_t flags, void *stream);
 RD_API int rd_float_text(const uint32_t *bits, int64_t n, uint8_t *text, uint8_t *len, void *stream);
 
+/* The records of a FASTQ / FASTA chunk as unaligned BAM records (CLI extension `--ubam_output`; csrc/rd_bam_encode.hpp): the raw view
+ * of a chunk that did not come from a BAM file. The rule is ribodetector_amd/bam.py (from_fastq). text / rec_start / seq_off / seq_len:
+ * a chunk as rd_fastq_gather / rd_fasta_gather leave it. Record i = 0 .. n_rec - 1 of the call is entry rec_first + i * rec_stride of the
+ * tables (rec_start is read at that entry and the one behind it; rec_first >= 0, rec_stride >= 1). flags: RD_UBAM_FASTA (the records
+ * are '>' header '\n' SEQ '\n': qualities 0xFF) | the BAM flag word of the call's even records << RD_UBAM_EVEN_SHIFT | that of its odd
+ * records << RD_UBAM_ODD_SHIFT (12 bits each) - 4 and 4: single-end; 77 and 77: mate 1's file; 141 and 141: mate 2's; 77 and 141: an
+ * interleaved chunk. Any other bit: RD_E_INVALID. Record i becomes: block_size, refID -1, pos -1, l_read_name, mapq 0, bin 4680,
+ * n_cigar_op 0, flag, l_seq, next_refID -1, next_pos -1, tlen 0; the name and a NUL; the bases, 4 bits each; the qualities; no tags.
+ * name = the id of rd_report_format, without a trailing /1 (flag & 0x40) or /2 (flag & 0x80) when flag & 1; an empty one becomes '*'.
+ * A base: the code of its letter in "=ACMGRSVTWYHKDBN", either case, U as T, any other byte 15. A quality: min(max(b, 33), 126) - 33.
+ * raw [dev, 16-byte aligned] uint8[raw_cap] receives the records, raw_start [dev] int64[n_rec + 1] their table. raw_cap >=
+ * text_bytes + 32 n_rec (FASTQ) or text_bytes + (text_bytes + 1) / 2 + 40 n_rec (FASTA) is always enough. info [dev] int64[8]:
+ * [0] records, [1] raw bytes, [2] the first record (index in the call) whose name is longer than 254 bytes or -1 - it is laid out with
+ * the first 254 -, [3] fault - 1: more than raw_cap bytes, 2: a table entry that does not describe the text; nothing is written into raw
+ * then, raw_start is zeroed and [0] [1] are 0 -, [4] bytes whose BAM letter differs from the input byte, [5] quality bytes outside
+ * 33..126, [6] names replaced by '*', [7] the first record whose quality line is not as long as its sequence or -1 (laid out with
+ * l_seq 0). A caller delivers nothing of a call whose [2] or [7] is not -1. workspace [dev, 256-byte aligned] of
+ * rd_bam_encode_workspace_bytes(n_rec) (0: bad n_rec). Every table entry is checked against text_bytes before it is followed and every
+ * output offset against raw_cap. Asynchronous on `stream`; n_rec == 0: info = {0, 0, -1, 0, 0, 0, 0, -1}, raw_start[0] = 0. */
+#define RD_UBAM_FASTA 1u
+#define RD_UBAM_EVEN_SHIFT 4
+#define RD_UBAM_ODD_SHIFT 16
+RD_API size_t rd_bam_encode_workspace_bytes(int64_t n_rec);
+RD_API int rd_bam_encode(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int64_t *seq_off, const int32_t *seq_len,
+                         int64_t n_rec, int64_t rec_first, int32_t rec_stride, uint32_t flags, uint8_t *raw, size_t raw_cap,
+                         int64_t *raw_start, int64_t *info, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Reads longer than max_len classified over WINDOWS of max_len bases (CLI extension `--windows`; the reference classifies read[:max_len],
  * reference detect.py:666-726, and that stays the rule without the flag). A window is one more (seq_off, seq_len) entry over the same
  * text, so rd_classify takes the window table as it takes a read table and its kernels do not change.

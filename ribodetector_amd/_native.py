@@ -32,6 +32,7 @@ SYMBOLS = [
     "rd_summary_words", "rd_summary_accumulate",
     "rd_bam_tag_find", "rd_bam_group_rows", "rd_bam_group_accumulate",
     "rd_bam_tag_splice_workspace_bytes", "rd_bam_tag_splice", "rd_bam_tag_splice_ex", "rd_float_text",
+    "rd_bam_encode_workspace_bytes", "rd_bam_encode",
     "rd_window_workspace_bytes", "rd_window_plan", "rd_window_fill", "rd_window_fuse",
     "rd_region_workspace_bytes", "rd_region_format",
     "rd_group_keys", "rd_group_workspace_bytes", "rd_gz_grouped_out_bound", "rd_group_pack", "rd_gz_compress_grouped",
@@ -44,6 +45,7 @@ WINDOW_FUSE = {"mean": 0, "max": 1}     # RD_WINDOW_MEAN / RD_WINDOW_MAX_D
 GROUPS_MAX = 65536      # RD_GROUPS_MAX: the most read groups a dictionary of rd_bam_group_rows holds
 BAM_TAGS_MAX = 16       # RD_BAM_TAGS_MAX: the most tags rd_bam_tag_splice copies into the header lines
 BAM_TAGS_FLOATS = 1     # RD_BAM_TAGS_FLOATS: the flag of rd_bam_tag_splice_ex that formats f and B:f values
+UBAM_FASTA, UBAM_EVEN_SHIFT, UBAM_ODD_SHIFT = 1, 4, 16      # RD_UBAM_*: the flags word of rd_bam_encode
 FLOAT_TEXT_SLOT = 16    # bytes per value in the text rd_float_text writes
 SPLIT_GROUPS_MAX = 1024     # RD_SPLIT_GROUPS_MAX: the most declared read groups a run splits its outputs by (--split_groups)
 GROUP_KEYS_MAX = 16384      # RD_GROUP_KEYS_MAX: the most keys of rd_group_pack / rd_gz_compress_grouped
@@ -153,6 +155,9 @@ def lib():
     L.rd_bam_tag_splice.argtypes = [vp, i64, vp, vp, i64, vp, i64, C.c_char_p, i32, vp, sz, vp, vp, vp, sz, vp]
     L.rd_bam_tag_splice_ex.argtypes = [vp, i64, vp, vp, i64, vp, i64, C.c_char_p, i32, vp, sz, vp, vp, vp, sz, C.c_uint32, vp]
     L.rd_float_text.argtypes = [vp, i64, vp, vp, vp]
+    L.rd_bam_encode_workspace_bytes.argtypes = [i64]
+    L.rd_bam_encode_workspace_bytes.restype = sz
+    L.rd_bam_encode.argtypes = [vp, i64, vp, vp, vp, i64, i64, i32, C.c_uint32, vp, sz, vp, vp, vp, sz, vp]
     L.rd_window_workspace_bytes.argtypes = [i64]
     L.rd_window_workspace_bytes.restype = sz
     L.rd_window_plan.argtypes = [vp, i64, i32, i64, i32, vp, vp, vp, sz, vp]

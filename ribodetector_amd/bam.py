@@ -36,6 +36,11 @@ fastq_text_tagged is fastq_text with that comment in front of the first newline 
 out and counted, or, with floats=True (--bam_tag_floats), written as float_g says: printf's %g, stated in whole numbers (device side
 csrc/rd_float_text.hpp, C ABI rd_float_text / rd_bam_tag_splice_ex). A record whose listed tags cannot be walked, or hold a byte that
 would break a FASTQ header line, gets no comment.
+
+FASTQ / FASTA text as BAM records (detect.py --ubam_output; device side csrc/rd_bam_encode.hpp, C ABI rd_bam_encode): from_fastq says
+what a record of the text becomes - encode_record of its name (ubam_name: the report's read id, without the mate's /1 or /2 in a paired
+run, '*' when empty), its bases as the letters of CODES (either case, U as T, anything else N), its qualities clamped to 0..93 (FASTA:
+absent) and the flag 4 / 77 / 141; an output file is encode_header((), UBAM_HEADER_TEXT) and the selected records in BGZF members.
 """
 import os
 import struct
@@ -368,6 +373,121 @@ def write_bam(path, reads, *, refs=(), text=b"", level=6, member_bytes=0xff00, e
         if eof:
             fh.write(EOF_MEMBER)
     return data
+
+
+# ---- FASTQ / FASTA text as unaligned BAM records (detect.py --ubam_output; device side csrc/rd_bam_encode.hpp, C ABI rd_bam_encode) ------
+# A record of the text becomes encode_record({"name": ubam_name(...), "seq": SEQ', "qual": QUAL', "flag": UBAM_FLAGS[...]}): no
+# reference, no CIGAR, no tags. This is this project's own rule; it is not claimed to be what `samtools import` writes.
+UBAM_HEADER_TEXT = b"@HD\tVN:1.6\tSO:unsorted\tGO:query\n"      # no @PG line, no references: the header's bytes are deterministic
+UBAM_FLAGS = {(1, 0): 4, (2, 0): 77, (2, 1): 141}              # (mates of the run, mate) -> flag: unmapped; paired, both unmapped, first / last
+UBAM_NAME_MAX = 254                                            # l_read_name is one byte and counts the NUL
+UBAM_NAME_ERROR = "--ubam_output: the name of record %d is longer than 254 bytes"
+UBAM_LENGTH_ERROR = "--ubam_output: the quality line of record %d is not as long as its sequence"
+INTERLEAVED = -1                                               # from_fastq(mate=INTERLEAVED): the records alternate mate 1, mate 2
+_ID_END = b" \t\r\n\v\f"
+_UP = bytes(c - 32 if 97 <= c <= 122 else c for c in range(256))
+UBAM_LETTER = bytes(CODES[CODES.index(_UP[c])] if _UP[c] in CODES else (ord("T") if _UP[c] == ord("U") else ord("N")) for c in range(256))
+UBAM_CODE = bytes(CODES.index(UBAM_LETTER[c]) for c in range(256))        # input byte -> 4-bit code
+UBAM_QUAL = bytes(min(max(c, 33), 126) - 33 for c in range(256))          # input byte -> stored quality
+_SHL4 = bytes((c << 4) & 0xff for c in range(256))
+_SAME_LETTER = bytes(c for c in range(256) if UBAM_LETTER[c] == c)
+_IN_RANGE = bytes(range(33, 127))
+
+
+def ubam_name(header_line, n_mates=1, mate=0):
+    """the QNAME of a record from its header line ('@...' / '>...', with or without the line's end): the read_id of the per-read
+    report - the bytes behind the first one up to the first space, \\t, \\r, \\n, \\v or \\f -, in a paired run (n_mates 2) without a
+    trailing /1 on a mate-1 record (mate 0) or /2 on a mate-2 record (mate 1), decided from this record alone; an id that is empty
+    after this becomes '*'. Longer than 254 bytes: returned as it is - from_fastq and the run refuse it."""
+    return _ubam_id(header_line, n_mates, mate) or b"*"
+
+
+def _ubam_id(header_line, n_mates, mate):
+    """ubam_name in front of its last step: empty where the name is '*'"""
+    line = bytes(header_line)[1:]
+    end = min((p for p in (line.find(bytes([c])) for c in _ID_END) if p >= 0), default=len(line))
+    name = line[:end]
+    if n_mates == 2 and name.endswith(b"/1" if mate == 0 else b"/2"):
+        name = name[:-2]
+    return name
+
+
+def _text_records(text, fasta):
+    """(header line, sequence, quality or None) of every record of FASTQ text (four lines per record) or FASTA text ('>' lines, the
+    lines between them joined)"""
+    lines = bytes(text).split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    if fasta:
+        head, seq = None, []
+        for ln in lines:
+            if ln[:1] == b">":
+                if head is not None:
+                    yield head, b"".join(seq), None
+                head, seq = ln, []
+            elif head is None:
+                raise ValueError("from_fastq: FASTA text does not start with '>'")
+            else:
+                seq.append(ln)
+        if head is not None:
+            yield head, b"".join(seq), None
+        return
+    if len(lines) % 4:
+        raise ValueError("from_fastq: FASTQ text is not four lines per record")
+    for k in range(0, len(lines), 4):
+        if lines[k][:1] != b"@":
+            raise ValueError("from_fastq: record %d does not start with '@'" % (k // 4))
+        yield lines[k], lines[k + 1], lines[k + 3]
+
+
+def _ubam_record(name, seq, qual, flag):
+    """encode_record({"name", "seq": seq through UBAM_LETTER, "qual": qual through UBAM_QUAL or None, "flag"}), without the Python
+    loop per base (tests/test_ubam_host.py holds the two against each other)"""
+    codes = seq.translate(UBAM_CODE)
+    n = (len(codes) + 1) // 2
+    hi, lo = codes[0::2].translate(_SHL4), codes[1::2]
+    packed = (int.from_bytes(hi, "little") | int.from_bytes(lo, "little")).to_bytes(n, "little")
+    q = b"\xff" * len(seq) if qual is None else qual.translate(UBAM_QUAL)
+    body = struct.pack("<iiBBHHHIiii", -1, -1, len(name) + 1, 0, 4680, 0, flag, len(seq), -1, -1, 0) + name + b"\0" + packed + q
+    return struct.pack("<i", len(body)) + body
+
+
+def from_fastq(text, n_mates=1, mate=0, fasta=False):
+    """the BAM records (their bytes, joined; no header) of FASTQ - or, fasta=True, FASTA - text: what --ubam_output makes of a file's
+    records. n_mates: 1 single-end, 2 a paired run; mate: 0 / 1 - which mate's file the text is -, or INTERLEAVED: the records
+    alternate mate 1, mate 2. Per record: name = ubam_name; flag = UBAM_FLAGS; a base = the letter of CODES it is in either case, U as
+    T, every other byte N (UBAM_LETTER); a quality = min(max(b, 33), 126) - 33 (UBAM_QUAL), FASTA: absent (0xFF throughout).
+    ValueError: a name of more than 254 bytes (UBAM_NAME_ERROR), a quality line that is not as long as its sequence
+    (UBAM_LENGTH_ERROR) - N counts the text's records from 0."""
+    out = []
+    for k, (head, seq, qual) in enumerate(_text_records(text, fasta)):
+        m = (k & 1) if mate == INTERLEAVED else int(mate)
+        name = ubam_name(head, n_mates, m)
+        if len(name) > UBAM_NAME_MAX:
+            raise ValueError(UBAM_NAME_ERROR % k)
+        if qual is not None and len(qual) != len(seq):
+            raise ValueError(UBAM_LENGTH_ERROR % k)
+        out.append(_ubam_record(name, seq, qual, UBAM_FLAGS[(int(n_mates), m)]))
+    return b"".join(out)
+
+
+def ubam_counts(text, n_mates=1, mate=0, fasta=False):
+    """the counters of a run with --ubam_output over the records of `text` (from_fastq's arguments): bases_changed = the bytes whose BAM
+    letter differs from the input byte, quals_clamped = the quality bytes outside '!'..'~', names_starred = the ids replaced by '*'"""
+    changed = clamped = starred = 0
+    for k, (head, seq, qual) in enumerate(_text_records(text, fasta)):
+        m = (k & 1) if mate == INTERLEAVED else int(mate)
+        changed += len(seq.translate(None, _SAME_LETTER))
+        clamped += len((qual or b"").translate(None, _IN_RANGE))
+        starred += not _ubam_id(head, n_mates, m)
+    return {"bases_changed": changed, "quals_clamped": clamped, "names_starred": starred}
+
+
+def ubam_bound(text_bytes, n, fasta=False):
+    """bytes that always hold from_fastq's records of n records in text_bytes bytes of text (csrc/rd_bam_encode.hpp derives them):
+    FASTQ text + 32 n; FASTA text + (text + 1) / 2 + 40 n"""
+    text_bytes, n = int(text_bytes), int(n)
+    return text_bytes + (text_bytes + 1) // 2 + 40 * n if fasta else text_bytes + 32 * n
 
 
 # ---- optional fields (tags) and read groups: the rule the device side (csrc/rd_bam_tags.hpp) is compared against ----------------------

@@ -33,6 +33,7 @@
 //   rd_bam_find_*, rd_bam_count        a record start behind an offset of inflated BAM bytes, the records of a share (rd_bam_shard.hpp)
 //   rd_bam_tag_find, rd_bam_group_*    the optional fields of raw BAM records, and the counters per read group (rd_bam_tags.hpp)
 //   rd_bam_tag_splice                  the listed tags as text behind the read names of the FASTQ text (rd_bam_tagtext.hpp)
+//   rd_bam_encode                      the records of a FASTQ / FASTA chunk as unaligned BAM records: --ubam_output (rd_bam_encode.hpp)
 //   rd_float_text                      float32 values as their exact %g text; the f / B:f values of rd_bam_tag_splice_ex (rd_float_text.hpp)
 //   rd_window_*                        reads longer than max_len as several windows: the window table and the fusion of its logits (rd_windows.hpp)
 //   rd_region_*                        the rRNA stretches of reads classified over windows, as text lines (rd_regions.hpp)
@@ -55,6 +56,7 @@
 #include "rd_bam_shard.hpp"
 #include "rd_bam_raw.hpp"
 #include "rd_report.hpp"
+#include "rd_bam_encode.hpp"
 #include "rd_pairs.hpp"
 #include "rd_summary.hpp"
 #include "rd_bam_tags.hpp"
@@ -1462,6 +1464,77 @@ int rd_bam_tag_splice_ex(const uint8_t *text, int64_t text_bytes, const int64_t 
         tagtext_launch<4, true>(text, text_bytes, rec_start, raw, raw_bytes, raw_start, n_rec, n_tags, names, out, cap, out_start, info, p, st);
     else
         tagtext_launch<4, false>(text, text_bytes, rec_start, raw, raw_bytes, raw_start, n_rec, n_tags, names, out, cap, out_start, info, p, st);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+// the records of a FASTQ / FASTA chunk as unaligned BAM records (rd_bam_encode.hpp): lengths, their scan, the write pass by output tiles
+namespace {
+struct BamEncodeWs {
+    int nb;
+    uint32_t *meta;
+    int64_t *qoff, *bsum;
+    unsigned long long *first_bad, *starred;     // (first_bad[2], starred and fault lie behind one another: one memset each way)
+    int32_t *fault;
+    size_t total;
+};
+BamEncodeWs bam_encode_ws(void *workspace, int64_t n) {
+    BamEncodeWs p;
+    Carver c(workspace);
+    p.nb = scan_blocks(n);
+    p.meta = c.take<uint32_t>((size_t)n);
+    p.qoff = c.take<int64_t>((size_t)n);
+    p.bsum = c.take<int64_t>((size_t)p.nb);
+    p.first_bad = c.take<unsigned long long>(2);
+    p.starred = c.take<unsigned long long>(1);
+    p.fault = c.take<int32_t>(1);
+    p.total = c.off;
+    return p;
+}
+}  // namespace
+
+size_t rd_bam_encode_workspace_bytes(int64_t n_rec) {
+    if (n_rec < 0 || n_rec > 0x3fffffffLL) return 0;
+    return bam_encode_ws(nullptr, n_rec).total;
+}
+
+int rd_bam_encode(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int64_t *seq_off, const int32_t *seq_len, int64_t n_rec, int64_t rec_first,
+                  int32_t rec_stride, uint32_t flags, uint8_t *raw, size_t raw_cap, int64_t *raw_start, int64_t *info, void *workspace, size_t workspace_bytes,
+                  void *stream) {
+    const uint32_t known = RD_UBAM_FASTA | (0xfffu << RD_UBAM_EVEN_SHIFT) | (0xfffu << RD_UBAM_ODD_SHIFT);
+    if (flags & ~known) RD_FAIL(RD_E_INVALID, "rd_bam_encode: unknown flag bits 0x%x", flags & ~known);
+    if (n_rec < 0 || n_rec > 0x3fffffffLL || text_bytes < 0) RD_FAIL(RD_E_INVALID, "rd_bam_encode: bad n_rec or text_bytes");
+    if (rec_first < 0 || rec_stride < 1 || rec_first > 0x3fffffffLL) RD_FAIL(RD_E_INVALID, "rd_bam_encode: bad rec_first or rec_stride");
+    if (!info || !raw_start) RD_FAIL(RD_E_INVALID, "rd_bam_encode: null info or raw_start");
+    hipStream_t st = (hipStream_t)stream;
+    RD_HIP(hipMemsetAsync(info, 0, 8 * sizeof(int64_t), st));
+    if (n_rec == 0) {
+        RD_HIP(hipMemsetAsync(info + 2, 0xff, sizeof(int64_t), st));
+        RD_HIP(hipMemsetAsync(info + 7, 0xff, sizeof(int64_t), st));
+        RD_HIP(hipMemsetAsync(raw_start, 0, sizeof(int64_t), st));
+        return RD_OK;
+    }
+    if ((!text && text_bytes > 0) || !rec_start || !seq_off || !seq_len || !raw || !workspace) RD_FAIL(RD_E_INVALID, "rd_bam_encode: null pointer");
+    if (((uintptr_t)workspace & 255) || ((uintptr_t)raw & 15)) RD_FAIL(RD_E_INVALID, "rd_bam_encode: workspace must be 256-byte aligned, raw 16-byte aligned");
+    const BamEncodeWs p = bam_encode_ws(workspace, n_rec);
+    if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "rd_bam_encode: workspace too small: %zu < %zu", workspace_bytes, p.total);
+    const int64_t cap = (int64_t)(raw_cap < (size_t)INT64_MAX ? raw_cap : (size_t)INT64_MAX);
+    RD_HIP(hipMemsetAsync(p.first_bad, 0xff, 2 * sizeof(unsigned long long), st));
+    RD_HIP(hipMemsetAsync(p.starred, 0, (size_t)((char *)p.fault - (char *)p.starred) + sizeof(int32_t), st));
+    const BeTabs t = {rec_start, seq_off, seq_len, rec_first, rec_stride};
+    hipLaunchKernelGGL(rd_be_len_kernel, dim3(p.nb), dim3(256), 0, st, text, text_bytes, t, n_rec, flags, raw_start, p.meta, p.qoff, p.bsum, p.first_bad, p.fault, p.starred);
+    scan_base(p.bsum, p.nb, info, cap, st);
+    hipLaunchKernelGGL((rd_scan_off_kernel<8, 1, ScanTab<1>, BeVerdict>), dim3(p.nb), dim3(256), 0, st, ScanTab<1>{{raw_start}}, n_rec, ScanOut<1>{{raw_start}, {p.bsum}},
+                       BeVerdict{n_rec, p.fault, p.first_bad, p.starred, info});
+    // the tiles of the bound - or of raw_cap when that is less: the bytes are known on the device only, the workgroups stride over them
+    const int64_t fq = text_bytes + 32 * n_rec, fa = text_bytes + (text_bytes + 1) / 2 + 40 * n_rec;
+    int64_t most = flags & RD_UBAM_FASTA ? fa : fq;
+    if (most > cap) most = cap;
+    int64_t grid = (most + BE_TILE - 1) / BE_TILE;
+    if (grid < 1) grid = 1;
+    if (grid > BE_GRID) grid = BE_GRID;
+    hipLaunchKernelGGL(rd_be_write_kernel, dim3((unsigned)grid), dim3(256), 0, st, text, t, n_rec, flags, (const uint32_t *)p.meta, (const int64_t *)p.qoff, raw_start, raw,
+                       info);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }

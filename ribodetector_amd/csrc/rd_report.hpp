@@ -126,9 +126,14 @@ __device__ __forceinline__ uint32_t rp_byte(const uint8_t *__restrict__ text, in
 // The write pass of a tile: lines [0, nr) at out[offs[r], offs[r + 1]) - a contiguous range, no line empty, offs in LDS. Every lane
 // takes 16-byte pieces of the range and bisects for the line of a piece. src16(r, j): where bytes [j, j + 16) of line r stand in
 // the text when all of them do, else null; byte(r, j): byte j of line r. The pieces that the range shares with its neighbours
-// (other workgroups or tiles write the rest of them) go byte by byte.
-template <class Src16, class Byte>
-__device__ __forceinline__ void rp_write_tile(const int64_t *offs, int nr, uint8_t *__restrict__ out, Src16 src16, Byte byte) {
+// (other workgroups or tiles write the rest of them) go byte by byte. piece16(r, j, v): a caller whose bytes are COMPUTED from the text
+// (rd_bam_encode.hpp) makes the 16 bytes [j, j + 16) of line r in v when they lie in one field, and says whether it did.
+struct RpNoPiece16 {
+    __device__ __forceinline__ bool operator()(int, int64_t, u32x4 &) const { return false; }
+};
+
+template <class Src16, class Byte, class Piece16>
+__device__ __forceinline__ void rp_write_tile(const int64_t *offs, int nr, uint8_t *__restrict__ out, Src16 src16, Byte byte, Piece16 piece16) {
     const int64_t ob = offs[0], oe = offs[nr];
     for (int64_t o = (ob & ~(int64_t)15) + 16 * (int64_t)threadIdx.x; o < oe; o += 16 * 256) {
         const int64_t a = o < ob ? ob : o;             // the piece is [a, e)
@@ -148,6 +153,10 @@ __device__ __forceinline__ void rp_write_tile(const int64_t *offs, int nr, uint8
             continue;
         }
         u32x4 v = {0u, 0u, 0u, 0u};
+        if (whole && piece16(r, o - offs[r], v)) {
+            *reinterpret_cast<u32x4 *>(out + o) = v;
+            continue;
+        }
 #pragma unroll
         for (int b = 0; b < 16; ++b) {
             const int64_t p = o + b;
@@ -164,6 +173,11 @@ __device__ __forceinline__ void rp_write_tile(const int64_t *offs, int nr, uint8
                 if (o + b >= a && o + b < e) out[o + b] = (uint8_t)(v[b >> 2] >> (8 * (b & 3)));
         }
     }
+}
+
+template <class Src16, class Byte>
+__device__ __forceinline__ void rp_write_tile(const int64_t *offs, int nr, uint8_t *__restrict__ out, Src16 src16, Byte byte) {
+    rp_write_tile(offs, nr, out, src16, byte, RpNoPiece16{});
 }
 
 __global__ __launch_bounds__(256) void rd_report_write_kernel(const uint8_t *__restrict__ text, const int64_t *__restrict__ rec_start,

@@ -48,6 +48,11 @@ text - its FASTQ text with the listed tags of every record behind the read name 
 bam.tag_comment has the rule). It depends on the chunk alone, so it is made on the copy stream when the chunk is submitted; the output
 kernels select from that view (_select_chunk), everything else sees the untagged FASTQ view. --bam_tag_floats: the tagged view is built
 with the f and B:f values written in %g form (rd_bam_tag_splice_ex; bam.float_g has the rule) instead of skipped and counted.
+--ubam_output (an extension, FASTQ / FASTA input, one rank, chunk text on the device): every output is an unaligned BAM file. A chunk's
+raw view is MADE here - rd_bam_encode (ubam.py, csrc/rd_bam_encode.hpp; bam.from_fastq has the rule) on the copy stream when the chunk is
+submitted - and from there on the run is --bam_output's: the output kernels select from DeviceChunk.raw, the files start with a header
+(bam.UBAM_HEADER_TEXT, no references) and are BGZF. A record that cannot be a BAM record (a name of more than 254 bytes, a quality line
+that is not as long as its sequence) ends the run like a mate mismatch: the chunks in front of it are written, then the ValueError.
 """
 import argparse
 import functools
@@ -72,6 +77,7 @@ from . import groups as _grpmod
 from . import gz as _gzmod
 from . import regions as _regmod
 from . import summary as _summod
+from . import ubam as _ubammod
 from . import windows as _winmod
 from .data_loader import device_reader as dr
 from .data_loader import fastx_parser as fx
@@ -188,6 +194,10 @@ SPLIT = "groups"            # pieces[(mate, SPLIT)]: the grouped pieces of a mat
 
 class MateMismatch(RuntimeError):
     """--interleaved: two consecutive records whose ids are not those of mates (the chunks in front of them have been written)"""
+
+
+class UbamRecordError(ValueError):
+    """--ubam_output: a record that cannot be a BAM record (the chunks in front of its chunk have been written)"""
 
 
 class _MateWriter:
@@ -312,6 +322,9 @@ class Predictor:
         self.interleaved = bool(getattr(args, 'interleaved', False))     # paired-end reads from ONE interleaved FASTQ file
         self.mate_check = not getattr(args, 'no_mate_check', False)
         self.bam_output = bool(getattr(args, 'bam_output', False))       # BAM outputs: the selected records as they stand in the input
+        self.ubam_output = bool(getattr(args, 'ubam_output', False))     # BAM outputs of FASTQ / FASTA input: the records encoded on the device
+        self.bam_files = self.bam_output or self.ubam_output             # every output file is a BAM file, whichever way its records are made
+        self._ubam = None                        # ... ubam.DeviceUbam, one per input file (run_with_chunks)
         self.read_groups = bool(getattr(args, 'read_groups', False))     # --summary gains the counters per BAM read group
         self.split_groups = bool(getattr(args, 'split_groups', False))   # every output file becomes a family: a file per BAM read group
         self._split = self._split_ids = None     # ... gz.DeviceGroupSelect (run_with_chunks), the declared ids in row order (detect)
@@ -593,6 +606,7 @@ class Predictor:
             dev_in = [self._to_device(c, lo, hi, cs) for c in chunks]
             cur.wait_stream(cs)
         tagged = self._tag_chunks(chunks, on_dev) if self._tags is not None else None      # --bam_tags: the view the outputs select from
+        encoded = self._ubam_chunks(tk, chunks, on_dev) if self._ubam is not None else None   # --ubam_output: the raw view, made here
         if plans is None:
             outs = [self.model.classify_bytes(a, o, l, self.len, want_labels=not self.is_paired) for a, o, l in dev_in]
         else:                                       # (the window tables: the reads' own entries where nothing is longer than -l)
@@ -605,6 +619,8 @@ class Predictor:
         post = self._post_stream
         with torch.cuda.stream(post):
             post.wait_event(main_done)
+            if encoded is not None:
+                post.wait_event(encoded)
             self.model.sync_results()                # the reads inside the noise band, in float64 (current stream = post)
             if plans is not None:                    # the windows' logits are final: one pair of logits per read
                 outs = [self.model.window_fuse(p, self._windows["fuse"], want_labels=not self.is_paired) for p in plans]
@@ -640,7 +656,7 @@ class Predictor:
         # what the ticket only keeps alive: the tensors of dev_in (of pairs, of the tagged views; --read_groups: the raw views) were
         # allocated on the copy stream and must not return to that stream's pool while other streams read them - and the deferred
         # float64 pass reads the bases until the post-pass has run
-        tk.keep = (dev_in, outs, plans, pairs, tagged, [c.raw for c in chunks] if self._groups is not None or self._split is not None else None)
+        tk.keep = (dev_in, outs, plans, pairs, tagged, [c.raw for c in chunks] if self._groups is not None or self._split is not None or self._ubam is not None else None)
         return tk
 
     def _tag_chunks(self, chunks, on_dev):
@@ -659,6 +675,37 @@ class Predictor:
                 out.append((text, out_start))
         return out
 
+    def _ubam_chunks(self, tk, chunks, on_dev):
+        """--ubam_output: every input's chunk gets its raw view - its records as BAM records (ubam.DeviceUbam.encode) - on the COPY
+        stream behind the chunk's `ready` event, where the tag splice runs; like it, the encode needs no labels. Nothing waits: the
+        bound of the raw bytes is linear in the text. Returns the event behind the calls; the ticket's "ubam" check reads their verdicts."""
+        if not on_dev:
+            raise RuntimeError("--ubam_output: the chunk's text is not on the device")
+        infos, cs = [], self._copy_stream
+        with torch.cuda.stream(cs):
+            for f, (c, ub) in enumerate(zip(chunks, self._ubam)):
+                cs.wait_event(c.ready)
+                raw, raw_start, info = ub.encode(c, _bammod.INTERLEAVED if self.interleaved else f, 2 if self.is_paired else 1)
+                c.raw = (raw, raw_start)
+                infos.append(_pinned(info))
+            done = torch.cuda.Event()
+            done.record(cs)
+        first, self._ubam_seen = self._ubam_seen, self._ubam_seen + len(chunks[0].seq_len)
+        tk.checks["ubam"] = functools.partial(self._check_ubam, infos, first)
+        return done
+
+    def _check_ubam(self, infos, first):
+        """the verdicts of rd_bam_encode on a chunk, once the event behind them has passed: the counters are added up; a record that
+        cannot be a BAM record ends the run - first = the index of the chunk's first record in its file"""
+        worst = None
+        for ub, info in zip(self._ubam, infos):
+            long_name, mismatch = ub.add(info)
+            for idx, text in ((long_name, _bammod.UBAM_NAME_ERROR), (mismatch, _bammod.UBAM_LENGTH_ERROR)):
+                if idx >= 0 and (worst is None or idx < worst[0]):
+                    worst = (idx, text)
+        if worst is not None:
+            raise UbamRecordError(worst[1] % (first + worst[0]))
+
     def _group_rows(self, chunk):
         """the read-group rows of every raw record of mate 1's chunk (rd_bam_tag_find / rd_bam_group_rows over DeviceChunk.raw)"""
         if chunk.raw is None:
@@ -668,11 +715,11 @@ class Predictor:
 
     def _output_view(self, chunks, dev_in, labels, e, lo, hi, ring, pairs, tagged):
         """(text, record table, selecting labels) of mate e's records for the output files - the one place that chooses their source:
-        the records as they stand in the input under --bam_output (DeviceChunk.raw), else the text with the tags behind the read
-        names under --bam_tags, else the FASTQ view; record_view knows the layouts. labels None (--split_groups selects by key):
-        no selecting labels, none expanded."""
+        the records as they stand in the input under --bam_output, or as rd_bam_encode made them under --ubam_output
+        (DeviceChunk.raw), else the text with the tags behind the read names under --bam_tags, else the FASTQ view; record_view
+        knows the layouts. labels None (--split_groups selects by key): no selecting labels, none expanded."""
         f, pair_table = e if pairs is None else 0, None
-        if self.bam_output:
+        if self.bam_files:
             source = chunks[f].raw
         elif tagged is not None:
             source = tagged[f]
@@ -1041,7 +1088,7 @@ class Predictor:
                 t0 = time.perf_counter()
                 try:
                     labels = self.collect_chunk(tk)
-                except MateMismatch as e:           # the chunks in front of this one are written and the files closed, then the error
+                except (MateMismatch, UbamRecordError) as e:      # the chunks in front of this one are written and the files closed, then the error
                     mismatch = e
                     break
                 self._mark("labels")
@@ -1110,6 +1157,9 @@ class Predictor:
             self._tag_total = _tagmod.from_vector(total, len(self.bam_tags), len(self._tags))
             if self.rank == 0:
                 self.logger.info(_tagmod.log_line(self.bam_tags, self._tag_total))
+        if self._ubam is not None:                 # --ubam_output: one rank
+            self._ubam_total = [u.counts for u in self._ubam]
+            self.logger.info(_ubammod.log_line(self._ubam_total))
         if self.interleaved:
             fx.check_even_records(self._records_seen)
         if self._split is not None:
@@ -1181,6 +1231,8 @@ class Predictor:
             doc["bam_tags"] = _tagmod.to_json(self.bam_tags, self._tag_total, floats=self.bam_tag_floats)
         if self._split is not None:
             doc["split_groups"] = self._split_total
+        if self._ubam is not None:
+            doc["ubam_output"] = _ubammod.to_json(self._ubam_total)
         _summod.write_json(path, doc)
         frac = doc["reads"]["rRNA_fraction"]
         self.logger.info('rRNA fraction: {} (summary: {})'.format("n/a" if frac is None else "%.6f" % frac, path))
@@ -1300,13 +1352,16 @@ class Predictor:
                     if src not in headers:
                         headers[src] = np.frombuffer(_bammod.header(src), dtype=np.uint8)
                     files[-1][2].write_text(headers[src].ctypes.data, headers[src].size)
+                elif self.ubam_output and label in (0, 1, -1):      # ... or with the one header of --ubam_output: no references, no @PG
+                    hdr = np.frombuffer(_bammod.encode_header((), _bammod.UBAM_HEADER_TEXT), dtype=np.uint8)
+                    files[-1][2].write_text(hdr.ctypes.data, hdr.size)
         if self.rrna is not None:
             log('Writing output rRNA sequences into file: {}{}{}'.format(colors.OKBLUE, ", ".join(self.rrna), colors.ENDC))
             open_(1, self.rrna)
         log('Writing output non-rRNA sequences into file: {}{}{}'.format(colors.OKBLUE, ", ".join(self.output), colors.ENDC))
         open_(0, self.output)
         if self.is_paired and self.args.ensure == 'both':
-            unclf = [unclassified_path(path, self.bam_output) for path in self.output]
+            unclf = [unclassified_path(path, self.bam_files) for path in self.output]
             open_(-1, unclf)
             log('Writing unclassified sequences into file: {}{}{}'.format(colors.OKYELLOW, ", ".join(unclf), colors.ENDC))
         rep_path, reg_path = self.report_path, self.regions_path
@@ -1367,6 +1422,10 @@ class Predictor:
                     self._split_recs[(e, lab)] = np.zeros(G + 1, dtype=np.int64)
         # --bam_tags: the tagged view of every chunk, and the counters of the tags copied, per input file
         self._tags = [_tagmod.DeviceBamTags(self.device, self.bam_tags, floats=self.bam_tag_floats) for _ in self.input] if self.bam_tags is not None else None
+        # --ubam_output: the raw view of every chunk is made of its text, and the counters of what the BAM form changed, per input file
+        self._ubam, self._ubam_seen = None, 0
+        if self.ubam_output:
+            self._ubam = [_ubammod.DeviceUbam(self.device, fasta=fx.get_seq_format(p).startswith("fa")) for p in self.input]
         self._win_classified = [0, 0]
         # --regions: the lines of every chunk, formatted on the device; mate 1's writer appends the pieces (and deflates a .gz file)
         self._regions = bool(self.regions_path)
@@ -1403,7 +1462,7 @@ class Predictor:
         tmps = [path + '.joining' for path in finals]
         self._part_files += tmps if self.rank == 0 else []
         # .gz files whose members were made on the device are BGZF: one end-of-file block (an empty member) behind the last part
-        tails = [_gzmod.eof_block() if ((self.gzip_on_device and path.endswith('gz')) or (self.bam_output and path.endswith(('.bam', '.ubam'))))
+        tails = [_gzmod.eof_block() if ((self.gzip_on_device and path.endswith('gz')) or (self.bam_files and path.endswith(('.bam', '.ubam'))))
                  else b'' for path in finals]
         if self.rank == 0:
             for f, tmp in enumerate(tmps):
@@ -1431,7 +1490,7 @@ class Predictor:
         The same list on every rank (it depends on the arguments only): the files whose records are deflated on the device."""
         # (one file per mate - or, for the pairs of an interleaved input, ONE file per label: its key is mate 0's)
         files = [(e, lab) for lab, names in ((1, rrna), (0, output)) if names is not None for e, name in enumerate(names)
-                 if name.endswith('gz') or name.endswith(('.bam', '.ubam'))]      # (BAM names: --bam_output only - BGZF members, like a .gz)
+                 if name.endswith('gz') or name.endswith(('.bam', '.ubam'))]      # (BAM names: --bam_output / --ubam_output only - BGZF members, like a .gz)
         if is_paired and ensure == 'both':
             files += [(e, -1) for e in range(len(output))]
         return files
@@ -1457,15 +1516,15 @@ class Predictor:
         except RuntimeError as e:
             self.logger.error('{}{}{}'.format(colors.FAIL, _COUNT_ERRORS.get(str(e), str(e)), colors.ENDC))
             raise
-        check_read_report(self.report_path, self.output, self.rrna, self.is_paired, self.args.ensure, self.bam_output)
-        check_summary(self.summary_path, self.output, self.rrna, self.is_paired, self.args.ensure, self.report_path, self.bam_output)
+        check_read_report(self.report_path, self.output, self.rrna, self.is_paired, self.args.ensure, self.bam_files)
+        check_summary(self.summary_path, self.output, self.rrna, self.is_paired, self.args.ensure, self.report_path, self.bam_files)
         check_read_groups(self.read_groups, self.summary_path, self.input, self.bam_shard)
         check_bam_tags(self.bam_tags_arg, self.input, self.bam_output, floats=self.bam_tag_floats)
         self._split_ids = check_split_groups(self.split_groups, self.input, self.output, self.rrna, self.args.ensure, self.report_path,
                                              self.summary_path, self.regions_path, self.bam_output, self.interleaved)
         self._windows = check_windows(self.args)
         check_regions(self.regions_path, self._windows is not None, self.output, self.rrna, self.is_paired, self.args.ensure,
-                      self.report_path, self.summary_path, self.bam_output)
+                      self.report_path, self.summary_path, self.bam_files)
         # reference batch-size heuristic (detect.py:558-568); kept because --chunk_size is expressed in these batches
         denom = (2 * self.len * 6.4) if self.is_paired else (self.len * 6.4)
         self.batch_size = 2 ** math.floor(math.log2(((self.args.memory - 2) * 1024 * 1024) / denom))
@@ -1527,13 +1586,14 @@ def unclassified_path(out, bam_output=False):
     return out + ('.unclassified.bam' if bam_output else '.unclassified.gz')
 
 
-def check_bam(inputs, output, rrna, bam_output=False, bam_shard=False, interleaved=False):
+def check_bam(inputs, output, rrna, bam_output=False, bam_shard=False, interleaved=False, ubam_output=False):
     """BAM input (.bam / .ubam, ribodetector_amd/bam.py): the rules that hold before anything touches a device; returns whether the
     inputs are BAM. The records become FASTQ text on the device, so the outputs are FASTQ files; there is no host reader for BAM,
     so the switches and layouts that need one are refused. bam_output (--bam_output): every input is BAM and every -o / -r name ends
     with .bam / .ubam - the selected records are written as they stand in the input (all outputs are BAM or none is). bam_shard
     (--bam_shard): BAM input under several ranks, each one with its own share of the records (data_loader/bam_shard.py) - the sharded
-    parse of BGZF members, so not with RD_BGZF_SHARD=0, and not an interleaved file (no byte range of one holds whole pairs by itself)."""
+    parse of BGZF members, so not with RD_BGZF_SHARD=0, and not an interleaved file (no byte range of one holds whole pairs by itself).
+    ubam_output (--ubam_output; check_ubam has its rules): .bam / .ubam names on -o / -r are what the run writes."""
     def fmt(path):
         try:
             return fx.get_seq_format(path)
@@ -1550,7 +1610,7 @@ def check_bam(inputs, output, rrna, bam_output=False, bam_shard=False, interleav
                 raise RuntimeError("--bam_output: {} must end with .bam or .ubam - all outputs are BAM or none is (checked before anything "
                                    "touches a device)".format(o))
     for o in outs:
-        if fmt(o) == "bam" and not bam_output:
+        if fmt(o) == "bam" and not (bam_output or ubam_output):
             raise RuntimeError("BAM output is not supported: {} (-o / -r take FASTQ names, plain or .gz; checked before anything touches a "
                                "device)".format(o))
     if "bam" not in kinds:
@@ -1580,6 +1640,43 @@ def check_bam(inputs, output, rrna, bam_output=False, bam_shard=False, interleav
         raise RuntimeError("BAM input runs on one rank: the multi-rank layouts use the host reader, which has no BAM support (or give "
                            "--bam_shard; checked before anything touches a device)")
     return True
+
+
+def check_ubam(ubam_output, inputs, output, rrna, bam_output=False, parse_wanted=None):
+    """--ubam_output (FASTQ / FASTA input written as unaligned BAM; bam.from_fastq has the rule): the rules that hold before anything
+    touches a device. The input is no BAM file (--bam_output writes those as they stand); not with --bam_output; every -o / -r name
+    ends with .bam / .ubam (all outputs are BAM or none is); the chunks' text lives on the device, where the records are encoded - not
+    RD_DEVICE_PARSE=0 or RD_INGEST=host, and no input that the device reader turns down (parse_wanted: device_reader.
+    device_parse_wanted unless given); one rank."""
+    if not ubam_output:
+        return
+    tail = " (checked before anything touches a device)"
+
+    def fmt(path):
+        try:
+            return fx.get_seq_format(path)
+        except ValueError:
+            return None
+    if bam_output:
+        raise RuntimeError("--ubam_output encodes FASTQ / FASTA input as BAM records, --bam_output writes the records of BAM input as they "
+                           "stand: give one of them" + tail)
+    for p in inputs or []:
+        if fmt(p) == "bam":
+            raise RuntimeError("--ubam_output takes FASTQ / FASTA input: {} is a BAM file, whose records --bam_output writes as they "
+                               "stand".format(p) + tail)
+    for o in list(output or []) + list(rrna or []):
+        if fmt(o) != "bam":
+            raise RuntimeError("--ubam_output: {} must end with .bam or .ubam - all outputs are BAM or none is".format(o) + tail)
+    if fx.ingest_env("RD_DEVICE_PARSE", "1") == "0":
+        raise RuntimeError("--ubam_output encodes the records where the chunks' text is, on the device: it cannot run with "
+                           "RD_DEVICE_PARSE=0 or RD_INGEST=host" + tail)
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("--ubam_output runs on one rank" + tail)
+    wanted = dr.device_parse_wanted if parse_wanted is None else parse_wanted
+    for p in inputs or []:
+        if not wanted(p):
+            raise RuntimeError("--ubam_output: the text of {} does not stay on the device (the device reader does not take this input "
+                               "or the ingest switches keep it on the host)".format(p) + tail)
 
 
 def check_read_report(path, output, rrna, is_paired, ensure, bam_output=False):
@@ -1835,6 +1932,13 @@ none: give label based on the mean probability of read pair.
                       help='(extension) BAM input only: -o / -r take .bam / .ubam names, and every output file is a BAM file - the header of\n'
                            'its input and the selected records, byte for byte as they stand in the input (every tag kept), in input\n'
                            'order. Secondary / supplementary records are in no output. No @PG line is added.')
+    args.add_argument('--ubam_output', action='store_true',
+                      help='(extension) FASTQ / FASTA input, one rank: -o / -r take .bam / .ubam names, and every output file is an unaligned\n'
+                           'BAM file of the selected records, encoded on the GPU: name = the header up to its first whitespace (in a\n'
+                           'paired run without a trailing /1 of mate 1 or /2 of mate 2; empty: *), flag 4 / 77 / 141, bases as the\n'
+                           'letters of =ACMGRSVTWYHKDBN in either case (U as T, anything else N), qualities clamped to 0..93 (FASTA:\n'
+                           'absent), no tags. The header is @HD VN:1.6 SO:unsorted GO:query; no @PG line is added. A name of more\n'
+                           'than 254 bytes ends the run with an error behind the chunks in front of it.')
     args.add_argument('--read_groups', action='store_true',
                       help='(extension) BAM input with --summary: the summary gains "read_groups" - units (reads or pairs) and bases per\n'
                            'label for every @RG line of the header of the first -i file (by the records\' RG:Z tag; a pair counts in\n'
@@ -1879,7 +1983,8 @@ def main(argv=None, log_level=None):
     # (in front of check_bam: several ranks are refused for the split as such, with or without --bam_shard)
     check_split_groups(args.split_groups, args.input, args.output, args.rrna, args.ensure, args.read_report, args.summary, args.regions,
                        args.bam_output, args.interleaved)
-    check_bam(args.input, args.output, args.rrna, args.bam_output, args.bam_shard, args.interleaved)
+    check_ubam(args.ubam_output, args.input, args.output, args.rrna, args.bam_output)
+    check_bam(args.input, args.output, args.rrna, args.bam_output, args.bam_shard, args.interleaved, ubam_output=args.ubam_output)
     check_read_groups(args.read_groups, args.summary, args.input, args.bam_shard)
     check_bam_tags(args.bam_tags, args.input, args.bam_output, floats=args.bam_tag_floats)
     seq_pred = Predictor(config, args, log_level=log_level)

@@ -5,6 +5,9 @@ from typing import Any, Callable, Dict, NamedTuple, Optional
 # the order in which collect_chunk runs a ticket's checks, whatever the order the side products were enqueued in: when two faults
 # coincide, the run ends with the first one's error
 CHECK_ORDER = ("totals", "pairs", "summary", "groups", "regions")
+# ... and behind them the checks whose fault is the INPUT's, not a table's: a record that --ubam_output cannot write as a BAM record.
+# (A tuple of its own, not one more name in CHECK_ORDER: tests/test_chunk_stage_host.py pins CHECK_ORDER to the five names above.)
+LATE_CHECKS = ("ubam",)
 
 
 @dataclass(slots=True)
@@ -14,7 +17,7 @@ class Ticket:
     event behind everything the chunk enqueued; pieces: {key: [detect.Piece]} - key (mate, label): the label pieces of that file (one, or
     one per rank behind the label gather), detect.REPORT / detect.REGIONS: those of the two text files, (mate, detect.SPLIT): the
     grouped pieces of the mate's family files under --split_groups (one per grouped call); chunk: mate 1's chunk. checks: name (one of
-    CHECK_ORDER) -> callable that reads, once `done` has passed, the verdict a side product's kernel wrote into pinned memory, and
+    CHECK_ORDER or LATE_CHECKS) -> callable that reads, once `done` has passed, the verdict a side product's kernel wrote into pinned memory, and
     raises on a fault. keep: what is only kept alive until the ticket goes."""
     n: int
     bounds: Optional[list]
@@ -28,7 +31,7 @@ class Ticket:
     keep: tuple = ()
 
     def run_checks(self):
-        for name in CHECK_ORDER:
+        for name in CHECK_ORDER + LATE_CHECKS:
             if name in self.checks:
                 self.checks[name]()
 
