@@ -593,6 +593,27 @@ RD_API int rd_bam_encode(const uint8_t *text, int64_t text_bytes, const int64_t 
                          int64_t n_rec, int64_t rec_first, int32_t rec_stride, uint32_t flags, uint8_t *raw, size_t raw_cap,
                          int64_t *raw_start, int64_t *info, void *workspace, size_t workspace_bytes, void *stream);
 
+/* rd_bam_encode with the tags of the header lines' comments (CLI extension `--ubam_tags`; the rule is bam.py tags_from_comment). names
+ * [host]: n_names names of 2 bytes each ([A-Za-z][A-Za-z0-9], no name twice, 0 <= n_names <= RD_BAM_TAGS_MAX). n_names == 0 IS
+ * rd_bam_encode: the same launches, info int64[8]. Else every record ends in the listed tags that its header line's comment holds, in
+ * comment order, and block_size includes them. The header line ends in front of its '\n' (one '\r' in front of that is not part of it);
+ * the comment is every byte behind the ONE byte that ends the id; it is split at '\t'; a field 'XY:T:value' (X a letter, Y a letter or
+ * digit, T one of A i Z H B f) with a listed name counts when it is the first of its name. A: one byte 0x21..0x7E. i: [+-]?[0-9]{1,10}
+ * in [-2^31, 2^32 - 1], stored in the smallest of C S I (v >= 0) / c s i. Z: bytes 0x20..0x7E, H: an even number of hex digits, both
+ * with a NUL. B: a subtype of cCsSiI, then ',int' per element, each inside the subtype's range: subtype, count:uint32, elements. f and
+ * B:f are left out and counted. Anything else makes the record malformed: it gets no tags and is counted once. info [dev]
+ * int64[10 + n_names]: [0]..[7] as rd_bam_encode, but with fault 1 info[1] = the bytes the records need (a caller repeats the call
+ * once at that size); [8] records with malformed tags, [9] float values skipped, [10 + j] records in which name j was copied. A
+ * field of t text bytes makes at most max(t, 2 t - 4) tag bytes, so the bound of rd_bam_encode plus the comments' bytes always holds
+ * the records, and real comments shrink. A header line without '\n' inside its record is fault 2. workspace of
+ * rd_bam_encode_tags_workspace_bytes(n_rec, n_names) (n_names == 0: rd_bam_encode_workspace_bytes(n_rec)). Every offset the comment
+ * walk follows is compared with the record's end before it is read. */
+RD_API size_t rd_bam_encode_tags_workspace_bytes(int64_t n_rec, int32_t n_names);
+RD_API int rd_bam_encode_ex(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int64_t *seq_off, const int32_t *seq_len,
+                            int64_t n_rec, int64_t rec_first, int32_t rec_stride, uint32_t flags, const uint8_t *names, int32_t n_names,
+                            uint8_t *raw, size_t raw_cap, int64_t *raw_start, int64_t *info, void *workspace, size_t workspace_bytes,
+                            void *stream);
+
 /* Reads longer than max_len classified over WINDOWS of max_len bases (CLI extension `--windows`; the reference classifies read[:max_len],
  * reference detect.py:666-726, and that stays the rule without the flag). A window is one more (seq_off, seq_len) entry over the same
  * text, so rd_classify takes the window table as it takes a read table and its kernels do not change.

@@ -32,7 +32,7 @@ SYMBOLS = [
     "rd_summary_words", "rd_summary_accumulate",
     "rd_bam_tag_find", "rd_bam_group_rows", "rd_bam_group_accumulate",
     "rd_bam_tag_splice_workspace_bytes", "rd_bam_tag_splice", "rd_bam_tag_splice_ex", "rd_float_text",
-    "rd_bam_encode_workspace_bytes", "rd_bam_encode",
+    "rd_bam_encode_workspace_bytes", "rd_bam_encode", "rd_bam_encode_tags_workspace_bytes", "rd_bam_encode_ex",
     "rd_window_workspace_bytes", "rd_window_plan", "rd_window_fill", "rd_window_fuse",
     "rd_region_workspace_bytes", "rd_region_format",
     "rd_group_keys", "rd_group_workspace_bytes", "rd_gz_grouped_out_bound", "rd_group_pack", "rd_gz_compress_grouped",
@@ -158,6 +158,9 @@ def lib():
     L.rd_bam_encode_workspace_bytes.argtypes = [i64]
     L.rd_bam_encode_workspace_bytes.restype = sz
     L.rd_bam_encode.argtypes = [vp, i64, vp, vp, vp, i64, i64, i32, C.c_uint32, vp, sz, vp, vp, vp, sz, vp]
+    L.rd_bam_encode_tags_workspace_bytes.argtypes = [i64, i32]
+    L.rd_bam_encode_tags_workspace_bytes.restype = sz
+    L.rd_bam_encode_ex.argtypes = [vp, i64, vp, vp, vp, i64, i64, i32, C.c_uint32, C.c_char_p, i32, vp, sz, vp, vp, vp, sz, vp]
     L.rd_window_workspace_bytes.argtypes = [i64]
     L.rd_window_workspace_bytes.restype = sz
     L.rd_window_plan.argtypes = [vp, i64, i32, i64, i32, vp, vp, vp, sz, vp]

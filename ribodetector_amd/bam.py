@@ -440,23 +440,134 @@ def _text_records(text, fasta):
         yield lines[k], lines[k + 1], lines[k + 3]
 
 
-def _ubam_record(name, seq, qual, flag):
+def _ubam_record(name, seq, qual, flag, tags=b""):
     """encode_record({"name", "seq": seq through UBAM_LETTER, "qual": qual through UBAM_QUAL or None, "flag"}), without the Python
-    loop per base (tests/test_ubam_host.py holds the two against each other)"""
+    loop per base (tests/test_ubam_host.py holds the two against each other); tags: the bytes of its optional fields"""
     codes = seq.translate(UBAM_CODE)
     n = (len(codes) + 1) // 2
     hi, lo = codes[0::2].translate(_SHL4), codes[1::2]
     packed = (int.from_bytes(hi, "little") | int.from_bytes(lo, "little")).to_bytes(n, "little")
     q = b"\xff" * len(seq) if qual is None else qual.translate(UBAM_QUAL)
-    body = struct.pack("<iiBBHHHIiii", -1, -1, len(name) + 1, 0, 4680, 0, flag, len(seq), -1, -1, 0) + name + b"\0" + packed + q
+    body = struct.pack("<iiBBHHHIiii", -1, -1, len(name) + 1, 0, 4680, 0, flag, len(seq), -1, -1, 0) + name + b"\0" + packed + q + tags
     return struct.pack("<i", len(body)) + body
 
 
-def from_fastq(text, n_mates=1, mate=0, fasta=False):
+# --ubam_tags LIST (device side csrc/rd_bam_encode.hpp, C ABI rd_bam_encode_ex): the inverse of --bam_tags. A SAM-style comment of the
+# header line - '@id' one terminator byte 'XY:T:value' '\t' 'XY:T:value' ... - becomes the record's tags.
+_UBAM_TAG_TYPES = b"AiZHBf"
+_B_RANGE = {ord("c"): (-128, 127), ord("C"): (0, 255), ord("s"): (-32768, 32767), ord("S"): (0, 65535),
+            ord("i"): (-2 ** 31, 2 ** 31 - 1), ord("I"): (0, 2 ** 32 - 1)}
+_ALPHA = frozenset(b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz")
+_ALNUM = _ALPHA | frozenset(b"0123456789")
+
+
+def _tag_int(text):
+    """the value of [+-]?[0-9]{1,10}, None for any other text"""
+    digits = text[1:] if text[:1] in (b"+", b"-") else text
+    if not 1 <= len(digits) <= 10 or any(c < 48 or c > 57 for c in digits):
+        return None
+    return -int(digits) if text[:1] == b"-" else int(digits)
+
+
+def _small_int(v):
+    """type and bytes of v in [-2^31, 2^32 - 1] in the smallest type, as htslib's SAM parser stores an i value"""
+    if v >= 0:
+        return (b"C", "<B") if v <= 255 else (b"S", "<H") if v <= 65535 else (b"I", "<I")
+    return (b"c", "<b") if v >= -128 else (b"s", "<h") if v >= -32768 else (b"i", "<i")
+
+
+def ubam_comment(header_line):
+    """the comment of a header line ('@...' / '>...', with or without the line's end), or None when it has none: the line ends in
+    front of its '\\n', and one '\\r' at its end is not part of it; the id ends at the first of space, \\t, \\r, \\v, \\f (ubam_name's
+    rule); the comment is every byte behind that ONE byte"""
+    line = bytes(header_line)
+    nl = line.find(b"\n")
+    if nl >= 0:
+        line = line[:nl]
+    if line.endswith(b"\r"):
+        line = line[:-1]
+    body = line[1:]
+    end = min((p for p in (body.find(bytes([c])) for c in _ID_END) if p >= 0), default=-1)
+    return None if end < 0 else body[end + 1:]
+
+
+def tags_from_comment(header_line, tags):
+    """(tag_bytes, copied, malformed, floats) of a header line and the listed names (2 bytes each): tag_bytes = the optional fields
+    that go behind the record's qualities, in COMMENT order; copied = one bool per listed name; malformed = the record gets no tags
+    (tag_bytes empty, copied all False, floats 0); floats = the f and B:f values, which are left out.
+    The comment (ubam_comment) is split at \\t only. A field is a tag field when it is at least 5 bytes 'XY:T:...' with X a letter, Y a
+    letter or digit, T one of A i Z H B f and ':' at bytes 2 and 4; every other field is ignored, and so is a tag field whose name is
+    not listed (it is not validated). Of the tag fields with a listed name only the FIRST per name counts. Its value:
+      A  one byte 0x21..0x7E -> XY A b
+      i  [+-]?[0-9]{1,10} with value v in [-2^31, 2^32 - 1] -> the smallest type: C S I for v >= 0, c s i for v < 0
+      Z  zero or more bytes 0x20..0x7E -> XY Z bytes NUL
+      H  an even number of hex digits -> XY H bytes NUL
+      B  a subtype of cCsSiI, then ',int' per element (the syntax of i, inside the subtype's range) -> XY B s count:uint32 elements
+      f, B with subtype f: left out, counted
+    Anything else - an empty A / i / B value, a bad digit, a value out of range, an unknown subtype, an empty element or a trailing
+    comma, odd or non-hex H, a byte outside 0x20..0x7E - is malformed."""
+    tags = [bytes(t) for t in tags]
+    bad = (b"", [False] * len(tags), True, 0)
+    comment = ubam_comment(header_line)
+    out, copied, floats, seen = [], [False] * len(tags), 0, set()
+    for f in (comment.split(b"\t") if comment is not None else ()):
+        if not (len(f) >= 5 and f[0] in _ALPHA and f[1] in _ALNUM and f[2] == 58 and f[4] == 58 and f[3] in _UBAM_TAG_TYPES):
+            continue
+        name, t, v = f[:2], f[3:4], f[5:]
+        if name not in tags or name in seen:
+            continue
+        seen.add(name)
+        if t == b"A":
+            if len(v) != 1 or not 0x21 <= v[0] <= 0x7E:
+                return bad
+            enc = b"A" + v
+        elif t == b"i":
+            x = _tag_int(v)
+            if x is None or not -2 ** 31 <= x <= 2 ** 32 - 1:
+                return bad
+            ty, fmt = _small_int(x)
+            enc = ty + struct.pack(fmt, x)
+        elif t in (b"Z", b"H"):
+            if any(c < 0x20 or c > 0x7E for c in v):
+                return bad
+            if t == b"H" and (len(v) & 1 or any(c not in _HEX for c in v)):
+                return bad
+            enc = t + v + b"\0"
+        elif t == b"f" or v[:1] == b"f":
+            floats += 1
+            continue
+        else:
+            if not v or v[0] not in _B_RANGE or (len(v) > 1 and v[1] != 44):
+                return bad
+            lo, hi = _B_RANGE[v[0]]
+            vals = [_tag_int(e) for e in v[2:].split(b",")] if len(v) > 1 else []
+            if any(x is None or not lo <= x <= hi for x in vals):
+                return bad
+            enc = b"B" + v[:1] + struct.pack("<I", len(vals)) + struct.pack("<%d%s" % (len(vals), _TAG_INT[v[0]][1]), *vals)
+        out.append(name + enc)
+        copied[tags.index(name)] = True
+    return b"".join(out), copied, False, floats
+
+
+def ubam_tag_counts(text, tags, fasta=False):
+    """the counters of a run with --ubam_tags over the records of `text`: {"copied": [records in which name j was copied],
+    "malformed_records": ..., "float_values_skipped": ...}"""
+    copied, mal, fl = [0] * len(tags), 0, 0
+    for head, _, _ in _text_records(text, fasta):
+        _, c, m, f = tags_from_comment(head, tags)
+        mal += bool(m)
+        fl += f
+        for j, x in enumerate(c):
+            copied[j] += bool(x)
+    return {"copied": copied, "malformed_records": mal, "float_values_skipped": fl}
+
+
+def from_fastq(text, n_mates=1, mate=0, fasta=False, tags=None):
     """the BAM records (their bytes, joined; no header) of FASTQ - or, fasta=True, FASTA - text: what --ubam_output makes of a file's
     records. n_mates: 1 single-end, 2 a paired run; mate: 0 / 1 - which mate's file the text is -, or INTERLEAVED: the records
     alternate mate 1, mate 2. Per record: name = ubam_name; flag = UBAM_FLAGS; a base = the letter of CODES it is in either case, U as
     T, every other byte N (UBAM_LETTER); a quality = min(max(b, 33), 126) - 33 (UBAM_QUAL), FASTA: absent (0xFF throughout).
+    tags (--ubam_tags: names of 2 bytes): the record ends in tags_from_comment(header line, tags)'s bytes.
     ValueError: a name of more than 254 bytes (UBAM_NAME_ERROR), a quality line that is not as long as its sequence
     (UBAM_LENGTH_ERROR) - N counts the text's records from 0."""
     out = []
@@ -467,7 +578,8 @@ def from_fastq(text, n_mates=1, mate=0, fasta=False):
             raise ValueError(UBAM_NAME_ERROR % k)
         if qual is not None and len(qual) != len(seq):
             raise ValueError(UBAM_LENGTH_ERROR % k)
-        out.append(_ubam_record(name, seq, qual, UBAM_FLAGS[(int(n_mates), m)]))
+        extra = tags_from_comment(head, tags)[0] if tags else b""
+        out.append(_ubam_record(name, seq, qual, UBAM_FLAGS[(int(n_mates), m)], extra))
     return b"".join(out)
 
 

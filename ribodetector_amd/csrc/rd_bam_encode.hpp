@@ -1,6 +1,7 @@
 // rd_bam_encode.hpp - the records of a FASTQ / FASTA chunk as unaligned BAM records: the RAW view of a chunk that did not come from a
 // BAM file (rd_be_* kernels; C ABI rd_bam_encode, the CLI's --ubam_output). Part of the single translation unit rd_kernels.hip (included
-// from there, behind rd_report.hpp, whose id rule and tile writer it uses); DESIGN.md §3.28. The rule is ribodetector_amd/bam.py
+// from there, behind rd_report.hpp, whose id rule and tile writer it uses, and rd_bam_tagtext.hpp, whose lane-group copy the tag pass
+// uses); DESIGN.md §3.28. The rule is ribodetector_amd/bam.py
 // (from_fastq): record i becomes bam.encode_record({name, seq, qual, flag}) -
 //     block_size:int32 = S - 4, refID -1, pos -1, l_read_name = L + 1, mapq 0, bin 4680, n_cigar_op 0, flag, l_seq, next_refID -1,
 //     next_pos -1, tlen 0 (36 bytes), the name and its NUL (L + 1), the bases 4 bits each ((l_seq + 1) / 2), the qualities (l_seq):
@@ -32,10 +33,28 @@
 //                       Pieces that cross a field or a record go byte by byte. The counters are summed per lane, then per wave, then
 //                       in LDS: one 64-bit atomic per workgroup and counter.
 // Nothing is written on a fault (info[3]): raw_start is zeroed instead, so that it describes an empty view.
+//
+// Listed names (C ABI rd_bam_encode_ex, the CLI's --ubam_tags; the rule is bam.tags_from_comment): a record ends in the
+// listed tags that the comment of its header line holds. Without names the kernels' TAGS = false instances run - the launches above.
+//   rd_be_tag_count_kernel<L>   in FRONT of the length pass, L = 4 or 16 lanes per record: the comment's fields in order, every value
+//                               validated; per record the bytes of its tags, which the length pass adds to the record's length, and
+//                               the mask of the names copied; per copied name where its field stands and where its tag goes
+//   rd_be_len_kernel<true>, the scan (without a limit: BeTagVerdict holds the total against raw_cap and REPORTS it, fault 1),
+//   rd_be_write_kernel<true>    as above; the tile writer writes the tag bytes as zeros
+//   rd_be_tag_write_kernel<L>   behind the tile writer: the tags straight into raw at each record's tag offset, by lane groups
+// The bound. A field of t text bytes 'XY:T:value' makes: A 4 of 6; i 3 + 1, 2 or 4 of 5 + digits (a value that needs 4 bytes has 5
+// digits); Z / H 3 + (t - 5) + 1 = t - 1; B 8 + es count of t = 6 + the elements' text, each at least ',d' = 2 bytes for es <= 4: at most
+// 8 + 2 (t - 6) = 2 t - 4, reached by an I / i array of one-digit values (and by an array without elements: 8 of 6). So a field makes at
+// most max(t, 2 t - 4) < 2 t bytes, a record's tags at most twice its comment, and - the comment and the byte in front of it are
+// part of the text that the bounds above count as header -           raw <= bound above + sum of max(0, tags - comment - 1).
+// Real comments shrink (an ML:B:C,255 element is 4 text bytes for 1), so a caller sizes `raw` by the bound above and repeats the
+// call once, at the size info[1] reports, in the rare case of fault 1.
 #pragma once
 #include "rd_common.hpp"
 #include "rd_scan.hpp"
 #include "rd_report.hpp"
+#include "rd_bam_tags.hpp"
+#include "rd_bam_tagtext.hpp"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "rd_bam_encode.hpp is written for gfx950 (wave64, 16-byte global stores)"
@@ -102,10 +121,12 @@ __device__ __forceinline__ uint32_t be_flag(uint32_t flags, int64_t i) {      //
     return i & 1 ? (flags >> RD_UBAM_ODD_SHIFT) & 0xfffu : (flags >> RD_UBAM_EVEN_SHIFT) & 0xfffu;
 }
 
+// TAGS (rd_bam_encode_ex with listed names): tagb[i], the bytes of record i's tags (rd_be_tag_count_kernel ran first), are part of its length
+template <bool TAGS>
 __global__ __launch_bounds__(256) void rd_be_len_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, BeTabs t, int64_t n, uint32_t flags,
                                                        int64_t *__restrict__ rec_len, uint32_t *__restrict__ meta, int64_t *__restrict__ qoff,
                                                        int64_t *__restrict__ bsum, unsigned long long *__restrict__ first_bad, int32_t *__restrict__ fault,
-                                                       unsigned long long *__restrict__ starred) {
+                                                       unsigned long long *__restrict__ starred, const int64_t *__restrict__ tagb) {
     __shared__ int64_t sh[4];
     __shared__ unsigned int s_star;
     if (threadIdx.x == 0) s_star = 0;
@@ -153,7 +174,8 @@ __global__ __launch_bounds__(256) void rd_be_len_kernel(const uint8_t *__restric
             m |= (uint32_t)idl;
         }
         bad_any |= bad;
-        const int64_t len = bad ? BE_MIN_REC : 36 + idl + 1 + (ls + 1) / 2 + ls;
+        int64_t len = bad ? BE_MIN_REC : 36 + idl + 1 + (ls + 1) / 2 + ls;
+        if constexpr (TAGS) len += bad ? 0 : tagb[i];
         rec_len[i] = len;
         meta[i] = bad ? (BE_STAR | BE_NOSEQ | 1u) : m;
         qoff[i] = q0;
@@ -196,11 +218,16 @@ __device__ __forceinline__ uint32_t be_fixed_byte(int64_t size, const BeRec &r, 
     return (v >> (8 * (j & 3))) & 0xffu;
 }
 
+// TAGS: a record ends in tagb[i] bytes of tags, which this pass writes as zeros (whole pieces of them as one store) and
+// rd_be_tag_write_kernel, behind it on the stream, fills in
+template <bool TAGS>
 __global__ __launch_bounds__(256) void rd_be_write_kernel(const uint8_t *__restrict__ text, BeTabs t, int64_t n, uint32_t flags,
                                                          const uint32_t *__restrict__ meta, const int64_t *__restrict__ qoff,
-                                                         int64_t *__restrict__ raw_start, uint8_t *__restrict__ raw, int64_t *__restrict__ info) {
+                                                         int64_t *__restrict__ raw_start, uint8_t *__restrict__ raw, int64_t *__restrict__ info,
+                                                         const int64_t *__restrict__ tagb) {
     __shared__ int64_t offs[BE_RECS + 1];
     __shared__ BeRec recs[BE_RECS];
+    __shared__ int64_t tg[TAGS ? BE_RECS : 1];
     __shared__ uint8_t code[256];
     __shared__ int64_t r_bounds[2];
     __shared__ unsigned int s_cnt[2];
@@ -245,6 +272,7 @@ __global__ __launch_bounds__(256) void rd_be_write_kernel(const uint8_t *__restr
             r.l_seq = m & BE_NOSEQ ? 0 : t.seq_len[e];
             r.flag = be_flag(flags, i) | (m & BE_STAR);
             recs[k] = r;
+            if constexpr (TAGS) tg[k] = tagb[i];
         }
         __syncthreads();
         const int64_t skip0 = lo - start0;       // bytes of record r0 in front of the tile
@@ -259,7 +287,8 @@ __global__ __launch_bounds__(256) void rd_be_write_kernel(const uint8_t *__restr
             [&](int k, int64_t j) -> uint32_t {
                 if (k == 0) j += skip0;
                 const BeRec &r = recs[k];
-                const int64_t size = 36 + r.name + 1 + ((int64_t)r.l_seq + 1) / 2 + r.l_seq;
+                int64_t size = 36 + r.name + 1 + ((int64_t)r.l_seq + 1) / 2 + r.l_seq;
+                if constexpr (TAGS) size += tg[k];
                 if (j < 36) return be_fixed_byte(size, r, (int)j);
                 j -= 36;
                 if (j < r.name) return r.flag & BE_STAR ? (uint32_t)'*' : text[r.id_src + j];
@@ -273,6 +302,8 @@ __global__ __launch_bounds__(256) void rd_be_write_kernel(const uint8_t *__restr
                     return ((c0 & 15u) << 4) | (c1 & 15u);
                 }
                 j -= half;
+                if constexpr (TAGS)
+                    if (j >= r.l_seq) return 0u;
                 if (fasta) return 0xffu;
                 return be_qual4(text[r.q_src + j] | 0x21212100u, clamped);
             },
@@ -301,6 +332,8 @@ __global__ __launch_bounds__(256) void rd_be_write_kernel(const uint8_t *__restr
                     return true;
                 }
                 j -= half;
+                if constexpr (TAGS)
+                    if (j >= r.l_seq) return j + 16 <= r.l_seq + tg[k];      // (v is zero) 16 bytes of the record's tags
                 if (j + 16 > r.l_seq) return false;
                 if (fasta) {
                     v = u32x4{0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
@@ -328,4 +361,406 @@ __global__ __launch_bounds__(256) void rd_be_write_kernel(const uint8_t *__restr
     if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd((unsigned long long *)&info[4 + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
 }
 
+// ---- the tags of the header line's comment (rd_bam_encode_ex with listed names; the rule is bam.tags_from_comment) ------------------------
+constexpr int BT_THREADS = 256;
+constexpr int BT_CNT = 2 + RD_BAM_TAGS_MAX;      // counters: malformed records, float values skipped, records per copied name
+
+__device__ __forceinline__ int bt_first_ws(u32x4 v) {      // index of the first byte of v that ends an id (rp_ws), 16: none
+    int j = 16;
+#pragma unroll
+    for (int w = 3; w >= 0; --w)
+#pragma unroll
+        for (int c = 3; c >= 0; --c)
+            if (rp_ws((v[w] >> (8 * c)) & 0xffu)) j = 4 * w + c;
+    return j;
+}
+
+__device__ __forceinline__ int bt_first_eq(u32x4 v, uint32_t c) {      // index of the first byte of v equal to c, 16: none
+    const uint32_t m = c * 0x01010101u;
+    return tg_first_zero(u32x4{v[0] ^ m, v[1] ^ m, v[2] ^ m, v[3] ^ m});
+}
+
+// The first byte of text[p, e) that is c - WS: that ends an id -, e when there is none: lane j of a group looks at bytes [16 j, 16 j + 16)
+// of a step of 16 L bytes, a ballot finds the first. Called by EVERY lane of the wave (the ballots and the shuffle are executed by all
+// 64); on, p and e are the same in the lanes of a group, and a group with on == false idles and gets e. No byte at or behind e is read.
+template <int L, bool WS>
+__device__ __forceinline__ int64_t bt_find(const uint8_t *__restrict__ text, int64_t p, int64_t e, bool on, int sub, int gbase, unsigned long long gmask,
+                                           uint32_t c) {
+    int64_t at = e;
+    bool searching = on && p < e;
+    for (;;) {
+        if (!__ballot(searching)) break;
+        int z = 16;
+        if (searching) {
+            const int64_t q0 = p + 16 * sub;
+            if (q0 + 16 <= e) {
+                u32x4 w;
+                __builtin_memcpy(&w, text + q0, 16);
+                z = WS ? bt_first_ws(w) : bt_first_eq(w, c);
+            } else {
+                for (int64_t q = q0; q < e; ++q)
+                    if (WS ? rp_ws(text[q]) : text[q] == c) { z = (int)(q - q0); break; }
+            }
+        }
+        const unsigned long long found = __ballot(z < 16) & gmask;
+        const int first = found ? __ffsll((long long)found) - 1 : gbase;
+        const int zf = __shfl(z, first);
+        if (searching) {
+            if (found) {
+                at = p + 16 * (int64_t)(first - gbase) + zf;
+                searching = false;
+            } else {
+                p += 16 * L;
+                if (p >= e) searching = false;
+            }
+        }
+    }
+    return at;
+}
+
+// [+-]?[0-9]{1,10} at text[p, e): its value and where it ends; false: no digit, or an eleventh one
+__device__ __forceinline__ bool bt_int(const uint8_t *__restrict__ text, int64_t p, int64_t e, int64_t &v, int64_t &end) {
+    bool neg = false;
+    if (p < e && (text[p] == '+' || text[p] == '-')) { neg = text[p] == '-'; ++p; }
+    int64_t m = 0;
+    int d = 0;
+    for (; p < e && d < 11; ++p, ++d) {
+        const uint32_t c = text[p];
+        if (c < '0' || c > '9') break;
+        m = m * 10 + (int64_t)(c - '0');
+    }
+    v = neg ? -m : m;
+    end = p;
+    return d >= 1 && d <= 10;
+}
+
+__device__ __forceinline__ bool bt_in_range(int64_t v, uint8_t t) {      // may v stand in an element of type t (one of cCsSiI)?
+    const int64_t lo = t == 'c' ? -128 : t == 's' ? -32768 : t == 'i' ? -2147483648LL : 0;
+    const int64_t hi = t == 'c' ? 127 : t == 'C' ? 255 : t == 's' ? 32767 : t == 'S' ? 65535 : t == 'i' ? 2147483647LL : 4294967295LL;
+    return v >= lo && v <= hi;
+}
+
+__device__ __forceinline__ uint8_t bt_small_type(int64_t v) {          // the smallest type that holds v in [-2^31, 2^32)
+    if (v >= 0) return v <= 255 ? 'C' : v <= 65535 ? 'S' : 'I';
+    return v >= -128 ? 'c' : v >= -32768 ? 's' : 'i';
+}
+
+// the element behind the comma at text[q] of a B value that ends at fe: its value when it is [+-]?digits up to the next comma or fe
+// and lies in the range of subtype st
+__device__ __forceinline__ bool bt_element(const uint8_t *__restrict__ text, int64_t q, int64_t fe, uint8_t st, int64_t &v) {
+    int64_t end;
+    if (!bt_int(text, q + 1, fe, v, end)) return false;
+    if (end < fe && text[end] != ',') return false;
+    return bt_in_range(v, st);
+}
+
+// 16 bytes of a B value at text[i] (fewer at its end fe): a bit per byte that is a comma
+__device__ __forceinline__ uint32_t bt_commas(const uint8_t *__restrict__ text, int64_t i, int64_t fe) {
+    uint32_t m = 0;
+    if (i + 16 <= fe) {
+        u32x4 w;
+        __builtin_memcpy(&w, text + i, 16);
+#pragma unroll
+        for (int c = 0; c < 16; ++c)
+            if (((w[c >> 2] >> (8 * (c & 3))) & 0xffu) == ',') m |= 1u << c;
+    } else {
+        for (int64_t q = i; q < fe; ++q)
+            if (text[q] == ',') m |= 1u << (int)(q - i);
+    }
+    return m;
+}
+
+// The count pass: L lanes per record. The header line's end (the first '\n' inside the record; none: the table fault), the id's end, the
+// comment behind that one byte up to the line's end (without one '\r' in front of the '\n'); then the fields of the comment in order,
+// a step of the loop per field and group: its end (the next '\t'), the five bytes 'XY:T:' and the listed name they hold, the value -
+// the lanes stride over the bytes of a Z / H value and over 16-byte pieces of a B value, in which each lane parses the elements whose
+// comma stands in its piece. The sums meet in shuffles behind the strided loops. Per record: the bytes of its tags (tagb) and the mask
+// of the names that are copied (0 for a malformed record); per copied name: where the field stands in the text (foff, fend) and where
+// its tag goes in the record's tag bytes (ooff) - comment order. Every offset is compared with the record's end before it is read.
+template <int L>
+__global__ __launch_bounds__(BT_THREADS) void rd_be_tag_count_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, BeTabs t, int64_t n, int n_names,
+                                                                    TtNames names, int64_t *__restrict__ tagb, uint32_t *__restrict__ mask,
+                                                                    int64_t *__restrict__ foff, int64_t *__restrict__ fend, int64_t *__restrict__ ooff,
+                                                                    unsigned long long *__restrict__ cnt, int32_t *__restrict__ fault) {
+    __shared__ unsigned int scnt[BT_CNT];
+    if (threadIdx.x < BT_CNT) scnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int sub = lane & (L - 1), gbase = lane & ~(L - 1);
+    const unsigned long long gmask = ((1ull << L) - 1ull) << gbase;
+    const int64_t k = ((int64_t)blockIdx.x * BT_THREADS + threadIdx.x) / L;
+    const bool live = k < n;
+    int64_t a = 0, b = 0;
+    bool ok = false;                                      // a record with a header line (the length pass judges every other one)
+    if (live) {
+        const int64_t e = t.at(k);
+        a = t.rec_start[e], b = t.rec_start[e + 1];
+        ok = a >= 0 && a < b && b <= text_bytes;
+        if (ok) ok = text[a] == '@' || text[a] == '>';
+    }
+    const int64_t nl = bt_find<L, false>(text, a + 1, b, ok, sub, gbase, gmask, '\n');
+    if (ok && nl >= b) {                                  // a header line that runs past its record
+        if (sub == 0) atomicOr(fault, 1);
+        ok = false;
+    }
+    const int64_t ws = bt_find<L, true>(text, a + 1, nl, ok, sub, gbase, gmask, 0);
+    int64_t ce = nl;                                      // the line's end
+    if (ok && nl - 1 > a && text[nl - 1] == '\r') ce = nl - 1;
+    int64_t p = ws + 1;                                   // the field that the next step takes starts here
+    bool more = ok && ws < ce;
+    bool mal = false;
+    uint32_t seen = 0, copied = 0;
+    int floats = 0;
+    int64_t tags = 0;
+    for (;;) {
+        if (!__ballot(more)) break;                       // (wave-uniform: the ballots and shuffles below are executed by every lane)
+        const int64_t fe = bt_find<L, false>(text, p, ce, more, sub, gbase, gmask, '\t');
+        int j = -1;
+        uint8_t ty = 0;
+        if (more && fe - p >= 5) {
+            const uint32_t c0 = text[p], c1 = text[p + 1], c3 = text[p + 3];
+            const bool alpha0 = (c0 >= 'A' && c0 <= 'Z') || (c0 >= 'a' && c0 <= 'z');
+            const bool alnum1 = (c1 >= 'A' && c1 <= 'Z') || (c1 >= 'a' && c1 <= 'z') || (c1 >= '0' && c1 <= '9');
+            const bool type3 = c3 == 'A' || c3 == 'i' || c3 == 'Z' || c3 == 'H' || c3 == 'B' || c3 == 'f';
+            if (alpha0 && alnum1 && type3 && text[p + 2] == ':' && text[p + 4] == ':') {
+                for (int q = 0; q < n_names; ++q)
+                    if (names.b[2 * q] == c0 && names.b[2 * q + 1] == c1) j = q;
+                if (j >= 0 && ((seen >> j) & 1u)) j = -1;             // (only the first field of a name counts)
+                ty = (uint8_t)c3;
+            }
+        }
+        int64_t tb = 0;                                   // this lane's share of the tag's bytes
+        int lbad = 0;
+        bool is_float = false;
+        if (j >= 0) {
+            const int64_t v0 = p + 5, vl = fe - v0;
+            if (ty == 'A') {
+                if (vl != 1 || text[v0] < 0x21u || text[v0] > 0x7eu) lbad = 1;
+                if (sub == 0) tb = 4;
+            } else if (ty == 'i') {
+                if (sub == 0) {
+                    int64_t v, end;
+                    if (!bt_int(text, v0, fe, v, end) || end != fe || v < -2147483648LL || v > 4294967295LL) lbad = 1;
+                    else tb = 3 + tg_elem_size(bt_small_type(v));
+                }
+            } else if (ty == 'Z' || ty == 'H') {
+                const bool hex = ty == 'H';
+                if (hex && (vl & 1)) lbad = 1;
+                if (sub == 0) tb = 4 + vl;
+                for (int64_t i = 16 * (int64_t)sub; i < vl; i += 16 * L) {
+                    if (i + 16 <= vl) {
+                        u32x4 w;
+                        __builtin_memcpy(&w, text + v0 + i, 16);
+#pragma unroll
+                        for (int c = 0; c < 16; ++c)
+                            if (!tt_text_byte((w[c >> 2] >> (8 * (c & 3))) & 0xffu, hex)) lbad = 1;
+                    } else {
+                        for (int64_t q = i; q < vl; ++q)
+                            if (!tt_text_byte(text[v0 + q], hex)) lbad = 1;
+                    }
+                }
+            } else if (ty == 'f') {
+                is_float = true;
+            } else {                                      // B: a subtype, then ',int' per element
+                const uint8_t st = vl >= 1 ? text[v0] : 0;
+                if (st == 'f') is_float = true;
+                else if (!tt_is_int(st) || (vl > 1 && text[v0 + 1] != ',')) lbad = 1;
+                else {
+                    const int es = tg_elem_size(st);
+                    if (sub == 0) tb = 8;
+                    for (int64_t i = v0 + 1 + 16 * (int64_t)sub; i < fe; i += 16 * L) {
+                        uint32_t m = bt_commas(text, i, fe);
+                        while (m) {
+                            const int c = __ffs((int)m) - 1;
+                            m &= m - 1;
+                            int64_t v;
+                            if (bt_element(text, i + c, fe, st, v)) tb += es;
+                            else lbad = 1;
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int o = L / 2; o >= 1; o >>= 1) {
+            tb += __shfl_xor(tb, o);
+            lbad |= __shfl_xor(lbad, o);
+        }
+        if (j >= 0) {
+            seen |= 1u << j;
+            if (lbad) mal = true;
+            else if (is_float) ++floats;
+            else {
+                if (sub == 0) {
+                    const int64_t at = (int64_t)j * n + k;
+                    foff[at] = p;
+                    fend[at] = fe;
+                    ooff[at] = tags;
+                }
+                copied |= 1u << j;
+                tags += tb;
+            }
+        }
+        if (more) {
+            if (fe < ce) p = fe + 1;
+            else more = false;
+        }
+    }
+    if (mal) { tags = 0; copied = 0; floats = 0; }
+    if (live && sub == 0) {
+        tagb[k] = tags;
+        mask[k] = copied;
+        if (mal) atomicAdd(&scnt[0], 1u);
+        if (floats) atomicAdd(&scnt[1], (unsigned int)floats);
+    }
+    for (int j = 0; j < n_names; ++j) {                   // (uniform) one LDS add per wave and name
+        const unsigned long long m = __ballot(sub == 0 && ((copied >> j) & 1u));
+        if (lane == 0 && m) atomicAdd(&scnt[2 + j], (unsigned int)__popcll(m));
+    }
+    __syncthreads();
+    if (threadIdx.x < BT_CNT && scnt[threadIdx.x]) atomicAdd(&cnt[threadIdx.x], (unsigned long long)scnt[threadIdx.x]);
+}
+
+// the verdict of a call with listed names: BeVerdict's words, with the bytes the records NEED in info[1] when they are more than raw_cap
+// (fault 1), and behind them info[8] = records with malformed tags, [9] = float values skipped, [10 + j] = records in which name j was
+// copied. tot: the int64[4] of rd_scan_base_kernel, which ran without a limit
+struct BeTagVerdict {
+    int64_t n;
+    const int32_t *fault;
+    const unsigned long long *first_bad, *starred, *cnt;
+    const int64_t *tot;
+    int64_t raw_cap;
+    int n_names;
+    int64_t *info;
+    __device__ __forceinline__ void operator()() const {
+        const int64_t bytes = tot[1];
+        const int f = *fault != 0 ? 2 : (tot[3] != 0 || bytes > raw_cap) ? 1 : 0;
+        info[0] = f ? 0 : n;
+        info[1] = f == 2 ? 0 : bytes;
+        info[2] = (int64_t)first_bad[0];
+        info[3] = f;
+        info[6] = (int64_t)*starred;
+        info[7] = (int64_t)first_bad[1];
+        for (int j = 0; j < 2 + n_names; ++j) info[8 + j] = f == 2 ? 0 : (int64_t)cnt[j];
+    }
+};
+
+// The tag pass, behind the tile writer on the stream: L lanes per record write its tags straight into raw, behind the qualities - the
+// bytes the tile writer left zero. The names in list order, each at its own offset (ooff). The three bytes 'XY' type and a scalar by
+// the group's first lane; a Z / H value as tt_copy copies (aligned 16-byte pieces of the OUTPUT range, the ends bytewise); the elements
+// of a B array: a step takes 16 L bytes of the text, a lane counts the commas of its 16, a prefix sum of the counts over the group and a
+// running base say which element stands behind a lane's first comma, and the lane parses and stores its elements. That loop is stepped
+// by the whole wave (a ballot ends it), so the shuffles are executed by all 64 lanes. Nothing on a fault.
+template <int L>
+__global__ __launch_bounds__(BT_THREADS) void rd_be_tag_write_kernel(const uint8_t *__restrict__ text, int64_t n, int n_names, TtNames names,
+                                                                    const int64_t *__restrict__ tagb, const uint32_t *__restrict__ mask,
+                                                                    const int64_t *__restrict__ foff, const int64_t *__restrict__ fend,
+                                                                    const int64_t *__restrict__ ooff, const int64_t *__restrict__ raw_start,
+                                                                    uint8_t *__restrict__ raw, const int64_t *__restrict__ info) {
+    if (info[3]) return;                                  // (every lane of the grid)
+    const int lane = threadIdx.x & 63;
+    const int sub = lane & (L - 1), gbase = lane & ~(L - 1);
+    const int64_t k = ((int64_t)blockIdx.x * BT_THREADS + threadIdx.x) / L;
+    const bool live = k < n;
+    const uint32_t m = live ? mask[k] : 0u;
+    const int64_t base = live ? raw_start[k + 1] - tagb[k] : 0;      // where the record's tags begin
+    for (int j = 0; j < n_names; ++j) {                   // (uniform)
+        const bool on = (m >> j) & 1u;
+        int64_t o = 0, fe = 0, i0 = 0, run = 0;
+        uint8_t st = 'C';
+        bool array = false;
+        if (on) {
+            const int64_t at = (int64_t)j * n + k;
+            const int64_t p = foff[at], v0 = p + 5;
+            fe = fend[at];
+            o = base + ooff[at];
+            const uint8_t ty = text[p + 3];
+            if (sub == 0) {
+                raw[o] = names.b[2 * j];
+                raw[o + 1] = names.b[2 * j + 1];
+                raw[o + 2] = ty;
+                if (ty == 'A') raw[o + 3] = text[v0];
+                else if (ty == 'i') {
+                    int64_t v, end;
+                    bt_int(text, v0, fe, v, end);
+                    const uint8_t small = bt_small_type(v);
+                    raw[o + 2] = small;
+                    for (int c = 0; c < tg_elem_size(small); ++c) raw[o + 3 + c] = (uint8_t)((uint64_t)v >> (8 * c));
+                } else if (ty == 'B') {
+                    raw[o + 3] = text[v0];
+                } else {
+                    raw[o + 3 + (fe - v0)] = 0;           // Z / H: the NUL
+                }
+            }
+            if (ty == 'Z' || ty == 'H') tt_copy<L>(raw, o + 3, text + v0, fe - v0, sub);
+            else if (ty == 'B') {
+                array = true;
+                st = text[v0];
+                i0 = v0 + 1;
+            }
+        }
+        const int es = tg_elem_size(st);
+        for (;; i0 += 16 * L) {
+            if (!__ballot(array && i0 < fe)) break;       // (wave-uniform)
+            const int64_t i = i0 + 16 * (int64_t)sub;
+            uint32_t cm = array && i < fe ? bt_commas(text, i, fe) : 0u;
+            const int mine = __popc(cm);
+            int inc = mine;
+#pragma unroll
+            for (int d = 1; d < L; d <<= 1) {
+                const int up = __shfl_up(inc, d, L);
+                if (sub >= d) inc += up;
+            }
+            const int total = __shfl(inc, gbase + L - 1);
+            int64_t idx = run + (inc - mine);
+            while (cm) {
+                const int c = __ffs((int)cm) - 1;
+                cm &= cm - 1;
+                int64_t v;
+                bt_element(text, i + c, fe, st, v);       // (valid: the count pass has parsed it)
+                uint8_t *__restrict__ q = raw + o + 8 + idx * es;
+                for (int w = 0; w < es; ++w) q[w] = (uint8_t)((uint64_t)v >> (8 * w));
+                ++idx;
+            }
+            run += total;
+        }
+        if (array && sub == 0) {
+            for (int c = 0; c < 4; ++c) raw[o + 4 + c] = (uint8_t)((uint64_t)run >> (8 * c));
+        }
+    }
+}
+
+
+// the tables of a call in its workspace (carved by bam_encode_ws of rd_kernels.hip)
+struct BamEncodeWs {
+    int nb;
+    uint32_t *meta;
+    int64_t *qoff, *bsum;
+    unsigned long long *first_bad, *starred;     // (first_bad[2], starred and fault lie behind one another: one memset each way)
+    int32_t *fault;
+    // listed names (rd_bam_encode_ex): the tables of the tag passes, behind the ones every call has
+    int64_t *tagb, *foff, *fend, *ooff, *tot;
+    uint32_t *mask;
+    unsigned long long *cnt;
+    size_t total;
+};
+
+// the launches of a call with listed names, for one lane mapping of the tag passes
+template <int L>
+void bam_encode_tags_launch(const uint8_t *text, int64_t text_bytes, const BeTabs &t, int64_t n_rec, uint32_t flags, const TtNames &names, int32_t n_names,
+                            uint8_t *raw, int64_t cap, int64_t *raw_start, int64_t *info, const BamEncodeWs &p, unsigned grid, hipStream_t st) {
+    const int64_t per = BT_THREADS / L;
+    const dim3 tgrid((unsigned)((n_rec + per - 1) / per));
+    hipLaunchKernelGGL((rd_be_tag_count_kernel<L>), tgrid, dim3(BT_THREADS), 0, st, text, text_bytes, t, n_rec, (int)n_names, names, p.tagb, p.mask, p.foff, p.fend,
+                       p.ooff, p.cnt, p.fault);
+    hipLaunchKernelGGL(rd_be_len_kernel<true>, dim3(p.nb), dim3(256), 0, st, text, text_bytes, t, n_rec, flags, raw_start, p.meta, p.qoff, p.bsum, p.first_bad, p.fault,
+                       p.starred, (const int64_t *)p.tagb);
+    scan_base(p.bsum, p.nb, p.tot, INT64_MAX, st);
+    hipLaunchKernelGGL((rd_scan_off_kernel<8, 1, ScanTab<1>, BeTagVerdict>), dim3(p.nb), dim3(256), 0, st, ScanTab<1>{{raw_start}}, n_rec,
+                       ScanOut<1>{{raw_start}, {p.bsum}}, BeTagVerdict{n_rec, p.fault, p.first_bad, p.starred, p.cnt, p.tot, cap, (int)n_names, info});
+    hipLaunchKernelGGL(rd_be_write_kernel<true>, dim3(grid), dim3(256), 0, st, text, t, n_rec, flags, (const uint32_t *)p.meta, (const int64_t *)p.qoff, raw_start, raw,
+                       info, (const int64_t *)p.tagb);
+    hipLaunchKernelGGL((rd_be_tag_write_kernel<L>), tgrid, dim3(BT_THREADS), 0, st, text, n_rec, (int)n_names, names, (const int64_t *)p.tagb, (const uint32_t *)p.mask,
+                       (const int64_t *)p.foff, (const int64_t *)p.fend, (const int64_t *)p.ooff, (const int64_t *)raw_start, raw, (const int64_t *)info);
+}
 }  // namespace

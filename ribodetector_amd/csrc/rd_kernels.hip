@@ -56,11 +56,11 @@
 #include "rd_bam_shard.hpp"
 #include "rd_bam_raw.hpp"
 #include "rd_report.hpp"
-#include "rd_bam_encode.hpp"
 #include "rd_pairs.hpp"
 #include "rd_summary.hpp"
 #include "rd_bam_tags.hpp"
 #include "rd_bam_tagtext.hpp"
+#include "rd_bam_encode.hpp"
 #include "rd_windows.hpp"
 #include "rd_regions.hpp"
 #include "rd_group_pack.hpp"
@@ -1470,15 +1470,7 @@ int rd_bam_tag_splice_ex(const uint8_t *text, int64_t text_bytes, const int64_t 
 
 // the records of a FASTQ / FASTA chunk as unaligned BAM records (rd_bam_encode.hpp): lengths, their scan, the write pass by output tiles
 namespace {
-struct BamEncodeWs {
-    int nb;
-    uint32_t *meta;
-    int64_t *qoff, *bsum;
-    unsigned long long *first_bad, *starred;     // (first_bad[2], starred and fault lie behind one another: one memset each way)
-    int32_t *fault;
-    size_t total;
-};
-BamEncodeWs bam_encode_ws(void *workspace, int64_t n) {
+BamEncodeWs bam_encode_ws(void *workspace, int64_t n, int32_t n_names = 0) {
     BamEncodeWs p;
     Carver c(workspace);
     p.nb = scan_blocks(n);
@@ -1488,9 +1480,23 @@ BamEncodeWs bam_encode_ws(void *workspace, int64_t n) {
     p.first_bad = c.take<unsigned long long>(2);
     p.starred = c.take<unsigned long long>(1);
     p.fault = c.take<int32_t>(1);
+    p.tagb = p.foff = p.fend = p.ooff = p.tot = nullptr;
+    p.mask = nullptr;
+    p.cnt = nullptr;
+    if (n_names > 0) {
+        const size_t cells = (size_t)n * (size_t)n_names;
+        p.tagb = c.take<int64_t>((size_t)n);
+        p.foff = c.take<int64_t>(cells);
+        p.fend = c.take<int64_t>(cells);
+        p.ooff = c.take<int64_t>(cells);
+        p.tot = c.take<int64_t>(4);
+        p.mask = c.take<uint32_t>((size_t)n);
+        p.cnt = c.take<unsigned long long>(BT_CNT);
+    }
     p.total = c.off;
     return p;
 }
+
 }  // namespace
 
 size_t rd_bam_encode_workspace_bytes(int64_t n_rec) {
@@ -1498,43 +1504,80 @@ size_t rd_bam_encode_workspace_bytes(int64_t n_rec) {
     return bam_encode_ws(nullptr, n_rec).total;
 }
 
+size_t rd_bam_encode_tags_workspace_bytes(int64_t n_rec, int32_t n_names) {
+    if (n_rec < 0 || n_rec > 0x3fffffffLL || n_names < 0 || n_names > RD_BAM_TAGS_MAX) return 0;
+    return bam_encode_ws(nullptr, n_rec, n_names).total;
+}
+
 int rd_bam_encode(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int64_t *seq_off, const int32_t *seq_len, int64_t n_rec, int64_t rec_first,
                   int32_t rec_stride, uint32_t flags, uint8_t *raw, size_t raw_cap, int64_t *raw_start, int64_t *info, void *workspace, size_t workspace_bytes,
                   void *stream) {
+    return rd_bam_encode_ex(text, text_bytes, rec_start, seq_off, seq_len, n_rec, rec_first, rec_stride, flags, nullptr, 0, raw, raw_cap, raw_start, info, workspace,
+                            workspace_bytes, stream);
+}
+
+// n_names == 0: the launches of rd_bam_encode (the kernels' TAGS = false instances). Else the tag count pass in front of the length pass
+// (whose lengths include the tags' bytes), the scan without a limit - the verdict holds the total against raw_cap and reports it -, the
+// tile writer and the tag pass behind it
+int rd_bam_encode_ex(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int64_t *seq_off, const int32_t *seq_len, int64_t n_rec, int64_t rec_first,
+                     int32_t rec_stride, uint32_t flags, const uint8_t *names, int32_t n_names, uint8_t *raw, size_t raw_cap, int64_t *raw_start, int64_t *info,
+                     void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = n_names ? "rd_bam_encode_ex" : "rd_bam_encode";
     const uint32_t known = RD_UBAM_FASTA | (0xfffu << RD_UBAM_EVEN_SHIFT) | (0xfffu << RD_UBAM_ODD_SHIFT);
-    if (flags & ~known) RD_FAIL(RD_E_INVALID, "rd_bam_encode: unknown flag bits 0x%x", flags & ~known);
-    if (n_rec < 0 || n_rec > 0x3fffffffLL || text_bytes < 0) RD_FAIL(RD_E_INVALID, "rd_bam_encode: bad n_rec or text_bytes");
-    if (rec_first < 0 || rec_stride < 1 || rec_first > 0x3fffffffLL) RD_FAIL(RD_E_INVALID, "rd_bam_encode: bad rec_first or rec_stride");
-    if (!info || !raw_start) RD_FAIL(RD_E_INVALID, "rd_bam_encode: null info or raw_start");
+    if (flags & ~known) RD_FAIL(RD_E_INVALID, "%s: unknown flag bits 0x%x", fn, flags & ~known);
+    if (n_rec < 0 || n_rec > 0x3fffffffLL || text_bytes < 0) RD_FAIL(RD_E_INVALID, "%s: bad n_rec or text_bytes", fn);
+    if (rec_first < 0 || rec_stride < 1 || rec_first > 0x3fffffffLL) RD_FAIL(RD_E_INVALID, "%s: bad rec_first or rec_stride", fn);
+    if (n_names < 0 || n_names > RD_BAM_TAGS_MAX) RD_FAIL(RD_E_INVALID, "rd_bam_encode_ex: n_names=%d out of range [0,%d]", n_names, RD_BAM_TAGS_MAX);
+    if (n_names && !names) RD_FAIL(RD_E_INVALID, "rd_bam_encode_ex: null names");
+    TtNames nm;
+    memset(&nm, 0, sizeof(nm));
+    for (int j = 0; j < n_names; ++j) {
+        if (!tag_name_ok(names + 2 * j)) RD_FAIL(RD_E_INVALID, "rd_bam_encode_ex: name %d is not a tag name ([A-Za-z][A-Za-z0-9])", j);
+        for (int i = 0; i < j; ++i)
+            if (names[2 * i] == names[2 * j] && names[2 * i + 1] == names[2 * j + 1]) RD_FAIL(RD_E_INVALID, "rd_bam_encode_ex: name %d appears twice", j);
+        nm.b[2 * j] = names[2 * j];
+        nm.b[2 * j + 1] = names[2 * j + 1];
+    }
+    if (!info || !raw_start) RD_FAIL(RD_E_INVALID, "%s: null info or raw_start", fn);
     hipStream_t st = (hipStream_t)stream;
-    RD_HIP(hipMemsetAsync(info, 0, 8 * sizeof(int64_t), st));
+    RD_HIP(hipMemsetAsync(info, 0, (size_t)(n_names ? 10 + n_names : 8) * sizeof(int64_t), st));
     if (n_rec == 0) {
         RD_HIP(hipMemsetAsync(info + 2, 0xff, sizeof(int64_t), st));
         RD_HIP(hipMemsetAsync(info + 7, 0xff, sizeof(int64_t), st));
         RD_HIP(hipMemsetAsync(raw_start, 0, sizeof(int64_t), st));
         return RD_OK;
     }
-    if ((!text && text_bytes > 0) || !rec_start || !seq_off || !seq_len || !raw || !workspace) RD_FAIL(RD_E_INVALID, "rd_bam_encode: null pointer");
-    if (((uintptr_t)workspace & 255) || ((uintptr_t)raw & 15)) RD_FAIL(RD_E_INVALID, "rd_bam_encode: workspace must be 256-byte aligned, raw 16-byte aligned");
-    const BamEncodeWs p = bam_encode_ws(workspace, n_rec);
-    if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "rd_bam_encode: workspace too small: %zu < %zu", workspace_bytes, p.total);
+    if ((!text && text_bytes > 0) || !rec_start || !seq_off || !seq_len || !raw || !workspace) RD_FAIL(RD_E_INVALID, "%s: null pointer", fn);
+    if (((uintptr_t)workspace & 255) || ((uintptr_t)raw & 15)) RD_FAIL(RD_E_INVALID, "%s: workspace must be 256-byte aligned, raw 16-byte aligned", fn);
+    const BamEncodeWs p = bam_encode_ws(workspace, n_rec, n_names);
+    if (workspace_bytes < p.total) RD_FAIL(RD_E_WORKSPACE, "%s: workspace too small: %zu < %zu", fn, workspace_bytes, p.total);
     const int64_t cap = (int64_t)(raw_cap < (size_t)INT64_MAX ? raw_cap : (size_t)INT64_MAX);
     RD_HIP(hipMemsetAsync(p.first_bad, 0xff, 2 * sizeof(unsigned long long), st));
     RD_HIP(hipMemsetAsync(p.starred, 0, (size_t)((char *)p.fault - (char *)p.starred) + sizeof(int32_t), st));
     const BeTabs t = {rec_start, seq_off, seq_len, rec_first, rec_stride};
-    hipLaunchKernelGGL(rd_be_len_kernel, dim3(p.nb), dim3(256), 0, st, text, text_bytes, t, n_rec, flags, raw_start, p.meta, p.qoff, p.bsum, p.first_bad, p.fault, p.starred);
-    scan_base(p.bsum, p.nb, info, cap, st);
-    hipLaunchKernelGGL((rd_scan_off_kernel<8, 1, ScanTab<1>, BeVerdict>), dim3(p.nb), dim3(256), 0, st, ScanTab<1>{{raw_start}}, n_rec, ScanOut<1>{{raw_start}, {p.bsum}},
-                       BeVerdict{n_rec, p.fault, p.first_bad, p.starred, info});
-    // the tiles of the bound - or of raw_cap when that is less: the bytes are known on the device only, the workgroups stride over them
+    // the tiles of the bound - or of raw_cap when that is less: the bytes are known on the device only, the workgroups stride over them.
+    // (Tags take at most twice their text: rd_bam_encode.hpp.)
     const int64_t fq = text_bytes + 32 * n_rec, fa = text_bytes + (text_bytes + 1) / 2 + 40 * n_rec;
     int64_t most = flags & RD_UBAM_FASTA ? fa : fq;
+    if (n_names) most += 2 * text_bytes;
     if (most > cap) most = cap;
     int64_t grid = (most + BE_TILE - 1) / BE_TILE;
     if (grid < 1) grid = 1;
     if (grid > BE_GRID) grid = BE_GRID;
-    hipLaunchKernelGGL(rd_be_write_kernel, dim3((unsigned)grid), dim3(256), 0, st, text, t, n_rec, flags, (const uint32_t *)p.meta, (const int64_t *)p.qoff, raw_start, raw,
-                       info);
+    if (n_names) {
+        RD_HIP(hipMemsetAsync(p.cnt, 0, BT_CNT * sizeof(unsigned long long), st));
+        if (tag_lanes(text_bytes, n_rec) == 16) bam_encode_tags_launch<16>(text, text_bytes, t, n_rec, flags, nm, n_names, raw, cap, raw_start, info, p, (unsigned)grid, st);
+        else bam_encode_tags_launch<4>(text, text_bytes, t, n_rec, flags, nm, n_names, raw, cap, raw_start, info, p, (unsigned)grid, st);
+        RD_HIP(hipGetLastError());
+        return RD_OK;
+    }
+    hipLaunchKernelGGL(rd_be_len_kernel<false>, dim3(p.nb), dim3(256), 0, st, text, text_bytes, t, n_rec, flags, raw_start, p.meta, p.qoff, p.bsum, p.first_bad, p.fault,
+                       p.starred, (const int64_t *)nullptr);
+    scan_base(p.bsum, p.nb, info, cap, st);
+    hipLaunchKernelGGL((rd_scan_off_kernel<8, 1, ScanTab<1>, BeVerdict>), dim3(p.nb), dim3(256), 0, st, ScanTab<1>{{raw_start}}, n_rec, ScanOut<1>{{raw_start}, {p.bsum}},
+                       BeVerdict{n_rec, p.fault, p.first_bad, p.starred, info});
+    hipLaunchKernelGGL(rd_be_write_kernel<false>, dim3((unsigned)grid), dim3(256), 0, st, text, t, n_rec, flags, (const uint32_t *)p.meta, (const int64_t *)p.qoff,
+                       raw_start, raw, info, (const int64_t *)nullptr);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }

@@ -53,6 +53,9 @@ raw view is MADE here - rd_bam_encode (ubam.py, csrc/rd_bam_encode.hpp; bam.from
 submitted - and from there on the run is --bam_output's: the output kernels select from DeviceChunk.raw, the files start with a header
 (bam.UBAM_HEADER_TEXT, no references) and are BGZF. A record that cannot be a BAM record (a name of more than 254 bytes, a quality line
 that is not as long as its sequence) ends the run like a mate mismatch: the chunks in front of it are written, then the ValueError.
+--ubam_tags LIST (with --ubam_output): the records carry the listed tags that the comments of their header lines hold in SAM's text form
+(rd_bam_encode_ex; bam.tags_from_comment has the rule) - the inverse of --bam_tags. The host then waits for each encode's verdict on the
+copy stream: a chunk whose records need more than their buffer is encoded once more at the size the call reported.
 """
 import argparse
 import functools
@@ -325,6 +328,8 @@ class Predictor:
         self.ubam_output = bool(getattr(args, 'ubam_output', False))     # BAM outputs of FASTQ / FASTA input: the records encoded on the device
         self.bam_files = self.bam_output or self.ubam_output             # every output file is a BAM file, whichever way its records are made
         self._ubam = None                        # ... ubam.DeviceUbam, one per input file (run_with_chunks)
+        # --ubam_tags LIST: the names whose tags the records take from their header lines' comments (None: no tags)
+        self.ubam_tags = check_ubam_tags(getattr(args, 'ubam_tags', None), self.ubam_output)
         self.read_groups = bool(getattr(args, 'read_groups', False))     # --summary gains the counters per BAM read group
         self.split_groups = bool(getattr(args, 'split_groups', False))   # every output file becomes a family: a file per BAM read group
         self._split = self._split_ids = None     # ... gz.DeviceGroupSelect (run_with_chunks), the declared ids in row order (detect)
@@ -678,7 +683,8 @@ class Predictor:
     def _ubam_chunks(self, tk, chunks, on_dev):
         """--ubam_output: every input's chunk gets its raw view - its records as BAM records (ubam.DeviceUbam.encode) - on the COPY
         stream behind the chunk's `ready` event, where the tag splice runs; like it, the encode needs no labels. Nothing waits: the
-        bound of the raw bytes is linear in the text. Returns the event behind the calls; the ticket's "ubam" check reads their verdicts."""
+        bound of the raw bytes is linear in the text. Returns the event behind the calls; the ticket's "ubam" check reads their verdicts.
+        --ubam_tags: DeviceUbam.encode waits for each call's verdict there (a second call at the exact size) and hands its info over on the host."""
         if not on_dev:
             raise RuntimeError("--ubam_output: the chunk's text is not on the device")
         infos, cs = [], self._copy_stream
@@ -687,7 +693,7 @@ class Predictor:
                 cs.wait_event(c.ready)
                 raw, raw_start, info = ub.encode(c, _bammod.INTERLEAVED if self.interleaved else f, 2 if self.is_paired else 1)
                 c.raw = (raw, raw_start)
-                infos.append(_pinned(info))
+                infos.append(info if self.ubam_tags else _pinned(info))      # (--ubam_tags: the host has waited for the verdict already)
             done = torch.cuda.Event()
             done.record(cs)
         first, self._ubam_seen = self._ubam_seen, self._ubam_seen + len(chunks[0].seq_len)
@@ -1160,6 +1166,9 @@ class Predictor:
         if self._ubam is not None:                 # --ubam_output: one rank
             self._ubam_total = [u.counts for u in self._ubam]
             self.logger.info(_ubammod.log_line(self._ubam_total))
+            if self.ubam_tags:
+                self._ubam_tag_total = [u.tag_counts() for u in self._ubam]
+                self.logger.info(_ubammod.log_line_tags(self.ubam_tags, self._ubam_tag_total))
         if self.interleaved:
             fx.check_even_records(self._records_seen)
         if self._split is not None:
@@ -1233,6 +1242,8 @@ class Predictor:
             doc["split_groups"] = self._split_total
         if self._ubam is not None:
             doc["ubam_output"] = _ubammod.to_json(self._ubam_total)
+            if self.ubam_tags:
+                doc["ubam_tags"] = _ubammod.to_json_tags(self.ubam_tags, self._ubam_tag_total)
         _summod.write_json(path, doc)
         frac = doc["reads"]["rRNA_fraction"]
         self.logger.info('rRNA fraction: {} (summary: {})'.format("n/a" if frac is None else "%.6f" % frac, path))
@@ -1425,7 +1436,7 @@ class Predictor:
         # --ubam_output: the raw view of every chunk is made of its text, and the counters of what the BAM form changed, per input file
         self._ubam, self._ubam_seen = None, 0
         if self.ubam_output:
-            self._ubam = [_ubammod.DeviceUbam(self.device, fasta=fx.get_seq_format(p).startswith("fa")) for p in self.input]
+            self._ubam = [_ubammod.DeviceUbam(self.device, fasta=fx.get_seq_format(p).startswith("fa"), tags=self.ubam_tags or ()) for p in self.input]
         self._win_classified = [0, 0]
         # --regions: the lines of every chunk, formatted on the device; mate 1's writer appends the pieces (and deflates a .gz file)
         self._regions = bool(self.regions_path)
@@ -1642,15 +1653,29 @@ def check_bam(inputs, output, rrna, bam_output=False, bam_shard=False, interleav
     return True
 
 
-def check_ubam(ubam_output, inputs, output, rrna, bam_output=False, parse_wanted=None):
+def check_ubam_tags(ubam_tags, ubam_output):
+    """--ubam_tags LIST (the BAM records of --ubam_output carry the listed tags of their header lines' comments;
+    bam.tags_from_comment has the rule): only with --ubam_output, and a list that bam.parse_tag_list takes. Returns its names (2 bytes
+    each, list order), or None without the flag. Holds before anything touches a device."""
+    if ubam_tags is None:
+        return None
+    if not ubam_output:
+        raise RuntimeError("--ubam_tags says which tags of the header lines' comments the BAM records of --ubam_output carry: give "
+                           "--ubam_output with it (checked before anything touches a device)")
+    return _ubammod.parse_list(ubam_tags)
+
+
+def check_ubam(ubam_output, inputs, output, rrna, bam_output=False, parse_wanted=None, ubam_tags=None):
     """--ubam_output (FASTQ / FASTA input written as unaligned BAM; bam.from_fastq has the rule): the rules that hold before anything
     touches a device. The input is no BAM file (--bam_output writes those as they stand); not with --bam_output; every -o / -r name
     ends with .bam / .ubam (all outputs are BAM or none is); the chunks' text lives on the device, where the records are encoded - not
     RD_DEVICE_PARSE=0 or RD_INGEST=host, and no input that the device reader turns down (parse_wanted: device_reader.
-    device_parse_wanted unless given); one rank."""
-    if not ubam_output:
-        return
+    device_parse_wanted unless given); one rank. ubam_tags (--ubam_tags LIST: the records carry the listed tags of their header lines'
+    comments, bam.tags_from_comment): only with --ubam_output, and a list that bam.parse_tag_list takes; returns its names, else None."""
     tail = " (checked before anything touches a device)"
+    names = check_ubam_tags(ubam_tags, ubam_output)
+    if not ubam_output:
+        return None
 
     def fmt(path):
         try:
@@ -1677,6 +1702,7 @@ def check_ubam(ubam_output, inputs, output, rrna, bam_output=False, parse_wanted
         if not wanted(p):
             raise RuntimeError("--ubam_output: the text of {} does not stay on the device (the device reader does not take this input "
                                "or the ingest switches keep it on the host)".format(p) + tail)
+    return names
 
 
 def check_read_report(path, output, rrna, is_paired, ensure, bam_output=False):
@@ -1939,6 +1965,15 @@ none: give label based on the mean probability of read pair.
                            'letters of =ACMGRSVTWYHKDBN in either case (U as T, anything else N), qualities clamped to 0..93 (FASTA:\n'
                            'absent), no tags. The header is @HD VN:1.6 SO:unsorted GO:query; no @PG line is added. A name of more\n'
                            'than 254 bytes ends the run with an error behind the chunks in front of it.')
+    args.add_argument('--ubam_tags', default=None, type=str, metavar='LIST',
+                      help='(extension) with --ubam_output: LIST = tag names separated by commas (MM,ML,RG; at most 16). Every BAM record\n'
+                           'written carries the listed tags that the comment of its header line holds in SAM\'s text form -\n'
+                           '@name<TAB>MM:Z:...<TAB>ML:B:C,... (what --bam_tags, samtools fastq -T and dorado --emit-fastq write) - in\n'
+                           'comment order; an integer takes the smallest type that holds it. The comment is what stands behind the\n'
+                           'one byte that ends the name, split at TABs; fields that are no tag (1:N:0:ACGT), tags that are not listed\n'
+                           'and a listed name\'s second field are ignored. Float-typed values (f, B:f) are NOT copied; they are\n'
+                           'counted. A record with a listed tag whose value is not what its type allows gets no tags and is\n'
+                           'counted. Parsed and encoded on the GPU. The header stays @HD only: no @RG line is made up for RG:Z values.')
     args.add_argument('--read_groups', action='store_true',
                       help='(extension) BAM input with --summary: the summary gains "read_groups" - units (reads or pairs) and bases per\n'
                            'label for every @RG line of the header of the first -i file (by the records\' RG:Z tag; a pair counts in\n'
@@ -1983,7 +2018,7 @@ def main(argv=None, log_level=None):
     # (in front of check_bam: several ranks are refused for the split as such, with or without --bam_shard)
     check_split_groups(args.split_groups, args.input, args.output, args.rrna, args.ensure, args.read_report, args.summary, args.regions,
                        args.bam_output, args.interleaved)
-    check_ubam(args.ubam_output, args.input, args.output, args.rrna, args.bam_output)
+    check_ubam(args.ubam_output, args.input, args.output, args.rrna, args.bam_output, ubam_tags=args.ubam_tags)
     check_bam(args.input, args.output, args.rrna, args.bam_output, args.bam_shard, args.interleaved, ubam_output=args.ubam_output)
     check_read_groups(args.read_groups, args.summary, args.input, args.bam_shard)
     check_bam_tags(args.bam_tags, args.input, args.bam_output, floats=args.bam_tag_floats)

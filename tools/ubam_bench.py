@@ -11,6 +11,10 @@ JSON line per measurement and appends it to --out (default profiles/ubam_bench.j
           parent's behaviour and the yardstick). One untimed warm-up call of each leg, then `--calls` timed calls of each, the legs
           ALTERNATING in one process (model load excluded: Predictor.timing["detect_s"]); the ratio of the medians, whether the
           with-flag median lies inside the yardstick's spread, the bytes written and the peak of torch's allocator on both legs.
+  --tags  the legs of --ubam_tags instead (into profiles/ubam_tags_bench.jsonl). kernel: rd_bam_encode_ex with listed names on 2^20
+          reads of 100 bp with '\\tRG:Z:lib7' and on 8,192 reads of 10 kb with MM:Z 2 kB + ML:B:C x 2,000, against rd_bam_encode on the
+          same records without the comment, alternating. cli: the 100 bp file with the RG comment, --ubam_output with and without
+          --ubam_tags RG.
 The input is written by a process that never touches the GPU."""
 import argparse
 import json
@@ -116,28 +120,164 @@ def bench_cli(d, reads, calls):
           "counters": dict(last["fq_to_ubam"]._ubam_total[0]), "which_pass_holds_the_time": "not measured"})
 
 
+def _with_comment(fq, comment):
+    """the rows of bam_bench._rows with `comment` (uint8[n, c], or bytes for every row) behind the names"""
+    import numpy as np
+    import bam_bench
+    n = fq.shape[0]
+    if isinstance(comment, bytes):
+        comment = np.broadcast_to(np.frombuffer(comment, np.uint8), (n, len(comment)))
+    return np.ascontiguousarray(np.concatenate([fq[:, :bam_bench.NAME], comment, fq[:, bam_bench.NAME:]], axis=1))
+
+
+def _mm_ml(n, seed):
+    """'\\tMM:Z:C+m?' ',d' x 1,000 ';' (2 kB) and '\\tML:B:C' ',ddd' x 2,000 (values 100..255: rows of one width), per row"""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    mm = np.empty((n, 1000, 2), np.uint8)
+    mm[:, :, 0] = ord(",")
+    mm[:, :, 1] = 48 + rng.integers(0, 10, (n, 1000), dtype=np.uint8)
+    v = rng.integers(100, 256, (n, 2000))
+    ml = np.empty((n, 2000, 4), np.uint8)
+    ml[:, :, 0] = ord(",")
+    ml[:, :, 1], ml[:, :, 2], ml[:, :, 3] = 48 + v // 100, 48 + (v // 10) % 10, 48 + v % 10
+    head = lambda t: np.broadcast_to(np.frombuffer(t, np.uint8), (n, len(t)))      # noqa: E731
+    return np.concatenate([head(b"\tMM:Z:C+m?"), mm.reshape(n, -1), head(b";\tML:B:C"), ml.reshape(n, -1)], axis=1)
+
+
+def _alternate(fns, calls, warm=3):
+    """{leg: sorted us per call} of the legs, ALTERNATING in one process, by device events"""
+    import torch
+    for fn in fns.values():
+        for _ in range(warm):
+            fn()
+    ev = {k: [] for k in fns}
+    for _ in range(calls):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            ev[k].append((a, b))
+    torch.cuda.synchronize()
+    return {k: sorted(a.elapsed_time(b) * 1e3 for a, b in v) for k, v in ev.items()}
+
+
+def bench_kernel_tags(calls=20):
+    """rd_bam_encode_ex with listed names on a resident chunk whose header lines carry a comment, against rd_bam_encode on the SAME
+    records with the comment dropped - this build's n_names == 0 instances, the launches the parent makes; the parent's own binary is
+    not loaded next to it -, the two alternating. Bytes moved by the tags leg: the text read once and the comments twice more (the
+    count and the tag pass), the raw bytes written once and the tag bytes once more (zeros, then the tags), per record 80 bytes of
+    tables and workspace and 48 per listed name."""
+    import numpy as np
+    import torch
+    import bam_bench
+    from ribodetector_amd import bam, ubam
+    dev = torch.device("cuda:0")
+    for shape, n, length, names in (("short", 1 << 20, 100, [b"RG"]), ("long", 8192, 10000, [b"MM", b"ML"])):
+        step = max(1, (64 << 20) // (2 * length))
+        fq = np.concatenate([bam_bench._rows(min(step, n - f), f, length, seed=7 + f // step)[0] for f in range(0, n, step)])
+        tagged = _with_comment(fq, b"\tRG:Z:lib7" if shape == "short" else _mm_ml(n, 5))
+        legs, keep = {}, {}
+        for leg, rows, tags in (("tags", tagged, names), ("no_comment", fq, [])):
+            text = torch.from_numpy(rows.reshape(-1)).to(dev)
+            rs = torch.arange(n + 1, dtype=torch.int64, device=dev) * rows.shape[1]
+            so = (rs[:-1] + rows.shape[1] - 2 * length - 4).contiguous()
+            sl = torch.full((n,), length, dtype=torch.int32, device=dev)
+            cap = bam.ubam_bound(text.numel(), n)
+            raw = torch.empty(((cap + 255) // 256) * 256 + 256, dtype=torch.uint8, device=dev)
+            keep[leg] = (text, rs, so, sl, cap, raw, tags)
+            legs[leg] = (lambda a: (lambda: ubam.encode(a[0], a[1], a[2], a[3], n, ubam.flags_word(), raw_cap=a[4], raw=a[5], tags=a[6])))(keep[leg])
+        us = _alternate(legs, calls)
+        text, rs, so, sl, cap, raw, tags = keep["tags"]
+        _, raw_start, info = ubam.encode(text, rs, so, sl, n, ubam.flags_word(), raw_cap=cap, raw=raw, tags=tags)
+        info = info.cpu().tolist()
+        k = n // 2
+        a, b = int(raw_start[k]), int(raw_start[k + 1])
+        assert info[3] == 0 and info[0] == n and info[8] == 0 and bytes(raw[a:b].cpu().numpy()) == bam.from_fastq(tagged[k].tobytes(), tags=tags), info
+        comment = (tagged.shape[1] - fq.shape[1]) * n
+        tag_bytes = info[1] - len(bam.from_fastq(fq[k].tobytes())) * n
+        med = {leg: statistics.median(v) for leg, v in us.items()}
+        moved = text.numel() + 2 * comment + info[1] + tag_bytes + n * (80 + 48 * len(tags))
+        emit({"measurement": "kernel_ubam_tags", "what": "rd_bam_encode_ex against rd_bam_encode on the text without the comment", "shape": shape,
+              "read_len": length, "records": n, "names": [t.decode() for t in tags], "text_bytes": text.numel(), "comment_bytes": comment,
+              "raw_bytes": info[1], "tag_bytes": tag_bytes, "copied": info[10:], "calls": calls, "us_per_call": {leg: _us(v) for leg, v in us.items()},
+              "ratio_of_medians_tags_over_no_comment": round(med["tags"] / med["no_comment"], 3), "bytes_moved": moved,
+              "TB_per_s": round(moved / med["tags"] / 1e6, 3), "fraction_of_hbm_bound_pass_at_8TBps": round(moved / 8e12 / (med["tags"] * 1e-6), 4),
+              "yardstick": "this build's rd_bam_encode (n_names == 0); the parent's binary next to it: not measured",
+              "which_pass_holds_the_time": "not measured"})
+        del keep, legs, text, raw
+        torch.cuda.empty_cache()
+
+
+def _make_tagged(job):
+    """_make's file with '\\tRG:Z:lib7' behind every name"""
+    import bam_bench
+    path, reads = job
+    if os.path.exists(path):
+        return
+    step = 1 << 18
+    with open(path + ".tmp", "wb") as fh:
+        for first in range(0, reads, step):
+            fh.write(_with_comment(bam_bench._rows(min(step, reads - first), first, 100, seed=1000 + first // step)[0], b"\tRG:Z:lib7").tobytes())
+    os.replace(path + ".tmp", path)
+
+
+def bench_cli_tags(d, reads, calls):
+    """`reads` reads of 100 bp with '\\tRG:Z:lib7': --ubam_output with and without --ubam_tags RG, the legs alternating"""
+    import torch
+    from ribodetector_amd import detect
+    src = os.path.join(d, "se_rg_%d.fq" % reads)
+    argv = {"ubam": ["-l", "100", "-i", src, "-o", os.path.join(d, "o_plain.bam"), "--ubam_output"],
+            "ubam_tags": ["-l", "100", "-i", src, "-o", os.path.join(d, "o_tags.bam"), "--ubam_output", "--ubam_tags", "RG"]}
+    for k in argv:
+        detect.main(argv[k], log_level="WARNING")
+    secs, peak, last = {k: [] for k in argv}, {}, {}
+    for _ in range(calls):
+        for k in argv:
+            torch.cuda.reset_peak_memory_stats()
+            last[k] = detect.main(argv[k], log_level="WARNING")
+            secs[k].append(last[k].timing["detect_s"])
+            peak[k] = max(peak.get(k, 0), torch.cuda.max_memory_allocated())
+    rate = {k: sorted(reads / s for s in v) for k, v in secs.items()}
+    med = {k: statistics.median(v) for k, v in rate.items()}
+    yard, m = rate["ubam"], med["ubam_tags"]
+    outside = 0.0 if yard[0] <= m <= yard[-1] else (m / yard[0] - 1 if m < yard[0] else m / yard[-1] - 1)
+    emit({"measurement": "short_ubam_tags", "reads": reads, "read_len": 100, "calls": calls, "flow": "single-end x.fq with RG:Z comments -> .bam --ubam_output | + --ubam_tags RG",
+          "input_bytes": os.path.getsize(src), "output_bytes": {k: os.path.getsize(v[5]) for k, v in argv.items()},
+          "reads_per_s": {k: {"median": round(statistics.median(v)), "lowest": round(v[0]), "highest": round(v[-1])} for k, v in rate.items()},
+          "ratio_of_medians": round(m / med["ubam"], 4), "with_flag_median_inside_no_flag_spread": bool(outside == 0.0),
+          "outside_the_spread_by": round(outside, 4), "peak_allocated_MB": {k: round(v / 1e6) for k, v in peak.items()},
+          "flag_adds_MB": round((peak["ubam_tags"] - peak["ubam"]) / 1e6), "tag_counts": last["ubam_tags"]._ubam_tag_total[0],
+          "second_calls": last["ubam_tags"]._ubam[0].repeats, "which_pass_holds_the_time": "not measured"})
+
+
 def main():
     global OUT
     ap = argparse.ArgumentParser()
+    ap.add_argument("--tags", action="store_true", help="the --ubam_tags legs (default --out: profiles/ubam_tags_bench.jsonl)")
     ap.add_argument("--reads", type=int, default=1 << 22)
     ap.add_argument("--calls", type=int, default=3)
     ap.add_argument("--only", default=None, choices=["kernel", "cli"])
     ap.add_argument("--keep", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ubam_bench.jsonl"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    OUT = a.out
+    OUT = a.out or os.path.join(ROOT, "profiles", "ubam_tags_bench.jsonl" if a.tags else "ubam_bench.jsonl")
     d = a.keep or tempfile.mkdtemp(prefix="rdubam", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
     os.makedirs(d, exist_ok=True)
     try:
         if a.only != "kernel":
             import multiprocessing as mp
             with mp.get_context("spawn").Pool(1) as pool:          # (before anything initialises the GPU)
-                pool.map(_make, [(os.path.join(d, "se_%d.fq" % a.reads), a.reads)])
+                if a.tags:
+                    pool.map(_make_tagged, [(os.path.join(d, "se_rg_%d.fq" % a.reads), a.reads)])
+                else:
+                    pool.map(_make, [(os.path.join(d, "se_%d.fq" % a.reads), a.reads)])
         import ribodetector_amd  # noqa: F401
         if a.only != "cli":
-            bench_kernel()
+            bench_kernel_tags() if a.tags else bench_kernel()
         if a.only != "kernel":
-            bench_cli(d, a.reads, a.calls)
+            bench_cli_tags(d, a.reads, a.calls) if a.tags else bench_cli(d, a.reads, a.calls)
     finally:
         if not a.keep:
             shutil.rmtree(d, ignore_errors=True)
