@@ -607,7 +607,24 @@ RD_API int rd_bam_encode(const uint8_t *text, int64_t text_bytes, const int64_t 
  * field of t text bytes makes at most max(t, 2 t - 4) tag bytes, so the bound of rd_bam_encode plus the comments' bytes always holds
  * the records, and real comments shrink. A header line without '\n' inside its record is fault 2. workspace of
  * rd_bam_encode_tags_workspace_bytes(n_rec, n_names) (n_names == 0: rd_bam_encode_workspace_bytes(n_rec)). Every offset the comment
- * walk follows is compared with the record's end before it is read. */
+ * walk follows is compared with the record's end before it is read.
+ * flags | RD_UBAM_TAG_FLOATS (CLI extension `--ubam_tag_floats`; bit 28 - bits 0, 4..15 and 16..27 are taken): f and B:f values become
+ * float32 tags instead of being left out. An f value is of the syntax of rd_float_parse -> XY f and its 4 bytes; a B:f value is 'f', then
+ * ',value' per element ('XY:B:f' alone: none) -> XY B f count:uint32 and the elements. Such a tag counts as copied ([10 + j]). A value
+ * or element that is not of the syntax, an empty element, a trailing comma or a byte behind 'f' that is no comma makes the record
+ * malformed; a value, or any element, of more than 17 significant digits leaves the tag out and adds 1 to [9], which then counts
+ * nothing else. info keeps its layout, the workspace its size, and an f field of t >= 6 text bytes makes 7, a B:f field of t >= 6 + 2 n
+ * makes 8 + 4 n: the same bound. With n_names == 0, or passed to rd_bam_encode, the bit is RD_E_INVALID.
+ * rd_float_parse: the texts of n float values as float32 bit patterns, the rule of ribodetector_amd/bam.py (float_from_text). Value k is
+ * text [dev] bytes [start[k], start[k + 1]), start [dev] int64[n + 1]; every offset is compared with start[n] before it is read (an
+ * entry outside 0 <= start[k] <= start[k + 1] <= start[n] gives status 1). Syntax: [+-]? ( D+ | D* '.' D+ ) ( [eE] [+-]? D{1,4} )? with
+ * D = [0-9], or [+-]? inf / nan in any letter case. bits [dev] uint32[n]: inf 0x7f800000, nan 0x7fc00000, the sign bit for '-'; else, with
+ * M the digits without their leading and trailing zeros and v = M 10^q the EXACT value, the float32 nearest to v, ties to the even
+ * mantissa, denormals included, in one rounding (v >= 2^128 - 2^103: infinity; v <= 2^-150: zero). status [dev] uint8[n]: 0 converted,
+ * 1 not of the syntax, 2 more than 17 significant digits (bits is 0 for 1 and 2). Integer arithmetic, no double (csrc/
+ * rd_float_parse.hpp). One lane per value. n == 0: a no-op; a null pointer: RD_E_INVALID. Asynchronous on `stream`. */
+#define RD_UBAM_TAG_FLOATS (1u << 28)
+RD_API int rd_float_parse(const uint8_t *text, const int64_t *start, int64_t n, uint32_t *bits, uint8_t *status, void *stream);
 RD_API size_t rd_bam_encode_tags_workspace_bytes(int64_t n_rec, int32_t n_names);
 RD_API int rd_bam_encode_ex(const uint8_t *text, int64_t text_bytes, const int64_t *rec_start, const int64_t *seq_off, const int32_t *seq_len,
                             int64_t n_rec, int64_t rec_first, int32_t rec_stride, uint32_t flags, const uint8_t *names, int32_t n_names,

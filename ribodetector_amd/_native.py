@@ -31,7 +31,7 @@ SYMBOLS = [
     "rd_pair_split", "rd_pair_expand_labels",
     "rd_summary_words", "rd_summary_accumulate",
     "rd_bam_tag_find", "rd_bam_group_rows", "rd_bam_group_accumulate",
-    "rd_bam_tag_splice_workspace_bytes", "rd_bam_tag_splice", "rd_bam_tag_splice_ex", "rd_float_text",
+    "rd_bam_tag_splice_workspace_bytes", "rd_bam_tag_splice", "rd_bam_tag_splice_ex", "rd_float_text", "rd_float_parse",
     "rd_bam_encode_workspace_bytes", "rd_bam_encode", "rd_bam_encode_tags_workspace_bytes", "rd_bam_encode_ex",
     "rd_window_workspace_bytes", "rd_window_plan", "rd_window_fill", "rd_window_fuse",
     "rd_region_workspace_bytes", "rd_region_format",
@@ -46,6 +46,7 @@ GROUPS_MAX = 65536      # RD_GROUPS_MAX: the most read groups a dictionary of rd
 BAM_TAGS_MAX = 16       # RD_BAM_TAGS_MAX: the most tags rd_bam_tag_splice copies into the header lines
 BAM_TAGS_FLOATS = 1     # RD_BAM_TAGS_FLOATS: the flag of rd_bam_tag_splice_ex that formats f and B:f values
 UBAM_FASTA, UBAM_EVEN_SHIFT, UBAM_ODD_SHIFT = 1, 4, 16      # RD_UBAM_*: the flags word of rd_bam_encode
+UBAM_TAG_FLOATS = 1 << 28   # RD_UBAM_TAG_FLOATS: the flag of rd_bam_encode_ex that converts f and B:f values
 FLOAT_TEXT_SLOT = 16    # bytes per value in the text rd_float_text writes
 SPLIT_GROUPS_MAX = 1024     # RD_SPLIT_GROUPS_MAX: the most declared read groups a run splits its outputs by (--split_groups)
 GROUP_KEYS_MAX = 16384      # RD_GROUP_KEYS_MAX: the most keys of rd_group_pack / rd_gz_compress_grouped
@@ -155,6 +156,7 @@ def lib():
     L.rd_bam_tag_splice.argtypes = [vp, i64, vp, vp, i64, vp, i64, C.c_char_p, i32, vp, sz, vp, vp, vp, sz, vp]
     L.rd_bam_tag_splice_ex.argtypes = [vp, i64, vp, vp, i64, vp, i64, C.c_char_p, i32, vp, sz, vp, vp, vp, sz, C.c_uint32, vp]
     L.rd_float_text.argtypes = [vp, i64, vp, vp, vp]
+    L.rd_float_parse.argtypes = [vp, vp, i64, vp, vp, vp]
     L.rd_bam_encode_workspace_bytes.argtypes = [i64]
     L.rd_bam_encode_workspace_bytes.restype = sz
     L.rd_bam_encode.argtypes = [vp, i64, vp, vp, vp, i64, i64, i32, C.c_uint32, vp, sz, vp, vp, vp, sz, vp]

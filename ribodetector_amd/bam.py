@@ -43,6 +43,7 @@ run, '*' when empty), its bases as the letters of CODES (either case, U as T, an
 absent) and the flag 4 / 77 / 141; an output file is encode_header((), UBAM_HEADER_TEXT) and the selected records in BGZF members.
 """
 import os
+import re
 import struct
 import zlib
 
@@ -491,7 +492,69 @@ def ubam_comment(header_line):
     return None if end < 0 else body[end + 1:]
 
 
-def tags_from_comment(header_line, tags):
+FLOAT_SKIPPED = -1               # float_from_text: the syntax is right, but the value has more than FLOAT_DIGITS significant digits
+FLOAT_DIGITS = 17                # %.9g of a float, %.17g of a double, repr(): M < 10^17 < 2^57 bounds the device arithmetic
+_FLOAT_TEXT = re.compile(rb"([+-]?)(?:(?:([0-9]+)|([0-9]*)\.([0-9]+))(?:[eE]([+-]?[0-9]{1,4}))?|([iI][nN][fF]|[nN][aA][nN]))")
+
+
+def float_from_text(text):
+    """the bit pattern of the float32 that the text of an f value stands for (detect.py --ubam_tag_floats; device side
+    csrc/rd_float_parse.hpp, C ABI rd_float_parse): the inverse of float_g, stated in whole numbers. None: not of the syntax
+        [+-]? ( D+ | D* '.' D+ ) ( [eE] [+-]? D{1,4} )?   or   [+-]? 'inf' / 'nan' in any letter case        (D = [0-9])
+    - SAM's own grammar: a fraction exists only behind a point, '5.' and '1e' are no values, nor are hex floats, 'infinity', 'nan(1)'.
+    inf is 0x7f800000, nan 0x7fc00000, the sign bit set for '-'. Else the integer and fraction digits, joined, without their leading
+    and trailing zeros, are the integer M of s digits, and the value is EXACTLY v = M 10^q, q = the written exponent - the fraction's
+    length + the trailing zeros dropped. M = 0 is +-0. s > FLOAT_DIGITS: FLOAT_SKIPPED. Else the float32 nearest to v, ties to the
+    even mantissa, denormals included, in ONE rounding: v >= 2^128 - 2^103 is infinity, v <= 2^-150 zero."""
+    m = _FLOAT_TEXT.fullmatch(bytes(text))
+    if m is None:
+        return None
+    sign = 0x80000000 if m.group(1) == b"-" else 0
+    if m.group(6):
+        return sign | (0x7f800000 if m.group(6)[:1] in b"iI" else 0x7fc00000)
+    whole, frac = (m.group(2), b"") if m.group(2) is not None else (m.group(3), m.group(4))
+    digits = (whole + frac).lstrip(b"0")
+    stripped = digits.rstrip(b"0")
+    if not stripped:
+        return sign
+    if len(stripped) > FLOAT_DIGITS:
+        return FLOAT_SKIPPED
+    M, s = int(stripped), len(stripped)
+    q = int(m.group(5) or 0) - len(frac) + len(digits) - s
+    if s + q > 39:                                        # v >= 10^39 > 2^128
+        return sign | 0x7f800000
+    if s + q < -45:                                       # v < 10^-46 < 2^-150
+        return sign
+    num, den = (M * 10 ** q, 1) if q >= 0 else (M, 10 ** -q)
+    e = num.bit_length() - den.bit_length()               # floor(log2 v) or one more
+    if (num << -e if e < 0 else num) < (den << e if e > 0 else den):
+        e -= 1
+    E = max(e, -126)                                      # the exponent of the result's ulp is E - 23
+    sh = E - 23
+    a, b = (num << -sh, den) if sh < 0 else (num, den << sh)
+    n, r = divmod(a, b)
+    if 2 * r > b or (2 * r == b and n & 1):
+        n += 1
+    bits = ((E + 126) << 23) + n                          # n < 2^23: a denormal; n = 2^24: the rounding carried into the next exponent
+    return sign | min(bits, 0x7f800000)
+
+
+def _float_tag(t, v):
+    """the bytes behind the name of an f value / a B:f value v (behind 'XY:T:') under floats=True: None malformed, FLOAT_SKIPPED"""
+    if t == b"f":
+        x = float_from_text(v)
+        return x if x is None or x == FLOAT_SKIPPED else b"f" + struct.pack("<I", x)
+    if len(v) > 1 and v[1] != 44:
+        return None
+    vals = [float_from_text(e) for e in v[2:].split(b",")] if len(v) > 1 else []
+    if any(x is None for x in vals):
+        return None
+    if any(x == FLOAT_SKIPPED for x in vals):
+        return FLOAT_SKIPPED
+    return b"Bf" + struct.pack("<I%dI" % len(vals), len(vals), *vals)
+
+
+def tags_from_comment(header_line, tags, floats=False):
     """(tag_bytes, copied, malformed, floats) of a header line and the listed names (2 bytes each): tag_bytes = the optional fields
     that go behind the record's qualities, in COMMENT order; copied = one bool per listed name; malformed = the record gets no tags
     (tag_bytes empty, copied all False, floats 0); floats = the f and B:f values, which are left out.
@@ -503,10 +566,14 @@ def tags_from_comment(header_line, tags):
       Z  zero or more bytes 0x20..0x7E -> XY Z bytes NUL
       H  an even number of hex digits -> XY H bytes NUL
       B  a subtype of cCsSiI, then ',int' per element (the syntax of i, inside the subtype's range) -> XY B s count:uint32 elements
-      f, B with subtype f: left out, counted
+      f, B with subtype f: left out, counted - the value is not looked at
+    floats=True (--ubam_tag_floats): an f value is float_from_text's float32 -> XY f bits; a B:f value is 'f', then ',value' per element
+    ('XY:B:f' alone: none) -> XY B f count:uint32 bits...; such a tag counts as copied. A value - or an element - that is not of
+    float_from_text's syntax, an empty element, a trailing comma, a byte behind 'f' that is no comma: malformed. A value or an element
+    of more than FLOAT_DIGITS significant digits (FLOAT_SKIPPED): the tag is left out and adds 1 to floats.
     Anything else - an empty A / i / B value, a bad digit, a value out of range, an unknown subtype, an empty element or a trailing
     comma, odd or non-hex H, a byte outside 0x20..0x7E - is malformed."""
-    tags = [bytes(t) for t in tags]
+    tags, floats_on = [bytes(t) for t in tags], bool(floats)
     bad = (b"", [False] * len(tags), True, 0)
     comment = ubam_comment(header_line)
     out, copied, floats, seen = [], [False] * len(tags), 0, set()
@@ -534,8 +601,12 @@ def tags_from_comment(header_line, tags):
                 return bad
             enc = t + v + b"\0"
         elif t == b"f" or v[:1] == b"f":
-            floats += 1
-            continue
+            enc = _float_tag(t, v) if floats_on else FLOAT_SKIPPED
+            if enc is None:
+                return bad
+            if enc == FLOAT_SKIPPED:
+                floats += 1
+                continue
         else:
             if not v or v[0] not in _B_RANGE or (len(v) > 1 and v[1] != 44):
                 return bad
@@ -549,12 +620,12 @@ def tags_from_comment(header_line, tags):
     return b"".join(out), copied, False, floats
 
 
-def ubam_tag_counts(text, tags, fasta=False):
+def ubam_tag_counts(text, tags, fasta=False, floats=False):
     """the counters of a run with --ubam_tags over the records of `text`: {"copied": [records in which name j was copied],
     "malformed_records": ..., "float_values_skipped": ...}"""
     copied, mal, fl = [0] * len(tags), 0, 0
     for head, _, _ in _text_records(text, fasta):
-        _, c, m, f = tags_from_comment(head, tags)
+        _, c, m, f = tags_from_comment(head, tags, floats)
         mal += bool(m)
         fl += f
         for j, x in enumerate(c):
@@ -562,12 +633,13 @@ def ubam_tag_counts(text, tags, fasta=False):
     return {"copied": copied, "malformed_records": mal, "float_values_skipped": fl}
 
 
-def from_fastq(text, n_mates=1, mate=0, fasta=False, tags=None):
+def from_fastq(text, n_mates=1, mate=0, fasta=False, tags=None, floats=False):
     """the BAM records (their bytes, joined; no header) of FASTQ - or, fasta=True, FASTA - text: what --ubam_output makes of a file's
     records. n_mates: 1 single-end, 2 a paired run; mate: 0 / 1 - which mate's file the text is -, or INTERLEAVED: the records
     alternate mate 1, mate 2. Per record: name = ubam_name; flag = UBAM_FLAGS; a base = the letter of CODES it is in either case, U as
     T, every other byte N (UBAM_LETTER); a quality = min(max(b, 33), 126) - 33 (UBAM_QUAL), FASTA: absent (0xFF throughout).
-    tags (--ubam_tags: names of 2 bytes): the record ends in tags_from_comment(header line, tags)'s bytes.
+    tags (--ubam_tags: names of 2 bytes): the record ends in tags_from_comment(header line, tags, floats)'s bytes (floats:
+    --ubam_tag_floats).
     ValueError: a name of more than 254 bytes (UBAM_NAME_ERROR), a quality line that is not as long as its sequence
     (UBAM_LENGTH_ERROR) - N counts the text's records from 0."""
     out = []
@@ -578,7 +650,7 @@ def from_fastq(text, n_mates=1, mate=0, fasta=False, tags=None):
             raise ValueError(UBAM_NAME_ERROR % k)
         if qual is not None and len(qual) != len(seq):
             raise ValueError(UBAM_LENGTH_ERROR % k)
-        extra = tags_from_comment(head, tags)[0] if tags else b""
+        extra = tags_from_comment(head, tags, floats)[0] if tags else b""
         out.append(_ubam_record(name, seq, qual, UBAM_FLAGS[(int(n_mates), m)], extra))
     return b"".join(out)
 

@@ -42,9 +42,12 @@
 //   rd_be_len_kernel<true>, the scan (without a limit: BeTagVerdict holds the total against raw_cap and REPORTS it, fault 1),
 //   rd_be_write_kernel<true>    as above; the tile writer writes the tag bytes as zeros
 //   rd_be_tag_write_kernel<L>   behind the tile writer: the tags straight into raw at each record's tag offset, by lane groups
+// RD_UBAM_TAG_FLOATS (the CLI's --ubam_tag_floats): the FLOATS = true instances of the two tag kernels turn f and B:f
+// values into float32 (rd_float_parse.hpp) instead of leaving them out; the FLOATS = false ones are the code without the flag.
 // The bound. A field of t text bytes 'XY:T:value' makes: A 4 of 6; i 3 + 1, 2 or 4 of 5 + digits (a value that needs 4 bytes has 5
 // digits); Z / H 3 + (t - 5) + 1 = t - 1; B 8 + es count of t = 6 + the elements' text, each at least ',d' = 2 bytes for es <= 4: at most
-// 8 + 2 (t - 6) = 2 t - 4, reached by an I / i array of one-digit values (and by an array without elements: 8 of 6). So a field makes at
+// 8 + 2 (t - 6) = 2 t - 4, reached by an I / i array of one-digit values (and by an array without elements: 8 of 6); f 7 of t >= 6, B:f
+// 8 + 4 n of t >= 6 + 2 n: inside the same bound. So a field makes at
 // most max(t, 2 t - 4) < 2 t bytes, a record's tags at most twice its comment, and - the comment and the byte in front of it are
 // part of the text that the bounds above count as header -           raw <= bound above + sum of max(0, tags - comment - 1).
 // Real comments shrink (an ML:B:C,255 element is 4 text bytes for 1), so a caller sizes `raw` by the bound above and repeats the
@@ -55,6 +58,7 @@
 #include "rd_report.hpp"
 #include "rd_bam_tags.hpp"
 #include "rd_bam_tagtext.hpp"
+#include "rd_float_parse.hpp"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "rd_bam_encode.hpp is written for gfx950 (wave64, 16-byte global stores)"
@@ -454,6 +458,19 @@ __device__ __forceinline__ bool bt_element(const uint8_t *__restrict__ text, int
     return bt_in_range(v, st);
 }
 
+// (RD_UBAM_TAG_FLOATS) the element behind the comma at text[q] of a B:f value that ends at fe: FP_OK when it is of fp_scan's syntax up to
+// the next comma or fe, FP_LONG when it is and has more than 17 digits, else FP_BAD
+__device__ __forceinline__ int bt_float_element(const uint8_t *__restrict__ text, int64_t q, int64_t fe, FpNum &num) {
+    int64_t end;
+    const int fs = fp_scan(text, q + 1, fe, num, end);
+    return fs == FP_BAD || (end < fe && text[end] != ',') ? FP_BAD : fs;
+}
+
+__device__ __forceinline__ int bt_float_element(const uint8_t *__restrict__ text, int64_t q, int64_t fe) {
+    FpNum num;
+    return bt_float_element(text, q, fe, num);
+}
+
 // 16 bytes of a B value at text[i] (fewer at its end fe): a bit per byte that is a comma
 __device__ __forceinline__ uint32_t bt_commas(const uint8_t *__restrict__ text, int64_t i, int64_t fe) {
     uint32_t m = 0;
@@ -477,7 +494,11 @@ __device__ __forceinline__ uint32_t bt_commas(const uint8_t *__restrict__ text, 
 // comma stands in its piece. The sums meet in shuffles behind the strided loops. Per record: the bytes of its tags (tagb) and the mask
 // of the names that are copied (0 for a malformed record); per copied name: where the field stands in the text (foff, fend) and where
 // its tag goes in the record's tag bytes (ooff) - comment order. Every offset is compared with the record's end before it is read.
-template <int L>
+// FLOATS (RD_UBAM_TAG_FLOATS): an f value is scanned by the group's first lane (fp_scan: the syntax, at most 17 digits) and makes 7
+// bytes; the elements of a B:f value are scanned like the integer ones, by the lane in whose piece their comma stands, 4 bytes each. A
+// value or element of more than 17 digits leaves the tag out and counts once ("skipped" meets in the same shuffles as "malformed").
+// Without FLOATS an f or B:f value is counted and not looked at.
+template <int L, bool FLOATS>
 __global__ __launch_bounds__(BT_THREADS) void rd_be_tag_count_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, BeTabs t, int64_t n, int n_names,
                                                                     TtNames names, int64_t *__restrict__ tagb, uint32_t *__restrict__ mask,
                                                                     int64_t *__restrict__ foff, int64_t *__restrict__ fend, int64_t *__restrict__ ooff,
@@ -531,6 +552,7 @@ __global__ __launch_bounds__(BT_THREADS) void rd_be_tag_count_kernel(const uint8
         }
         int64_t tb = 0;                                   // this lane's share of the tag's bytes
         int lbad = 0;
+        int lskip = 0;                                    // (FLOATS) a value of more than 17 digits
         bool is_float = false;
         if (j >= 0) {
             const int64_t v0 = p + 5, vl = fe - v0;
@@ -560,11 +582,19 @@ __global__ __launch_bounds__(BT_THREADS) void rd_be_tag_count_kernel(const uint8
                     }
                 }
             } else if (ty == 'f') {
-                is_float = true;
+                if constexpr (FLOATS) {
+                    if (sub == 0) {
+                        FpNum num;
+                        const int fs = fp_value(text, v0, fe, num);
+                        if (fs == FP_BAD) lbad = 1;
+                        else if (fs == FP_LONG) lskip = 1;
+                        else tb = 7;
+                    }
+                } else is_float = true;
             } else {                                      // B: a subtype, then ',int' per element
                 const uint8_t st = vl >= 1 ? text[v0] : 0;
-                if (st == 'f') is_float = true;
-                else if (!tt_is_int(st) || (vl > 1 && text[v0 + 1] != ',')) lbad = 1;
+                if (!FLOATS && st == 'f') is_float = true;
+                else if (!(tt_is_int(st) || (FLOATS && st == 'f')) || (vl > 1 && text[v0 + 1] != ',')) lbad = 1;
                 else {
                     const int es = tg_elem_size(st);
                     if (sub == 0) tb = 8;
@@ -573,6 +603,15 @@ __global__ __launch_bounds__(BT_THREADS) void rd_be_tag_count_kernel(const uint8
                         while (m) {
                             const int c = __ffs((int)m) - 1;
                             m &= m - 1;
+                            if constexpr (FLOATS) {
+                                if (st == 'f') {
+                                    const int fs = bt_float_element(text, i + c, fe);
+                                    if (fs == FP_BAD) lbad = 1;
+                                    else if (fs == FP_LONG) lskip = 1;
+                                    else tb += 4;
+                                    continue;
+                                }
+                            }
                             int64_t v;
                             if (bt_element(text, i + c, fe, st, v)) tb += es;
                             else lbad = 1;
@@ -581,10 +620,15 @@ __global__ __launch_bounds__(BT_THREADS) void rd_be_tag_count_kernel(const uint8
                 }
             }
         }
+        if constexpr (FLOATS) lbad |= lskip << 1;
 #pragma unroll
         for (int o = L / 2; o >= 1; o >>= 1) {
             tb += __shfl_xor(tb, o);
             lbad |= __shfl_xor(lbad, o);
+        }
+        if constexpr (FLOATS) {
+            is_float = (lbad & 2) != 0;                   // the tag is left out and counted once
+            lbad &= 1;
         }
         if (j >= 0) {
             seen |= 1u << j;
@@ -651,7 +695,9 @@ struct BeTagVerdict {
 // of a B array: a step takes 16 L bytes of the text, a lane counts the commas of its 16, a prefix sum of the counts over the group and a
 // running base say which element stands behind a lane's first comma, and the lane parses and stores its elements. That loop is stepped
 // by the whole wave (a ballot ends it), so the shuffles are executed by all 64 lanes. Nothing on a fault.
-template <int L>
+// FLOATS: an f value is converted by the group's first lane (fp_round) and stored as 4 bytes, an element of a B:f array likewise by the
+// lane that holds it - a tag offset has no alignment, so the bytes go one by one as the integers' do.
+template <int L, bool FLOATS>
 __global__ __launch_bounds__(BT_THREADS) void rd_be_tag_write_kernel(const uint8_t *__restrict__ text, int64_t n, int n_names, TtNames names,
                                                                     const int64_t *__restrict__ tagb, const uint32_t *__restrict__ mask,
                                                                     const int64_t *__restrict__ foff, const int64_t *__restrict__ fend,
@@ -686,6 +732,13 @@ __global__ __launch_bounds__(BT_THREADS) void rd_be_tag_write_kernel(const uint8
                     const uint8_t small = bt_small_type(v);
                     raw[o + 2] = small;
                     for (int c = 0; c < tg_elem_size(small); ++c) raw[o + 3 + c] = (uint8_t)((uint64_t)v >> (8 * c));
+                } else if (FLOATS && ty == 'f') {
+                    if constexpr (FLOATS) {
+                        FpNum num;
+                        fp_value(text, v0, fe, num);      // (FP_OK: the count pass has scanned it)
+                        const uint32_t v = fp_bits(num);
+                        for (int c = 0; c < 4; ++c) raw[o + 3 + c] = (uint8_t)(v >> (8 * c));
+                    }
                 } else if (ty == 'B') {
                     raw[o + 3] = text[v0];
                 } else {
@@ -717,7 +770,16 @@ __global__ __launch_bounds__(BT_THREADS) void rd_be_tag_write_kernel(const uint8
                 const int c = __ffs((int)cm) - 1;
                 cm &= cm - 1;
                 int64_t v;
-                bt_element(text, i + c, fe, st, v);       // (valid: the count pass has parsed it)
+                bool is_f = false;
+                if constexpr (FLOATS) {
+                    if (st == 'f') {
+                        FpNum num;
+                        bt_float_element(text, i + c, fe, num);
+                        v = (int64_t)fp_bits(num);
+                        is_f = true;
+                    }
+                }
+                if (!is_f) bt_element(text, i + c, fe, st, v);       // (valid: the count pass has parsed it)
                 uint8_t *__restrict__ q = raw + o + 8 + idx * es;
                 for (int w = 0; w < es; ++w) q[w] = (uint8_t)((uint64_t)v >> (8 * w));
                 ++idx;
@@ -745,13 +807,13 @@ struct BamEncodeWs {
     size_t total;
 };
 
-// the launches of a call with listed names, for one lane mapping of the tag passes
-template <int L>
+// the launches of a call with listed names, for one lane mapping of the tag passes (FLOATS: RD_UBAM_TAG_FLOATS)
+template <int L, bool FLOATS>
 void bam_encode_tags_launch(const uint8_t *text, int64_t text_bytes, const BeTabs &t, int64_t n_rec, uint32_t flags, const TtNames &names, int32_t n_names,
                             uint8_t *raw, int64_t cap, int64_t *raw_start, int64_t *info, const BamEncodeWs &p, unsigned grid, hipStream_t st) {
     const int64_t per = BT_THREADS / L;
     const dim3 tgrid((unsigned)((n_rec + per - 1) / per));
-    hipLaunchKernelGGL((rd_be_tag_count_kernel<L>), tgrid, dim3(BT_THREADS), 0, st, text, text_bytes, t, n_rec, (int)n_names, names, p.tagb, p.mask, p.foff, p.fend,
+    hipLaunchKernelGGL((rd_be_tag_count_kernel<L, FLOATS>), tgrid, dim3(BT_THREADS), 0, st, text, text_bytes, t, n_rec, (int)n_names, names, p.tagb, p.mask, p.foff, p.fend,
                        p.ooff, p.cnt, p.fault);
     hipLaunchKernelGGL(rd_be_len_kernel<true>, dim3(p.nb), dim3(256), 0, st, text, text_bytes, t, n_rec, flags, raw_start, p.meta, p.qoff, p.bsum, p.first_bad, p.fault,
                        p.starred, (const int64_t *)p.tagb);
@@ -760,7 +822,7 @@ void bam_encode_tags_launch(const uint8_t *text, int64_t text_bytes, const BeTab
                        ScanOut<1>{{raw_start}, {p.bsum}}, BeTagVerdict{n_rec, p.fault, p.first_bad, p.starred, p.cnt, p.tot, cap, (int)n_names, info});
     hipLaunchKernelGGL(rd_be_write_kernel<true>, dim3(grid), dim3(256), 0, st, text, t, n_rec, flags, (const uint32_t *)p.meta, (const int64_t *)p.qoff, raw_start, raw,
                        info, (const int64_t *)p.tagb);
-    hipLaunchKernelGGL((rd_be_tag_write_kernel<L>), tgrid, dim3(BT_THREADS), 0, st, text, n_rec, (int)n_names, names, (const int64_t *)p.tagb, (const uint32_t *)p.mask,
+    hipLaunchKernelGGL((rd_be_tag_write_kernel<L, FLOATS>), tgrid, dim3(BT_THREADS), 0, st, text, n_rec, (int)n_names, names, (const int64_t *)p.tagb, (const uint32_t *)p.mask,
                        (const int64_t *)p.foff, (const int64_t *)p.fend, (const int64_t *)p.ooff, (const int64_t *)raw_start, raw, (const int64_t *)info);
 }
 }  // namespace

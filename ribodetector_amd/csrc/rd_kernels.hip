@@ -35,6 +35,7 @@
 //   rd_bam_tag_splice                  the listed tags as text behind the read names of the FASTQ text (rd_bam_tagtext.hpp)
 //   rd_bam_encode                      the records of a FASTQ / FASTA chunk as unaligned BAM records: --ubam_output (rd_bam_encode.hpp)
 //   rd_float_text                      float32 values as their exact %g text; the f / B:f values of rd_bam_tag_splice_ex (rd_float_text.hpp)
+//   rd_float_parse                     the text of float values as the nearest float32; the f / B:f values of rd_bam_encode_ex (rd_float_parse.hpp)
 //   rd_window_*                        reads longer than max_len as several windows: the window table and the fusion of its logits (rd_windows.hpp)
 //   rd_region_*                        the rRNA stretches of reads classified over windows, as text lines (rd_regions.hpp)
 #include <stdlib.h>
@@ -1523,7 +1524,8 @@ int rd_bam_encode_ex(const uint8_t *text, int64_t text_bytes, const int64_t *rec
                      int32_t rec_stride, uint32_t flags, const uint8_t *names, int32_t n_names, uint8_t *raw, size_t raw_cap, int64_t *raw_start, int64_t *info,
                      void *workspace, size_t workspace_bytes, void *stream) {
     const char *fn = n_names ? "rd_bam_encode_ex" : "rd_bam_encode";
-    const uint32_t known = RD_UBAM_FASTA | (0xfffu << RD_UBAM_EVEN_SHIFT) | (0xfffu << RD_UBAM_ODD_SHIFT);
+    const uint32_t known = RD_UBAM_FASTA | (0xfffu << RD_UBAM_EVEN_SHIFT) | (0xfffu << RD_UBAM_ODD_SHIFT) | (n_names > 0 ? RD_UBAM_TAG_FLOATS : 0u);
+    if (flags & ~known & RD_UBAM_TAG_FLOATS) RD_FAIL(RD_E_INVALID, "%s: RD_UBAM_TAG_FLOATS without listed names", fn);
     if (flags & ~known) RD_FAIL(RD_E_INVALID, "%s: unknown flag bits 0x%x", fn, flags & ~known);
     if (n_rec < 0 || n_rec > 0x3fffffffLL || text_bytes < 0) RD_FAIL(RD_E_INVALID, "%s: bad n_rec or text_bytes", fn);
     if (rec_first < 0 || rec_stride < 1 || rec_first > 0x3fffffffLL) RD_FAIL(RD_E_INVALID, "%s: bad rec_first or rec_stride", fn);
@@ -1566,8 +1568,11 @@ int rd_bam_encode_ex(const uint8_t *text, int64_t text_bytes, const int64_t *rec
     if (grid > BE_GRID) grid = BE_GRID;
     if (n_names) {
         RD_HIP(hipMemsetAsync(p.cnt, 0, BT_CNT * sizeof(unsigned long long), st));
-        if (tag_lanes(text_bytes, n_rec) == 16) bam_encode_tags_launch<16>(text, text_bytes, t, n_rec, flags, nm, n_names, raw, cap, raw_start, info, p, (unsigned)grid, st);
-        else bam_encode_tags_launch<4>(text, text_bytes, t, n_rec, flags, nm, n_names, raw, cap, raw_start, info, p, (unsigned)grid, st);
+        const bool wide = tag_lanes(text_bytes, n_rec) == 16, floats = flags & RD_UBAM_TAG_FLOATS;
+        if (wide && floats) bam_encode_tags_launch<16, true>(text, text_bytes, t, n_rec, flags, nm, n_names, raw, cap, raw_start, info, p, (unsigned)grid, st);
+        else if (wide) bam_encode_tags_launch<16, false>(text, text_bytes, t, n_rec, flags, nm, n_names, raw, cap, raw_start, info, p, (unsigned)grid, st);
+        else if (floats) bam_encode_tags_launch<4, true>(text, text_bytes, t, n_rec, flags, nm, n_names, raw, cap, raw_start, info, p, (unsigned)grid, st);
+        else bam_encode_tags_launch<4, false>(text, text_bytes, t, n_rec, flags, nm, n_names, raw, cap, raw_start, info, p, (unsigned)grid, st);
         RD_HIP(hipGetLastError());
         return RD_OK;
     }
@@ -1590,6 +1595,19 @@ int rd_float_text(const uint32_t *bits, int64_t n, uint8_t *text, uint8_t *len, 
     if (((uintptr_t)bits & 3) || ((uintptr_t)text & 15)) RD_FAIL(RD_E_INVALID, "rd_float_text: bits must be 4-byte aligned, text 16-byte aligned");
     const int64_t wgs = (n + FT_THREADS - 1) / FT_THREADS;
     hipLaunchKernelGGL(rd_float_text_kernel, dim3((unsigned)(wgs < FT_MAX_WGS ? wgs : FT_MAX_WGS)), dim3(FT_THREADS), 0, (hipStream_t)stream, bits, n, text, len);
+    RD_HIP(hipGetLastError());
+    return RD_OK;
+}
+
+// the text of float values as the nearest float32 (rd_float_parse.hpp), one lane per value
+int rd_float_parse(const uint8_t *text, const int64_t *start, int64_t n, uint32_t *bits, uint8_t *status, void *stream) {
+    if (n < 0) RD_FAIL(RD_E_INVALID, "rd_float_parse: n=%lld is negative", (long long)n);
+    if (n == 0) return RD_OK;
+    if (!text || !start || !bits || !status) RD_FAIL(RD_E_INVALID, "rd_float_parse: null pointer");
+    if (((uintptr_t)start & 7) || ((uintptr_t)bits & 3)) RD_FAIL(RD_E_INVALID, "rd_float_parse: start must be 8-byte aligned, bits 4-byte aligned");
+    const int64_t wgs = (n + FP_THREADS - 1) / FP_THREADS;
+    hipLaunchKernelGGL(rd_float_parse_kernel, dim3((unsigned)(wgs < FP_MAX_WGS ? wgs : FP_MAX_WGS)), dim3(FP_THREADS), 0, (hipStream_t)stream, text, start, n, bits,
+                       status);
     RD_HIP(hipGetLastError());
     return RD_OK;
 }

@@ -55,7 +55,8 @@ submitted - and from there on the run is --bam_output's: the output kernels sele
 that is not as long as its sequence) ends the run like a mate mismatch: the chunks in front of it are written, then the ValueError.
 --ubam_tags LIST (with --ubam_output): the records carry the listed tags that the comments of their header lines hold in SAM's text form
 (rd_bam_encode_ex; bam.tags_from_comment has the rule) - the inverse of --bam_tags. The host then waits for each encode's verdict on the
-copy stream: a chunk whose records need more than their buffer is encoded once more at the size the call reported.
+copy stream: a chunk whose records need more than their buffer is encoded once more at the size the call reported. --ubam_tag_floats: the
+f and B:f values of the listed tags become float32 tags instead of being left out (bam.float_from_text has the rule; csrc/rd_float_parse.hpp).
 """
 import argparse
 import functools
@@ -329,7 +330,8 @@ class Predictor:
         self.bam_files = self.bam_output or self.ubam_output             # every output file is a BAM file, whichever way its records are made
         self._ubam = None                        # ... ubam.DeviceUbam, one per input file (run_with_chunks)
         # --ubam_tags LIST: the names whose tags the records take from their header lines' comments (None: no tags)
-        self.ubam_tags = check_ubam_tags(getattr(args, 'ubam_tags', None), self.ubam_output)
+        self.ubam_tag_floats = bool(getattr(args, 'ubam_tag_floats', False))      # ... with the f and B:f values as float32 tags
+        self.ubam_tags = check_ubam_tags(getattr(args, 'ubam_tags', None), self.ubam_output, self.ubam_tag_floats)
         self.read_groups = bool(getattr(args, 'read_groups', False))     # --summary gains the counters per BAM read group
         self.split_groups = bool(getattr(args, 'split_groups', False))   # every output file becomes a family: a file per BAM read group
         self._split = self._split_ids = None     # ... gz.DeviceGroupSelect (run_with_chunks), the declared ids in row order (detect)
@@ -1243,7 +1245,7 @@ class Predictor:
         if self._ubam is not None:
             doc["ubam_output"] = _ubammod.to_json(self._ubam_total)
             if self.ubam_tags:
-                doc["ubam_tags"] = _ubammod.to_json_tags(self.ubam_tags, self._ubam_tag_total)
+                doc["ubam_tags"] = _ubammod.to_json_tags(self.ubam_tags, self._ubam_tag_total, floats=self.ubam_tag_floats)
         _summod.write_json(path, doc)
         frac = doc["reads"]["rRNA_fraction"]
         self.logger.info('rRNA fraction: {} (summary: {})'.format("n/a" if frac is None else "%.6f" % frac, path))
@@ -1436,7 +1438,7 @@ class Predictor:
         # --ubam_output: the raw view of every chunk is made of its text, and the counters of what the BAM form changed, per input file
         self._ubam, self._ubam_seen = None, 0
         if self.ubam_output:
-            self._ubam = [_ubammod.DeviceUbam(self.device, fasta=fx.get_seq_format(p).startswith("fa"), tags=self.ubam_tags or ()) for p in self.input]
+            self._ubam = [_ubammod.DeviceUbam(self.device, fasta=fx.get_seq_format(p).startswith("fa"), tags=self.ubam_tags or (), floats=self.ubam_tag_floats) for p in self.input]
         self._win_classified = [0, 0]
         # --regions: the lines of every chunk, formatted on the device; mate 1's writer appends the pieces (and deflates a .gz file)
         self._regions = bool(self.regions_path)
@@ -1653,11 +1655,15 @@ def check_bam(inputs, output, rrna, bam_output=False, bam_shard=False, interleav
     return True
 
 
-def check_ubam_tags(ubam_tags, ubam_output):
+def check_ubam_tags(ubam_tags, ubam_output, floats=False):
     """--ubam_tags LIST (the BAM records of --ubam_output carry the listed tags of their header lines' comments;
     bam.tags_from_comment has the rule): only with --ubam_output, and a list that bam.parse_tag_list takes. Returns its names (2 bytes
-    each, list order), or None without the flag. Holds before anything touches a device."""
+    each, list order), or None without the flag. floats (--ubam_tag_floats) says what becomes of the float values of the listed tags,
+    so it needs the list. Holds before anything touches a device."""
     if ubam_tags is None:
+        if floats:
+            raise RuntimeError("--ubam_tag_floats says how --ubam_tags reads float values: give --ubam_tags LIST with it "
+                               "(checked before anything touches a device)")
         return None
     if not ubam_output:
         raise RuntimeError("--ubam_tags says which tags of the header lines' comments the BAM records of --ubam_output carry: give "
@@ -1665,15 +1671,16 @@ def check_ubam_tags(ubam_tags, ubam_output):
     return _ubammod.parse_list(ubam_tags)
 
 
-def check_ubam(ubam_output, inputs, output, rrna, bam_output=False, parse_wanted=None, ubam_tags=None):
+def check_ubam(ubam_output, inputs, output, rrna, bam_output=False, parse_wanted=None, ubam_tags=None, ubam_tag_floats=False):
     """--ubam_output (FASTQ / FASTA input written as unaligned BAM; bam.from_fastq has the rule): the rules that hold before anything
     touches a device. The input is no BAM file (--bam_output writes those as they stand); not with --bam_output; every -o / -r name
     ends with .bam / .ubam (all outputs are BAM or none is); the chunks' text lives on the device, where the records are encoded - not
     RD_DEVICE_PARSE=0 or RD_INGEST=host, and no input that the device reader turns down (parse_wanted: device_reader.
     device_parse_wanted unless given); one rank. ubam_tags (--ubam_tags LIST: the records carry the listed tags of their header lines'
-    comments, bam.tags_from_comment): only with --ubam_output, and a list that bam.parse_tag_list takes; returns its names, else None."""
+    comments, bam.tags_from_comment): only with --ubam_output, and a list that bam.parse_tag_list takes; returns its names, else None.
+    ubam_tag_floats (--ubam_tag_floats): only with --ubam_tags."""
     tail = " (checked before anything touches a device)"
-    names = check_ubam_tags(ubam_tags, ubam_output)
+    names = check_ubam_tags(ubam_tags, ubam_output, ubam_tag_floats)
     if not ubam_output:
         return None
 
@@ -1972,8 +1979,14 @@ none: give label based on the mean probability of read pair.
                            'comment order; an integer takes the smallest type that holds it. The comment is what stands behind the\n'
                            'one byte that ends the name, split at TABs; fields that are no tag (1:N:0:ACGT), tags that are not listed\n'
                            'and a listed name\'s second field are ignored. Float-typed values (f, B:f) are NOT copied; they are\n'
-                           'counted. A record with a listed tag whose value is not what its type allows gets no tags and is\n'
+                           'counted (--ubam_tag_floats converts them). A record with a listed tag whose value is not what its type allows gets no tags and is\n'
                            'counted. Parsed and encoded on the GPU. The header stays @HD only: no @RG line is made up for RG:Z values.')
+    args.add_argument('--ubam_tag_floats', action='store_true',
+                      help='(extension) with --ubam_tags: a listed XY:f:value becomes a float32 tag and XY:B:f,value,... a float32 array\n'
+                           'instead of being skipped: the float32 nearest to the exact decimal value, ties to even, denormals\n'
+                           'included (12.5, .5, 1e-3, -inf, nan; no hex floats). A value that is no such number makes the record\n'
+                           'malformed; one of more than 17 significant digits leaves its tag out and is counted. Converted on the\n'
+                           'GPU in integer arithmetic.')
     args.add_argument('--read_groups', action='store_true',
                       help='(extension) BAM input with --summary: the summary gains "read_groups" - units (reads or pairs) and bases per\n'
                            'label for every @RG line of the header of the first -i file (by the records\' RG:Z tag; a pair counts in\n'
@@ -2018,7 +2031,7 @@ def main(argv=None, log_level=None):
     # (in front of check_bam: several ranks are refused for the split as such, with or without --bam_shard)
     check_split_groups(args.split_groups, args.input, args.output, args.rrna, args.ensure, args.read_report, args.summary, args.regions,
                        args.bam_output, args.interleaved)
-    check_ubam(args.ubam_output, args.input, args.output, args.rrna, args.bam_output, ubam_tags=args.ubam_tags)
+    check_ubam(args.ubam_output, args.input, args.output, args.rrna, args.bam_output, ubam_tags=args.ubam_tags, ubam_tag_floats=args.ubam_tag_floats)
     check_bam(args.input, args.output, args.rrna, args.bam_output, args.bam_shard, args.interleaved, ubam_output=args.ubam_output)
     check_read_groups(args.read_groups, args.summary, args.input, args.bam_shard)
     check_bam_tags(args.bam_tags, args.input, args.bam_output, floats=args.bam_tag_floats)

@@ -7,6 +7,9 @@ csrc/rd_bam_encode.hpp. The rule is bam.py (from_fastq, ubam_name, UBAM_HEADER_T
 bam.tags_from_comment). A tag takes at most twice its text and real comments shrink, so the buffer keeps the same size
 (RD_UBAM_TAGS_HINT overrides it); the call reports the exact need with fault 1, and a chunk that needs more is encoded once more at
 that size - the host waits for the verdict of every call, as it does under --bam_tags.
+
+`--ubam_tag_floats`: the f and B:f values of the listed tags become float32 tags (flag RD_UBAM_TAG_FLOATS; the rule is
+bam.float_from_text, csrc/rd_float_parse.hpp) instead of being left out; float_parse is the converter alone (C ABI rd_float_parse).
 """
 import os
 
@@ -38,14 +41,17 @@ def flags_word(n_mates=1, mate=0, fasta=False):
     return (N.UBAM_FASTA if fasta else 0) | (even << N.UBAM_EVEN_SHIFT) | (odd << N.UBAM_ODD_SHIFT)
 
 
-def encode(text, rec_start, seq_off, seq_len, n_rec, flags, raw_cap=None, raw=None, rec_first=0, rec_stride=1, text_bytes=None, tags=()):
+def encode(text, rec_start, seq_off, seq_len, n_rec, flags, raw_cap=None, raw=None, rec_first=0, rec_stride=1, text_bytes=None, tags=(), floats=False):
     """one call of rd_bam_encode on the current stream: (raw, raw_start int64[n_rec + 1], info int64[8]), all on the device. raw: a
     uint8 buffer of at least raw_cap bytes (made here when None; raw_cap None: the bound of bam.ubam_bound). Asynchronous.
     tags (names of 2 bytes): one call of rd_bam_encode_ex - the records carry the listed tags of their header lines' comments, and info
-    is int64[10 + len(tags)]; fault 1 then leaves the bytes the records need in info[1]."""
+    is int64[10 + len(tags)]; fault 1 then leaves the bytes the records need in info[1]. floats (with tags): RD_UBAM_TAG_FLOATS - f and
+    B:f values become float32 tags."""
     n_rec, tags = int(n_rec), [bytes(t) for t in tags]
     if any(len(t) != 2 for t in tags):
         raise ValueError("encode: a tag has 2 bytes")
+    if floats and not tags:
+        raise ValueError("encode: floats says how the listed tags' float values are read: it needs tags")
     if text.dtype != torch.uint8 or not text.is_contiguous():
         raise TypeError("encode: text must be a contiguous uint8 tensor")
     for t, name, dt in ((rec_start, "rec_start", torch.int64), (seq_off, "seq_off", torch.int64), (seq_len, "seq_len", torch.int32)):
@@ -75,7 +81,7 @@ def encode(text, rec_start, seq_off, seq_len, n_rec, flags, raw_cap=None, raw=No
     ws = torch.empty(max(int(lib.rd_bam_encode_tags_workspace_bytes(n_rec, len(tags))), 256), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         N.check(lib.rd_bam_encode_ex(N.ptr(text), text_bytes, N.ptr(rec_start), N.ptr(seq_off), N.ptr(seq_len), n_rec, int(rec_first), int(rec_stride),
-                                     int(flags), b"".join(tags), len(tags), N.ptr(raw), raw_cap, N.ptr(raw_start), N.ptr(info), N.ptr(ws), ws.numel(),
+                                     int(flags) | (N.UBAM_TAG_FLOATS if floats else 0), b"".join(tags), len(tags), N.ptr(raw), raw_cap, N.ptr(raw_start), N.ptr(info), N.ptr(ws), ws.numel(),
                                      N.stream_ptr(dev)), "rd_bam_encode_ex")
     return raw, raw_start, info
 
@@ -89,6 +95,25 @@ def tags_hint(text_bytes, n_rec, fasta=False):
     return bam.ubam_bound(text_bytes, n_rec, fasta)
 
 
+def float_parse(texts):
+    """(bits uint32[n], status uint8[n]) of the texts of n float values (bytes each), both on the host: one call of rd_float_parse on
+    the current device's stream - bam.float_from_text on the device. status 0: converted; 1: not of the syntax; 2: more than 17
+    significant digits (bits is 0 for 1 and 2)."""
+    import numpy as np
+    texts = [bytes(t) for t in texts]
+    n = len(texts)
+    start = np.zeros(n + 1, np.int64)
+    start[1:] = np.cumsum(np.fromiter((len(t) for t in texts), np.int64, n))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    text = torch.from_numpy(np.frombuffer(b"".join(texts) or b"\0", np.uint8).copy()).to(dev)
+    st = torch.from_numpy(start).to(dev)
+    bits = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        N.check(N.lib().rd_float_parse(N.ptr(text), N.ptr(st), n, N.ptr(bits), N.ptr(status), N.stream_ptr(dev)), "rd_float_parse")
+    return bits[:n].cpu().numpy().view(np.uint32), status[:n].cpu().numpy()
+
+
 class DeviceUbam:
     """encode(chunk, mate, n_mates) -> (raw, raw_start, info): the raw view of a DeviceChunk of FASTQ (fasta: FASTA) records, all
     three on the device; mate = bam.INTERLEAVED for an interleaved chunk. Nothing waits: info (rd_bam_encode's int64[8]) is read by
@@ -98,10 +123,11 @@ class DeviceUbam:
     it on the current stream - a chunk whose records need more than their hint is encoded once more at the exact size (`repeats`
     counts them) - and info is rd_bam_encode_ex's int64[10 + len(tags)] as a host tensor; add(info) sums its tag counters too."""
 
-    def __init__(self, device, fasta=False, tags=()):
+    def __init__(self, device, fasta=False, tags=(), floats=False):
         self.device = torch.device(device)
         self.fasta = bool(fasta)
         self.tags = [bytes(t) for t in tags]
+        self.floats = bool(floats)               # --ubam_tag_floats: f and B:f values become float32 tags
         self.counts = dict.fromkeys(COUNTERS, 0)
         self.copied = [0] * len(self.tags)
         self.malformed_records = 0
@@ -110,7 +136,7 @@ class DeviceUbam:
 
     def _call(self, chunk, flags, cap):
         text, so, sl, rs = chunk.dev
-        raw, raw_start, info = encode(text, rs, so, sl, int(rs.numel()) - 1, flags, raw_cap=cap, tags=self.tags)
+        raw, raw_start, info = encode(text, rs, so, sl, int(rs.numel()) - 1, flags, raw_cap=cap, tags=self.tags, floats=self.floats)
         host = torch.empty(info.numel(), dtype=torch.int64, pin_memory=True)
         host.copy_(info, non_blocking=True)
         ev = N.new_event()
@@ -159,17 +185,21 @@ def log_line(counts_per_mate):
     return "BAM records from text: {} bases changed, {} qualities clamped, {} names starred".format(*(doc[k] for k in COUNTERS))
 
 
-def to_json_tags(tags, counts_per_mate):
+def to_json_tags(tags, counts_per_mate, floats=False):
     """the "ubam_tags" object of the summary: counts_per_mate = [tag_counts()] of a single-end or interleaved run, [mate 1's, mate
-    2's] of a two-file run (every count is then a pair)"""
+    2's] of a two-file run (every count is then a pair). floats (--ubam_tag_floats): "float_rounding" as the last key"""
     names = [bytes(t).decode() for t in tags]
     if len(counts_per_mate) == 1:
         c = counts_per_mate[0]
-        return {"tags": names, "copied": [int(x) for x in c["copied"]], "malformed_records": int(c["malformed_records"]),
-                "float_values_skipped": int(c["float_values_skipped"])}
-    return {"tags": names, "copied": [[int(c["copied"][j]) for c in counts_per_mate] for j in range(len(names))],
-            "malformed_records": [int(c["malformed_records"]) for c in counts_per_mate],
-            "float_values_skipped": [int(c["float_values_skipped"]) for c in counts_per_mate]}
+        doc = {"tags": names, "copied": [int(x) for x in c["copied"]], "malformed_records": int(c["malformed_records"]),
+               "float_values_skipped": int(c["float_values_skipped"])}
+    else:
+        doc = {"tags": names, "copied": [[int(c["copied"][j]) for c in counts_per_mate] for j in range(len(names))],
+               "malformed_records": [int(c["malformed_records"]) for c in counts_per_mate],
+               "float_values_skipped": [int(c["float_values_skipped"]) for c in counts_per_mate]}
+    if floats:
+        doc["float_rounding"] = "nearest-even"
+    return doc
 
 
 def log_line_tags(tags, counts_per_mate):

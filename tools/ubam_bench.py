@@ -15,6 +15,12 @@ JSON line per measurement and appends it to --out (default profiles/ubam_bench.j
           reads of 100 bp with '\\tRG:Z:lib7' and on 8,192 reads of 10 kb with MM:Z 2 kB + ML:B:C x 2,000, against rd_bam_encode on the
           same records without the comment, alternating. cli: the 100 bp file with the RG comment, --ubam_output with and without
           --ubam_tags RG.
+  --tags --floats  the legs of --ubam_tag_floats instead (appended to the same file). kernel: rd_float_parse ALONE on 2^24 resident
+          values - %g texts of uniform random bit patterns, and qs-like 5.0-40.0 with 4 decimals - next to rd_float_text on the same
+          patterns in the same process; rd_bam_encode_ex with the bit set on 2^20 reads of 100 bp with '\\tqs:f:dd.dddd\\tRG:Z:lib7'
+          against the SAME call on records whose qs is a qs:i of 7 digits (existing code), and on 8,192 reads of 10 kb with a B:f array
+          of 2,000 elements beside MM / ML against the same records without the bit (the array counted and left out). cli: the 100 bp
+          file with '\\tqs:f:12.3456\\tRG:Z:lib7', --ubam_output --ubam_tags qs,RG with and without --ubam_tag_floats.
 The input is written by a process that never touches the GPU."""
 import argparse
 import json
@@ -210,7 +216,7 @@ def bench_kernel_tags(calls=20):
         torch.cuda.empty_cache()
 
 
-def _make_tagged(job):
+def _make_tagged(job, comment=b"\tRG:Z:lib7"):
     """_make's file with '\\tRG:Z:lib7' behind every name"""
     import bam_bench
     path, reads = job
@@ -219,8 +225,154 @@ def _make_tagged(job):
     step = 1 << 18
     with open(path + ".tmp", "wb") as fh:
         for first in range(0, reads, step):
-            fh.write(_with_comment(bam_bench._rows(min(step, reads - first), first, 100, seed=1000 + first // step)[0], b"\tRG:Z:lib7").tobytes())
+            fh.write(_with_comment(bam_bench._rows(min(step, reads - first), first, 100, seed=1000 + first // step)[0], comment).tobytes())
     os.replace(path + ".tmp", path)
+
+
+def _make_qs(job):
+    _make_tagged(job, b"\tqs:f:12.3456\tRG:Z:lib7")
+
+
+def _digits(v, width):
+    """uint8[n, width]: the decimal digits of the whole numbers v, zero-padded"""
+    import numpy as np
+    out = np.empty((len(v), width), np.uint8)
+    for c in range(width):
+        out[:, width - 1 - c] = 48 + (v // 10 ** c) % 10
+    return out
+
+
+def bench_kernel_float_parse(calls=20):
+    """rd_float_parse alone on 2^24 resident values, next to rd_float_text on the same bit patterns. Bytes moved by the parse: the text
+    read once, 8 bytes of the table read and 5 written per value; by the formatter 4 read and 17 written."""
+    import numpy as np
+    import torch
+    from ribodetector_amd import _native as N
+    from ribodetector_amd import bam, bamtags
+    dev, n = torch.device("cuda:0"), 1 << 24
+    rng = np.random.default_rng(3)
+    for what in ("uniform_bit_patterns_as_%g", "qs_like_5_to_40_with_4_decimals"):
+        if what.startswith("uniform"):
+            bits = torch.from_numpy(rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32).view(np.int32)).to(dev)
+            slots, lens = bamtags.float_text(bits)             # the texts come from the formatter: uint8[n, 16] and their lengths
+            keep = torch.arange(16, device=dev)[None, :] < lens[:, None].to(torch.int64)
+            text = slots[keep].contiguous()
+            start = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            start[1:] = torch.cumsum(lens.to(torch.int64), 0)
+            del slots, keep
+        else:
+            v = rng.integers(50000, 400000, n)
+            rows = np.concatenate([_digits(v // 10000, 2), np.full((n, 1), ord("."), np.uint8), _digits(v % 10000, 4)], axis=1)
+            text = torch.from_numpy(rows.reshape(-1)).to(dev)
+            start = torch.arange(n + 1, dtype=torch.int64, device=dev) * 7
+            bits = torch.from_numpy((v / 10000.0).astype(np.float32).view(np.int32)).to(dev)
+        out, status = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+        slot, ln = torch.empty(16 * n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+        lib, st = N.lib(), N.stream_ptr(dev)
+        us = _alternate({"rd_float_parse": lambda: N.check(lib.rd_float_parse(N.ptr(text), N.ptr(start), n, N.ptr(out), N.ptr(status), st), "rd_float_parse"),
+                         "rd_float_text": lambda: N.check(lib.rd_float_text(N.ptr(bits), n, N.ptr(slot), N.ptr(ln), st), "rd_float_text")}, calls)
+        k = [0, 1, n // 2, n - 1]
+        host = bytes(text.cpu().numpy())
+        s = start.cpu().numpy()
+        assert int(status.max()) == 0 and [int(out[i]) & 0xffffffff for i in k] == [bam.float_from_text(host[s[i]:s[i + 1]]) for i in k]
+        med = {leg: statistics.median(v) for leg, v in us.items()}
+        moved = {"rd_float_parse": text.numel() + 13 * n, "rd_float_text": 21 * n}
+        emit({"measurement": "kernel_float_parse", "what": "rd_float_parse next to rd_float_text, alternating", "values": n, "distribution": what,
+              "text_bytes": text.numel(), "calls": calls, "us_per_call": {leg: _us(v) for leg, v in us.items()},
+              "values_per_s": {leg: round(n / m * 1e6) for leg, m in med.items()}, "bytes_moved": moved,
+              "TB_per_s": {leg: round(moved[leg] / m / 1e6, 3) for leg, m in med.items()},
+              "fraction_of_hbm_bound_pass_at_8TBps": {leg: round(moved[leg] / 8e12 / (m * 1e-6), 4) for leg, m in med.items()}})
+        del text, start, bits, out, status, slot, ln
+        torch.cuda.empty_cache()
+
+
+def bench_kernel_tag_floats(calls=20):
+    """rd_bam_encode_ex with RD_UBAM_TAG_FLOATS. short: 2^20 reads of 100 bp, list qs,RG, floats on - '\\tqs:f:dd.dddd\\tRG:Z:lib7' against
+    the SAME call on '\\tqs:i:ddddddd\\tRG:Z:lib7' (existing code: the integer path; both comments are 24 bytes). long: 8,192 reads of
+    10 kb with MM, ML and '\\tXF:B:f' ',d.ddd' x 2,000, list MM,ML,XF, with the bit against without it (the array counted and left out)."""
+    import numpy as np
+    import torch
+    import bam_bench
+    from ribodetector_amd import bam, ubam
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(9)
+    for shape, n, length, names in (("short", 1 << 20, 100, [b"qs", b"RG"]), ("long", 8192, 10000, [b"MM", b"ML", b"XF"])):
+        step = max(1, (64 << 20) // (2 * length))
+        fq = np.concatenate([bam_bench._rows(min(step, n - f), f, length, seed=7 + f // step)[0] for f in range(0, n, step)])
+        head = lambda t: np.broadcast_to(np.frombuffer(t, np.uint8), (n, len(t)))      # noqa: E731
+        if shape == "short":
+            v = rng.integers(50000, 400000, n)
+            qs_f = np.concatenate([head(b"\tqs:f:"), _digits(v // 10000, 2), head(b"."), _digits(v % 10000, 4), head(b"\tRG:Z:lib7")], axis=1)
+            qs_i = np.concatenate([head(b"\tqs:i:"), _digits(rng.integers(10 ** 6, 10 ** 7, n), 7), head(b"\tRG:Z:lib7")], axis=1)
+            rows = {"floats": (_with_comment(fq, qs_f), True), "yardstick_qs_i": (_with_comment(fq, qs_i), True)}
+            yard = "the same call on records whose qs is a qs:i of 7 digits"
+        else:
+            el = np.empty((n, 2000, 6), np.uint8)
+            el[:, :, 0], el[:, :, 2] = ord(","), ord(".")
+            d = rng.integers(0, 10000, (n, 2000))
+            el[:, :, 1], el[:, :, 3], el[:, :, 4], el[:, :, 5] = 48 + d // 1000, 48 + (d // 100) % 10, 48 + (d // 10) % 10, 48 + d % 10
+            tagged = _with_comment(fq, np.concatenate([_mm_ml(n, 5), head(b"\tXF:B:f"), el.reshape(n, -1)], axis=1))
+            rows = {"floats": (tagged, True), "yardstick_left_out": (tagged, False)}
+            yard = "the same records and list without the bit: the array is counted and left out"
+        legs, keep = {}, {}
+        for leg, (r, fl) in rows.items():
+            text = torch.from_numpy(r.reshape(-1)).to(dev)
+            rs = torch.arange(n + 1, dtype=torch.int64, device=dev) * r.shape[1]
+            so = (rs[:-1] + r.shape[1] - 2 * length - 4).contiguous()
+            sl = torch.full((n,), length, dtype=torch.int32, device=dev)
+            cap = bam.ubam_bound(text.numel(), n)
+            raw = torch.empty(((cap + 255) // 256) * 256 + 256, dtype=torch.uint8, device=dev)
+            keep[leg] = (text, rs, so, sl, cap, raw, fl)
+            legs[leg] = (lambda a: (lambda: ubam.encode(a[0], a[1], a[2], a[3], n, ubam.flags_word(), raw_cap=a[4], raw=a[5], tags=names, floats=a[6])))(keep[leg])
+        us = _alternate(legs, calls)
+        text, rs, so, sl, cap, raw, _ = keep["floats"]
+        _, raw_start, info = ubam.encode(text, rs, so, sl, n, ubam.flags_word(), raw_cap=cap, raw=raw, tags=names, floats=True)
+        info = info.cpu().tolist()
+        k = n // 2
+        a, b = int(raw_start[k]), int(raw_start[k + 1])
+        assert info[3] == 0 and info[0] == n and info[8] == info[9] == 0 and min(info[10:]) == n, info
+        assert bytes(raw[a:b].cpu().numpy()) == bam.from_fastq(rows["floats"][0][k].tobytes(), tags=names, floats=True)
+        med = {leg: statistics.median(v) for leg, v in us.items()}
+        other = [leg for leg in med if leg != "floats"][0]
+        lo, hi = us[other][0], us[other][-1]
+        emit({"measurement": "kernel_ubam_tag_floats", "what": "rd_bam_encode_ex | RD_UBAM_TAG_FLOATS", "shape": shape, "read_len": length, "records": n,
+              "names": [t.decode() for t in names], "text_bytes": text.numel(), "raw_bytes": info[1], "calls": calls, "yardstick": yard,
+              "us_per_call": {leg: _us(v) for leg, v in us.items()}, "ratio_of_medians_floats_over_yardstick": round(med["floats"] / med[other], 3),
+              "floats_median_inside_yardstick_spread": bool(lo <= med["floats"] <= hi), "which_pass_holds_the_time": "not measured"})
+        del keep, legs, text, raw
+        torch.cuda.empty_cache()
+
+
+def bench_cli_tag_floats(d, reads, calls):
+    """`reads` reads of 100 bp with '\\tqs:f:12.3456\\tRG:Z:lib7': --ubam_output --ubam_tags qs,RG with and without --ubam_tag_floats
+    (without: the parent's behaviour and the yardstick), the legs alternating"""
+    import torch
+    from ribodetector_amd import detect
+    src = os.path.join(d, "se_qs_%d.fq" % reads)
+    base = ["-l", "100", "-i", src, "-o"]
+    argv = {"tags": base + [os.path.join(d, "o_tags.bam"), "--ubam_output", "--ubam_tags", "qs,RG"],
+            "tag_floats": base + [os.path.join(d, "o_floats.bam"), "--ubam_output", "--ubam_tags", "qs,RG", "--ubam_tag_floats"]}
+    for k in argv:
+        detect.main(argv[k], log_level="WARNING")
+    secs, peak, last = {k: [] for k in argv}, {}, {}
+    for _ in range(calls):
+        for k in argv:
+            torch.cuda.reset_peak_memory_stats()
+            last[k] = detect.main(argv[k], log_level="WARNING")
+            secs[k].append(last[k].timing["detect_s"])
+            peak[k] = max(peak.get(k, 0), torch.cuda.max_memory_allocated())
+    rate = {k: sorted(reads / s for s in v) for k, v in secs.items()}
+    med = {k: statistics.median(v) for k, v in rate.items()}
+    yard, m = rate["tags"], med["tag_floats"]
+    outside = 0.0 if yard[0] <= m <= yard[-1] else (m / yard[0] - 1 if m < yard[0] else m / yard[-1] - 1)
+    emit({"measurement": "short_ubam_tag_floats", "reads": reads, "read_len": 100, "calls": calls,
+          "flow": "single-end x.fq with qs:f and RG:Z comments -> .bam --ubam_output --ubam_tags qs,RG | + --ubam_tag_floats",
+          "input_bytes": os.path.getsize(src), "output_bytes": {k: os.path.getsize(v[5]) for k, v in argv.items()},
+          "reads_per_s": {k: {"median": round(statistics.median(v)), "lowest": round(v[0]), "highest": round(v[-1])} for k, v in rate.items()},
+          "ratio_of_medians": round(m / med["tags"], 4), "with_flag_median_inside_no_flag_spread": bool(outside == 0.0),
+          "outside_the_spread_by": round(outside, 4), "peak_allocated_MB": {k: round(v / 1e6) for k, v in peak.items()},
+          "flag_adds_MB": round((peak["tag_floats"] - peak["tags"]) / 1e6), "tag_counts": {k: last[k]._ubam_tag_total[0] for k in argv},
+          "second_calls": last["tag_floats"]._ubam[0].repeats, "which_pass_holds_the_time": "not measured"})
 
 
 def bench_cli_tags(d, reads, calls):
@@ -256,6 +408,7 @@ def main():
     global OUT
     ap = argparse.ArgumentParser()
     ap.add_argument("--tags", action="store_true", help="the --ubam_tags legs (default --out: profiles/ubam_tags_bench.jsonl)")
+    ap.add_argument("--floats", action="store_true", help="with --tags: the --ubam_tag_floats legs")
     ap.add_argument("--reads", type=int, default=1 << 22)
     ap.add_argument("--calls", type=int, default=3)
     ap.add_argument("--only", default=None, choices=["kernel", "cli"])
@@ -269,11 +422,20 @@ def main():
         if a.only != "kernel":
             import multiprocessing as mp
             with mp.get_context("spawn").Pool(1) as pool:          # (before anything initialises the GPU)
-                if a.tags:
+                if a.tags and a.floats:
+                    pool.map(_make_qs, [(os.path.join(d, "se_qs_%d.fq" % a.reads), a.reads)])
+                elif a.tags:
                     pool.map(_make_tagged, [(os.path.join(d, "se_rg_%d.fq" % a.reads), a.reads)])
                 else:
                     pool.map(_make, [(os.path.join(d, "se_%d.fq" % a.reads), a.reads)])
         import ribodetector_amd  # noqa: F401
+        if a.tags and a.floats:
+            if a.only != "cli":
+                bench_kernel_float_parse()
+                bench_kernel_tag_floats()
+            if a.only != "kernel":
+                bench_cli_tag_floats(d, a.reads, a.calls)
+            return
         if a.only != "cli":
             bench_kernel_tags() if a.tags else bench_kernel()
         if a.only != "kernel":
